@@ -22,7 +22,7 @@ $(PKG)/libdbsp_gen.so: $(PKG)/csrc/gen_lib.cpp $(PKG)/csrc/nexmark_gen.hpp inclu
 	$(CXX) $(CXXFLAGS) -shared $(PKG)/csrc/gen_lib.cpp -o $@
 
 hip: $(PKG)/libdbsp_hip.so
-$(PKG)/libdbsp_hip.so: $(PKG)/csrc/kernels.hip $(PKG)/csrc/engine.cpp $(PKG)/csrc/nexmark_gen.hpp include/dbsp_hip.h
+$(PKG)/libdbsp_hip.so: $(PKG)/csrc/kernels.hip $(PKG)/csrc/engine.cpp $(PKG)/csrc/kernels_iface.hpp $(PKG)/csrc/nexmark_gen.hpp include/dbsp_hip.h
 	$(HIPCC) $(HIPFLAGS) -shared $(PKG)/csrc/kernels.hip $(PKG)/csrc/engine.cpp \
 	    -L/opt/rocm/lib -lrccl -o $@
 

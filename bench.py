@@ -17,6 +17,11 @@ Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
 all-to-all-v over xGMI; weak scaling: each rank processes tick_events per
 tick, so the whole job covers tick_events*N events per step).
 
+A plain run does only what the headline figure needs: generate + stage the
+events, warm up, time --steps ticks, print the line.  --full adds the
+cpu_baseline and roofline legs (each a run of its own).  --dump-outputs DIR
+writes the output delta of the last timed tick as DIR/<column>.npy.
+
 Rank 0 prints ONE JSON line (driver contract).
 """
 import argparse
@@ -57,6 +62,64 @@ def generate_rank_slices(n_ticks, tick, world, rank, seed=1):
         out.append(chunk[rank * tick:(rank + 1) * tick].copy())
     st.close()
     return np.concatenate(out)
+
+
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs budget over all files
+
+
+def _exact_f64(name, col):
+    """An 8-byte integer column as float64 array(s) without losing bits:
+    one array while every value is within +-2^53, else the 32-bit halves of
+    the two's-complement pattern as <name>_hi / <name>_lo."""
+    import numpy as np
+    lim = 1 << 53
+    if col.dtype == np.uint64:
+        exact = bool((col <= lim).all())
+    else:
+        exact = bool(((col >= -lim) & (col <= lim)).all())
+    if exact:
+        return {name: col.astype(np.float64)}
+    u = col.view(np.uint64)
+    return {name + "_hi": (u >> np.uint64(32)).astype(np.float64),
+            name + "_lo": (u & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+
+
+def dump_outputs(out_dir, rows, f64_cols=()):
+    """Write what the timed path's last tick handed its caller (the output
+    delta Z-set, or q0's event Z-set) as one float64 .npy per column.  A Z-set
+    is unordered, so rows go out in canonical column-lexicographic order;
+    columns named in f64_cols hold f64 bit patterns and are written as those
+    doubles.  Past DUMP_MAX_BYTES a fixed seeded row sample (of the ordered
+    rows) is written instead, with its row indices in sample_index.npy."""
+    import numpy as np
+    names = rows.dtype.names
+    rows = rows[np.lexsort([rows[n] for n in reversed(names)])]
+    cols = {}
+    for n in names:
+        col = np.ascontiguousarray(rows[n])
+        if n in f64_cols:
+            cols[n] = col.view(np.float64)
+        else:
+            cols.update(_exact_f64(n, col))
+    max_rows = DUMP_MAX_BYTES // (8 * (len(cols) + 1))
+    if len(rows) > max_rows:
+        idx = np.sort(np.random.default_rng(0).choice(
+            len(rows), size=max_rows, replace=False))
+        cols = {n: c[idx] for n, c in cols.items()}
+        cols["sample_index"] = idx.astype(np.float64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for n, c in cols.items():
+        np.save(out_dir / f"{n}.npy", c)
+
+
+def _dump_dir(args, rank, world):
+    """--dump-outputs target of this rank (one sub-directory per rank when
+    the job is sharded), or None."""
+    if args.dump_outputs is None:
+        return None
+    d = Path(args.dump_outputs)
+    return d if world == 1 else d / f"rank{rank}"
 
 
 def run_engine(ctx_dev, query, events, n_ticks, tick, world, rank, nccl_id,
@@ -296,7 +359,7 @@ def run_c5(args, rank, world, local_rank, dist):
     n_ticks = args.warmup + args.steps
     nd = args.tick
 
-    def one_run(warm, timed):
+    def one_run(warm, timed, dump_dir=None):
         ctx = Ctx(local_rank)
         eng = Engine(ctx, query=100, rank=rank, world=world)
         eng.c5_init(args.c5_trace, nd, seed=args.seed + rank * 7919)
@@ -315,17 +378,22 @@ def run_c5(args, rank, world, local_rank, dist):
         st = {name: eng.kernel_stats(k) for k, name in
               {0: "sort_consolidate", 1: "merge", 2: "join",
                3: "aggregate"}.items()}
+        if dump_dir is not None:
+            # (key, f64 sum bits, weight) rows: per touched key at most one
+            # insertion and one retraction of the previous sum
+            dump_outputs(dump_dir, eng.output(cap=2 * nd + 1024),
+                         f64_cols=("v",))
         eng.close()
         ctx.close()
         return el, st
 
-    elapsed, _ = one_run(args.warmup, args.steps)
+    elapsed, _ = one_run(args.warmup, args.steps, _dump_dir(args, rank, world))
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     stats = None
-    if not args.no_extras and world == 1:
+    if args.full and world == 1:
         # per-kernel-class hipEvent timing needs DBSP_PROFILE=1 at ctx
         # creation: collect it from a short separate run
         os.environ["DBSP_PROFILE"] = "1"
@@ -375,7 +443,7 @@ def run_c5(args, rank, world, local_rank, dist):
                            "launches": v[2]} for k, v in stats.items()},
         },
     }
-    if not args.no_extras and world == 1:
+    if args.full and world == 1:
         result["cpu_baseline"] = c5_cpu_baseline(args.c5_trace, nd, args.seed)
     print(json.dumps(result))
 
@@ -383,21 +451,48 @@ def run_c5(args, rank, world, local_rank, dist):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=250)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed ticks (default 250; c5: 20)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--query", default="3",
                     choices=["0", "3", "4", "5", "6", "8", "c5"])
-    ap.add_argument("--tick", type=int, default=40_000)
+    ap.add_argument("--tick", type=int, default=None,
+                    help="events (c5: delta rows) per tick "
+                         "(default 40000; c5: 10M)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--c5-trace", type=int, default=1_000_000_000,
                     help="C5 trace rows (configs[4]: 1B)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cpu_baseline and roofline legs")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip cpu_baseline and roofline legs")
+                    help="accepted for old command lines; the extra legs "
+                         "only run with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed tick's output as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+
+    # configs[4] (c5): a step = one 10M-row delta; --tick keeps its meaning as
+    # rows per step, defaulting to the config's 10M (not the Nexmark 40k)
+    c5 = args.query == "c5"
+    if args.tick is None:
+        args.tick = 10_000_000 if c5 else 40_000
+    if args.steps is None:
+        args.steps = 20 if c5 else 250
+    if not c5:
+        args.query = int(args.query)
+
+    cpu_baseline = None
+    if args.full and world == 1 and not c5 and args.query != 0:
+        # first, while this process has not opened the GPU: the all-cores
+        # leg forks its workers, and they would inherit the open device
+        cpu_baseline = cpu_baseline_leg(args.query, args.tick)
+
     import torch
     if torch.cuda.is_available():
         # keep torch's notion of the current device aligned with the rank's
@@ -425,16 +520,9 @@ def main():
         tdist.broadcast(t, src=0)
         nccl_id = t.numpy()
 
-    if args.query == "c5":
-        # configs[4]: a step = one 10M-row delta; --tick keeps its meaning as
-        # rows per step, defaulting to the config's 10M (not the Nexmark 40k)
-        if args.tick == 40_000:
-            args.tick = 10_000_000
-        if args.steps == 250:
-            args.steps = 20
+    if c5:
         run_c5(args, rank, world, local_rank, dist)
         return
-    args.query = int(args.query)
 
     n_ticks = args.warmup + args.steps
     events = generate_rank_slices(n_ticks, args.tick, world, rank,
@@ -449,6 +537,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dump_dir = _dump_dir(args, rank, world)
+    if dump_dir is not None:
+        dump_outputs(dump_dir, eng.output_events(cap=args.tick + 16)
+                     if args.query == 0 else eng.output())
     eng.close()
     ctx.close()
 
@@ -477,8 +569,8 @@ def main():
             "parallelism": f"keyshard{world}" if world > 1 else "single",
         },
     }
-    if not args.no_extras and world == 1 and args.query != 0:
-        result["cpu_baseline"] = cpu_baseline_leg(args.query, args.tick)
+    if cpu_baseline is not None:
+        result["cpu_baseline"] = cpu_baseline
         result["roofline"] = roofline_leg(args.query, events, n_ticks, args.tick)
     print(json.dumps(result))
 
