@@ -595,6 +595,28 @@ struct Spine {
     }
 };
 
+// Incremental partitioned rolling aggregate with the linear weight-sum
+// aggregator (PartitionedRollingAggregate::eval, operator/time_series/
+// rolling_aggregate.rs:487-604; range_of(ts) = [ts - before, ts + after],
+// RelRange::new(Before(before), After(after)), range.rs:93-104).
+// in_sp is the input integral INCLUDING the current tick, out_sp the integral
+// of this operator's own outputs EXCLUDING it.  step() is defined below the
+// spine helpers it uses.
+struct RollingOp {
+    uint64_t before = 10000, after = 0;
+    Spine in_sp, out_sp;
+
+    // delta: consolidated rows (partition, ts, w), retained by the caller;
+    // out: the tick's consolidated output delta (p<<32|ts, sum, +-1).
+    // DBSP_ERR_INVALID (state unchanged) if a partition or time is >= 2^32.
+    dbsp_status step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out);
+
+    void clear(dbsp_ctx *c) {
+        in_sp.clear(c);
+        out_sp.clear(c);
+    }
+};
+
 // ---------------------------------------------------------------------------
 // kernel-level C ABI (device-pointer primitives; used by GPU parity tests)
 // ---------------------------------------------------------------------------
@@ -1139,6 +1161,9 @@ struct dbsp_engine {
     Spine c5_trace;   // (k, f64-bits val, +1 i64) join-side trace
     Spine c5_wint;    // f64-WEIGHTED integral of the weighed join stream
     Spine c5_out;     // aggregate output trace (k -> f64 sum bits, i64 w)
+    // query 101 state: per-auction rolling bid volume
+    RollingOp roll;
+    bool roll_stepped = false;  // rolling_init is rejected after a step
     int64_t c5_n_delta = 0;
     uint64_t c5_seed = 0;
     uint64_t c5_delta_stride = 0;
@@ -1186,7 +1211,7 @@ struct dbsp_engine {
 extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
                                           int query, int rank, int world) {
     if (query != 0 && query != 3 && query != 4 && query != 5 &&
-        query != 6 && query != 8 && query != 100)
+        query != 6 && query != 8 && query != 100 && query != 101)
         return DBSP_ERR_INVALID;
 
     dbsp_engine *e = new dbsp_engine();
@@ -1223,6 +1248,7 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
                      &e->q4_avgout, &e->q4_maxin_sp, &e->q6_a_int,
                      &e->q6_b_int, &e->q6_maxin_sp, &e->q6_fold_sp})
         s->clear(c);
+    e->roll.clear(c);
     free_batch(c, e->q4_maxout);
     free_batch(c, e->q6_maxout);
     free_batch(c, e->q6_foldout);
@@ -2254,6 +2280,171 @@ static TraceArgs trace_args_of(Spine &sp) {
         t.nb++;
     }
     return t;
+}
+
+// ---- incremental partitioned rolling aggregate (rolling_aggregate.rs
+// :487-604) ----
+// Per tick, over a consolidated delta D of nd rows:
+//   ranges   D -> merged gather ranges (p, [ts-before-after, ts+before+after])
+//            and merged affected ranges (p, [ts-after, ts+before]); a time is
+//            affected iff D has a row of its partition inside range_of(time),
+//            which is the reference's affected_range_of merged with D's own
+//            times (affected_ranges, rolling_aggregate.rs:436-456)
+//   gather   in_sp rows inside the gather ranges (they cover the sum range
+//            of every affected time), consolidated into one slice
+//   eval     radix-16 tree over the slice; every affected slice row of
+//            positive weight emits (p<<32|ts, sum over range_of(ts), +1)
+//   retract  out_sp rows inside the affected ranges, weights negated
+//   output   consolidate(retractions + insertions), appended to out_sp
+// Cost follows the rows gathered, not the trace: O(nd log) searches per
+// spine batch plus sort/tree/eval over the slice.  The explicit per-op path
+// (host length syncs between phases, as q4/q6); no chaining.
+dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
+    out = DevBatch{};
+    if (delta.n == 0) return DBSP_OK;
+    ScopedTimer timer(c, 3, 0.0);
+    const int64_t n = delta.n;
+    // the range lists depend on the delta alone and their kernel raises the
+    // precondition word, so they run before any state changes
+    uint64_t *rb = nullptr;
+    int64_t n_gather = 0, n_affected = 0;
+    int err = 0;
+    TRY(dbspk::roll_ranges(c->stream, delta.k, delta.v, n, before, after, &rb,
+                           &n_gather, &n_affected, &err));
+    if (err) return DBSP_ERR_INVALID;
+    {
+        DevBatch cpy;
+        TRY(copy_batch(c, delta, cpy));
+        TRY(in_sp.insert(c, cpy));
+    }
+    if ((int)in_sp.batches.size() > MAX_TRACE_BATCHES)
+        TRY(in_sp.consolidate_all(c));
+    if ((int)out_sp.batches.size() > MAX_TRACE_BATCHES)
+        TRY(out_sp.consolidate_all(c));
+    // gather + consolidate the slice of the input integral
+    DevBatch raw, slice;
+    TRY(dbspk::range_gather(c->stream, rb, rb + n, rb + 2 * n, n_gather,
+                            trace_args_of(in_sp), 0, 1, &raw.k, &raw.v, &raw.w,
+                            &raw.n));
+    int64_t moved = raw.n;
+    TRY(sort_consolidate_batch(c, raw, slice));
+    // insertions
+    std::vector<DevBatch> parts;
+    if (slice.n > 0) {
+        DevBatch ins;
+        TRY(dbspk::roll_eval_rows(c->stream, slice.k, slice.v, slice.w,
+                                  slice.n, delta.k, delta.v, n, before, after,
+                                  &ins.k, &ins.v, &ins.w, &ins.n));
+        moved += ins.n;
+        if (ins.n > 0) parts.push_back(ins);
+    }
+    free_batch(c, slice);
+    // retractions
+    {
+        DevBatch ret;
+        TRY(dbspk::range_gather(c->stream, rb + 3 * n, rb + 4 * n, rb + 5 * n,
+                                n_affected, trace_args_of(out_sp), 1, -1,
+                                &ret.k, &ret.v, &ret.w, &ret.n));
+        moved += 2 * ret.n;
+        if (ret.n > 0) parts.push_back(ret);
+    }
+    HIP_CHECK_ST(dbspk::cache_free(rb, c->stream));
+    if (!parts.empty()) TRY(finalize_raw(c, parts, out));
+    if (out.n > 0) {
+        DevBatch cpy;
+        TRY(copy_batch(c, out, cpy));
+        TRY(out_sp.insert(c, cpy));
+    }
+    timer.bytes = 24.0 * (double)moved;  // rows gathered + rows emitted
+    return DBSP_OK;
+}
+
+struct dbsp_rolling {
+    dbsp_ctx *ctx = nullptr;
+    RollingOp op;
+};
+
+extern "C" dbsp_status dbsp_rolling_create(dbsp_ctx *c, uint64_t before,
+                                           uint64_t after, dbsp_rolling **out) {
+    if (!c || !out) return DBSP_ERR_INVALID;
+    dbsp_rolling *r = new dbsp_rolling();
+    r->ctx = c;
+    r->op.before = before;
+    r->op.after = after;
+    *out = r;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_step(dbsp_rolling *r, const uint64_t *k,
+                                         const uint64_t *v, const int64_t *w,
+                                         int64_t n, dbsp_batch *out) {
+    if (!r || !out || n < 0) return DBSP_ERR_INVALID;
+    dbsp_ctx *c = r->ctx;
+    *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
+    if (n == 0) return DBSP_OK;
+    DevBatch raw, delta, res;
+    TRY(alloc_batch(c, n, raw));
+    HIP_CHECK_ST(hipMemcpyAsync(raw.k, k, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(raw.v, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(raw.w, w, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    TRY(sort_consolidate_batch(c, raw, delta));
+    const dbsp_status st = r->op.step(c, delta, res);
+    free_batch(c, delta);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    if (st != DBSP_OK) return st;
+    if (res.n == 0) free_batch(c, res);
+    out->k = res.k;
+    out->v = res.v;
+    out->w = res.w;
+    out->len = res.n;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_stats(dbsp_rolling *r, int64_t *in_rows,
+                                          int *in_batches, int64_t *out_rows,
+                                          int *out_batches) {
+    if (!r) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = r->op.in_sp.total();
+    if (in_batches) *in_batches = (int)r->op.in_sp.batches.size();
+    if (out_rows) *out_rows = r->op.out_sp.total();
+    if (out_batches) *out_batches = (int)r->op.out_sp.batches.size();
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_destroy(dbsp_rolling *r) {
+    if (!r) return DBSP_OK;
+    r->op.clear(r->ctx);
+    (void)hipStreamSynchronize(r->ctx->stream);
+    delete r;
+    return DBSP_OK;
+}
+
+// ---- query 101: per-auction rolling bid volume ----
+// bids.map_index(|b| (b.auction, (b.date_time, b.price)))
+//     .partitioned_rolling_aggregate_linear(...)   (the q17-class shape):
+// the flatmap weighs the price into the weight, one stream through
+// build_deltas (which also exchanges by auction on sharded ranks:
+// partitions are independent), then the operator.
+static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
+                             int64_t n) {
+    dbsp_ctx *c = e->ctx;
+    engine_free_output(e);
+    e->roll_stepped = true;
+    DevBatch d, dummy;
+    TRY(build_deltas(e, d_ev, n, d, dummy, false));
+    const dbsp_status st = e->roll.step(c, d, e->output);
+    free_batch(c, d);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return st;
+}
+
+extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
+                                                uint64_t before_ms,
+                                                uint64_t after_ms) {
+    if (!e || e->query != 101 || e->roll_stepped) return DBSP_ERR_INVALID;
+    e->roll.before = before_ms;
+    e->roll.after = after_ms;
+    return DBSP_OK;
 }
 
 // ---- q3 tick (queries/q3.rs:35-63) ----
@@ -4009,6 +4200,7 @@ extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
         case 6: return q6_step(e, d_ev, hi - lo);
         case 5: return q5_step(e, d_ev, hi - lo);
         case 8: return q8_step(e, d_ev, hi - lo);
+        case 101: return q101_step(e, d_ev, hi - lo);
     }
     return DBSP_ERR_INVALID;
 }
@@ -4055,6 +4247,7 @@ extern "C" dbsp_status dbsp_engine_step(dbsp_engine *e, const dbsp_event *events
         case 6: st = q6_step(e, d_ev, n); break;
         case 5: st = q5_step(e, d_ev, n); break;
         case 8: st = q8_step(e, d_ev, n); break;
+        case 101: st = q101_step(e, d_ev, n); break;
         default: st = DBSP_ERR_INVALID;
     }
     (void)dbspk::cache_free(d_ev, c->stream);

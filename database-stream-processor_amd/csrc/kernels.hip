@@ -2808,6 +2808,16 @@ __global__ void k_flatmap(const dbsp_event *ev, dbspk::EventCols cols, int64_t n
             if (p1) {
                 k1[pos1] = e.f3; v1[pos1] = e.f1; w1[pos1] = e.w;
             }
+        } else if (query == 101) {
+            // bids.map_index(|b| (b.auction, (b.date_time, b.price))) with
+            // the price weighed into the weight (aggregate/mod.rs:297-323):
+            // the input of partitioned_rolling_aggregate_linear
+            const bool p0 = act && e.kind == 2;
+            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
+            if (p0) {
+                k0[pos0] = e.f0; v0[pos0] = e.f3;
+                w0[pos0] = e.w * (int64_t)e.f2;
+            }
         }
     }
 }
@@ -4178,6 +4188,30 @@ __device__ inline int64_t rt_range_sum(const int64_t *w, int64_t nw,
     return sum;
 }
 
+// first row of the (k, v)-sorted rows [lo, hi) with (k, v) >= (kk, vv) /
+// > (kk, vv): a partition's time bound as a row index (shared by the batch
+// primitive below and the incremental operator's gather / eval kernels)
+__device__ inline int64_t lex_lower(const uint64_t *k, const uint64_t *v,
+                                    int64_t lo, int64_t hi, uint64_t kk,
+                                    uint64_t vv) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2;
+        const uint64_t km = k[mid];
+        if (km < kk || (km == kk && v[mid] < vv)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ inline int64_t lex_upper(const uint64_t *k, const uint64_t *v,
+                                    int64_t lo, int64_t hi, uint64_t kk,
+                                    uint64_t vv) {
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2;
+        const uint64_t km = k[mid];
+        if (km < kk || (km == kk && v[mid] <= vv)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 __global__ void k_rolling_agg(const uint64_t *k, const uint64_t *v,
                               const int64_t *w, int64_t n, RtLevels t,
                               uint64_t width, uint64_t *ok, uint64_t *ov,
@@ -4195,36 +4229,25 @@ __global__ void k_rolling_agg(const uint64_t *k, const uint64_t *v,
         }
         // time range [ts - width, ts] inclusive (range.rs:93-110, saturating)
         const uint64_t t0 = ts >= width ? ts - width : 0;
-        int64_t qlo = plo, qhi = plo;
-        {   // lower_bound of t0 and upper_bound of ts within [plo, phi)
-            int64_t lo = plo, hi = phi;
-            while (lo < hi) {
-                int64_t mid = (lo + hi) / 2;
-                if (v[mid] < t0) lo = mid + 1; else hi = mid;
-            }
-            qlo = lo;
-            hi = phi;
-            while (lo < hi) {
-                int64_t mid = (lo + hi) / 2;
-                if (v[mid] <= ts) lo = mid + 1; else hi = mid;
-            }
-            qhi = lo;
-        }
+        const int64_t qlo = lex_lower(k, v, plo, phi, p, t0);
+        const int64_t qhi = lex_upper(k, v, qlo, phi, p, ts);
         ok[i] = p;
         ov[i] = ts;
         ow[i] = rt_range_sum(w, n, t, qlo, qhi);
     }
 }
 
-dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
-                             const uint64_t *v, const int64_t *w, int64_t n,
-                             uint64_t width, uint64_t *ok, uint64_t *ov,
-                             int64_t *ow) {
-    if (n <= 0) return DBSP_OK;
-    RtLevels t{};
+#define TRY_K(x)                                                          \
+    do {                                                                  \
+        dbsp_status st_ = (x);                                            \
+        if (st_ != DBSP_OK) return st_;                                   \
+    } while (0)
+
+// build the radix-16 levels over the weight column w[0..n)
+static dbsp_status rt_build(hipStream_t s, const int64_t *w, int64_t n,
+                            RtLevels &t, int64_t **bufs) {
     int64_t cur_n = n;
     const int64_t *cur = w;
-    int64_t *bufs[RT_MAX_LEVELS] = {};
     while (cur_n > 1 && t.nl < RT_MAX_LEVELS) {
         const int64_t nn = (cur_n + RT_RADIX - 1) / RT_RADIX;
         HIP_CHECK(dbspk::cache_malloc((void **)&bufs[t.nl],
@@ -4236,10 +4259,283 @@ dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
         cur_n = nn;
         t.nl++;
     }
-    k_rolling_agg<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, t, width, ok, ov,
-                                              ow);
+    return DBSP_OK;
+}
+
+static dbsp_status rt_free(hipStream_t s, const RtLevels &t, int64_t **bufs) {
     for (int i = 0; i < t.nl; i++)
         HIP_CHECK(dbspk::cache_free(bufs[i], s));
+    return DBSP_OK;
+}
+
+dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
+                             const uint64_t *v, const int64_t *w, int64_t n,
+                             uint64_t width, uint64_t *ok, uint64_t *ov,
+                             int64_t *ow) {
+    if (n <= 0) return DBSP_OK;
+    RtLevels t{};
+    int64_t *bufs[RT_MAX_LEVELS] = {};
+    TRY_K(rt_build(s, w, n, t, bufs));
+    k_rolling_agg<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, t, width, ok, ov,
+                                              ow);
+    return rt_free(s, t, bufs);
+}
+
+// ---------------------------------------------------------------------------
+// Incremental partitioned rolling aggregate (PartitionedRollingAggregate::eval,
+// operator/time_series/rolling_aggregate.rs:487-604, linear weight-sum
+// aggregator).  Per tick the operator (engine.cpp RollingOp) touches only
+// the times the delta can affect:
+//   k_roll_heads / k_roll_ranges   delta -> merged gather + affected ranges
+//                                  (affected_ranges, rolling_aggregate.rs
+//                                  :436-456 / RelRange::affected_range_of,
+//                                  range.rs:109-120)
+//   k_range_count / k_range_emit   ranges x spine batches -> signed row copy
+//   k_roll_flags / k_roll_emit     gathered slice -> (p<<32|ts, sum, +1) for
+//                                  the affected rows of positive weight
+// Times and partitions are < 2^32 (they pack into one output key); ranges
+// saturate at 0 and at 2^32-1.
+// ---------------------------------------------------------------------------
+
+#define ROLL_TMAX 0xFFFFFFFFull
+
+__device__ inline uint64_t roll_lo(uint64_t ts, uint64_t below) {
+    return ts >= below ? ts - below : 0;
+}
+__device__ inline uint64_t roll_hi(uint64_t ts, uint64_t above) {
+    if (ts >= ROLL_TMAX) return ROLL_TMAX;
+    return above >= ROLL_TMAX - ts ? ROLL_TMAX : ts + above;
+}
+
+// head flags of both run lists, packed (gather | affected << 32) so ONE scan
+// numbers both.  The delta is (p, ts)-sorted and each list's widths are
+// uniform, so a run breaks exactly where the partition changes or this row's
+// range starts past the previous row's end.  Raises the precondition word.
+__global__ void k_roll_heads(const uint64_t *dk, const uint64_t *dv, int64_t n,
+                             uint64_t before, uint64_t after, uint64_t both,
+                             uint64_t *flags, unsigned long long *err) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = dk[i], ts = dv[i];
+        if (p > ROLL_TMAX || ts > ROLL_TMAX) atomicOr(err, 1ull);
+        uint64_t hg = 1, ha = 1;
+        if (i > 0 && dk[i - 1] == p) {
+            const uint64_t tp = dv[i - 1];
+            hg = roll_lo(ts, both) > roll_hi(tp, both);
+            ha = roll_lo(ts, after) > roll_hi(tp, before);
+        }
+        flags[i] = hg | (ha << 32);
+    }
+}
+
+// run r of a list takes lo from its first row and hi from its last
+__global__ void k_roll_ranges(const uint64_t *dk, const uint64_t *dv, int64_t n,
+                              uint64_t before, uint64_t after, uint64_t both,
+                              const uint64_t *flags, const uint64_t *fscan,
+                              uint64_t *gp, uint64_t *glo, uint64_t *ghi,
+                              uint64_t *ap, uint64_t *alo, uint64_t *ahi) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = dk[i], ts = dv[i];
+        const uint64_t f = flags[i], sc = fscan[i];
+        const uint64_t fn = i + 1 < n ? flags[i + 1] : ~0ull;
+        const uint64_t hg = f & 1, ha = (f >> 32) & 1;
+        // row 0 heads both lists, so the run index is never negative
+        const int64_t ig = (int64_t)(sc & ROLL_TMAX) + (int64_t)hg - 1;
+        const int64_t ia = (int64_t)(sc >> 32) + (int64_t)ha - 1;
+        if (hg) { gp[ig] = p; glo[ig] = roll_lo(ts, both); }
+        if (fn & 1) ghi[ig] = roll_hi(ts, both);
+        if (ha) { ap[ia] = p; alo[ia] = roll_lo(ts, after); }
+        if ((fn >> 32) & 1) ahi[ia] = roll_hi(ts, before);
+    }
+}
+
+// range-gather count: one thread per (range, spine batch) pair, two binary
+// searches.  mode 0: rows (k, v) in [(p, lo), (p, hi)] (the input trace);
+// mode 1: rows with k in [p<<32|lo, p<<32|hi] (the output trace, whose key
+// packs partition and time).  Empty batches and ranges count 0.
+__global__ void k_range_count(const uint64_t *rp, const uint64_t *rlo,
+                              const uint64_t *rhi, int64_t nr, TraceArgs t,
+                              int mode, uint64_t *cnt, uint64_t *start) {
+    const int64_t np = nr * t.nb;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < np;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = j / t.nb;
+        const int b = (int)(j % t.nb);
+        const uint64_t p = rp[r], lo_t = rlo[r], hi_t = rhi[r];
+        const int64_t n = t.n[b];
+        int64_t lo = 0, hi = 0;
+        if (n > 0 && lo_t <= hi_t) {
+            if (mode == 0) {
+                lo = lex_lower(t.k[b], t.v[b], 0, n, p, lo_t);
+                hi = lex_upper(t.k[b], t.v[b], lo, n, p, hi_t);
+            } else {
+                lo = lower_bound_k(t.k[b], n, (p << 32) | lo_t);
+                hi = lo + upper_bound_k(t.k[b] + lo, n - lo, (p << 32) | hi_t);
+            }
+        }
+        cnt[j] = (uint64_t)(hi - lo);
+        start[j] = (uint64_t)lo;
+    }
+}
+
+// emit over the OUTPUT index space (as k_join_emit): the pair is found by
+// binary search in the exclusive offsets, so one huge range costs no more
+// per thread than many small ones
+__global__ void k_range_emit(TraceArgs t, int64_t np, const uint64_t *offsets,
+                             const uint64_t *start, int64_t n_out,
+                             int64_t sign, uint64_t *ok, uint64_t *ov,
+                             int64_t *ow) {
+    for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < n_out;
+         o += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = upper_bound_k(offsets, np, (uint64_t)o) - 1;
+        const int b = (int)(j % t.nb);
+        const int64_t src = (int64_t)start[j] + (o - (int64_t)offsets[j]);
+        ok[o] = t.k[b][src];
+        ov[o] = t.v[b][src];
+        ow[o] = sign * t.w[b][src];
+    }
+}
+
+// a slice row (p, ts) is re-emitted iff its total weight is positive
+// (!weight.le0(), rolling_aggregate.rs:574) and the delta has a row of
+// partition p with time in range_of(ts) = [ts - before, ts + after]
+__global__ void k_roll_flags(const uint64_t *sk, const uint64_t *sv,
+                             const int64_t *sw, int64_t n, const uint64_t *dk,
+                             const uint64_t *dv, int64_t nd, uint64_t before,
+                             uint64_t after, uint64_t *flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t f = 0;
+        if (sw[i] > 0) {
+            const uint64_t p = sk[i], ts = sv[i];
+            const int64_t j = lex_lower(dk, dv, 0, nd, p, roll_lo(ts, before));
+            f = j < nd && dk[j] == p && dv[j] <= roll_hi(ts, after);
+        }
+        flags[i] = f;
+    }
+}
+
+__global__ void k_roll_emit(const uint64_t *sk, const uint64_t *sv,
+                            const int64_t *sw, int64_t n, RtLevels t,
+                            uint64_t before, uint64_t after,
+                            const uint64_t *flags, const uint64_t *fscan,
+                            uint64_t *ok, uint64_t *ov, int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t p = sk[i], ts = sv[i];
+        const int64_t qlo = lex_lower(sk, sv, 0, n, p, roll_lo(ts, before));
+        const int64_t qhi = lex_upper(sk, sv, qlo, n, p, roll_hi(ts, after));
+        const int64_t o = (int64_t)fscan[i];
+        ok[o] = (p << 32) | ts;
+        ov[o] = (uint64_t)rt_range_sum(sw, n, t, qlo, qhi);
+        ow[o] = 1;
+    }
+}
+
+static inline uint64_t sat_add_u64(uint64_t a, uint64_t b) {
+    return a + b < a ? UINT64_MAX : a + b;
+}
+
+dbsp_status roll_ranges(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
+                        int64_t n, uint64_t before, uint64_t after,
+                        uint64_t **ranges, int64_t *n_gather,
+                        int64_t *n_affected, int *err) {
+    *ranges = nullptr;
+    *n_gather = *n_affected = 0;
+    *err = 0;
+    if (n <= 0) return DBSP_OK;
+    const uint64_t both = sat_add_u64(before, after);
+    uint64_t *flags, *fscan, *rb;
+    // flags[n] is the precondition error word
+    HIP_CHECK(dbspk::cache_malloc((void **)&flags, (n + 1) * sizeof(uint64_t), s));
+    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
+    HIP_CHECK(dbspk::cache_malloc((void **)&rb, 6 * n * sizeof(uint64_t), s));
+    HIP_CHECK(hipMemsetAsync(flags + n, 0, sizeof(uint64_t), s));
+    k_roll_heads<<<grid_for(n), BLK, 0, s>>>(dk, dv, n, before, after, both,
+                                             flags,
+                                             (unsigned long long *)(flags + n));
+    uint64_t h_err = 0, total = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_err, flags + n, sizeof(uint64_t),
+                             hipMemcpyDeviceToHost, s));
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));  // syncs: err + lengths
+    if (h_err == 0) {
+        k_roll_ranges<<<grid_for(n), BLK, 0, s>>>(
+            dk, dv, n, before, after, both, flags, fscan, rb, rb + n,
+            rb + 2 * n, rb + 3 * n, rb + 4 * n, rb + 5 * n);
+        *n_gather = (int64_t)(total & ROLL_TMAX);
+        *n_affected = (int64_t)(total >> 32);
+        *ranges = rb;
+    } else {
+        HIP_CHECK(dbspk::cache_free(rb, s));
+        *err = 1;
+    }
+    HIP_CHECK(dbspk::cache_free(flags, s));
+    HIP_CHECK(dbspk::cache_free(fscan, s));
+    return DBSP_OK;
+}
+
+dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
+                         const uint64_t *rlo, const uint64_t *rhi, int64_t nr,
+                         const TraceArgs &t, int mode, int64_t sign,
+                         uint64_t **ok, uint64_t **ov, int64_t **ow,
+                         int64_t *out_n) {
+    *ok = *ov = nullptr;
+    *ow = nullptr;
+    *out_n = 0;
+    if (nr <= 0 || t.nb <= 0) return DBSP_OK;
+    const int64_t np = nr * t.nb;
+    uint64_t *cnt, *start;
+    HIP_CHECK(dbspk::cache_malloc((void **)&cnt, np * sizeof(uint64_t), s));
+    HIP_CHECK(dbspk::cache_malloc((void **)&start, np * sizeof(uint64_t), s));
+    k_range_count<<<grid_for(np), BLK, 0, s>>>(rp, rlo, rhi, nr, t, mode, cnt,
+                                               start);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, cnt, cnt, np, &total));
+    if (total > 0) {
+        HIP_CHECK(dbspk::cache_malloc((void **)ok, total * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)ov, total * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)ow, total * sizeof(int64_t) + 8, s));
+        k_range_emit<<<grid_for((int64_t)total), BLK, 0, s>>>(
+            t, np, cnt, start, (int64_t)total, sign, *ok, *ov, *ow);
+    }
+    *out_n = (int64_t)total;
+    HIP_CHECK(dbspk::cache_free(cnt, s));
+    HIP_CHECK(dbspk::cache_free(start, s));
+    return DBSP_OK;
+}
+
+dbsp_status roll_eval_rows(hipStream_t s, const uint64_t *sk,
+                           const uint64_t *sv, const int64_t *sw, int64_t n,
+                           const uint64_t *dk, const uint64_t *dv, int64_t nd,
+                           uint64_t before, uint64_t after, uint64_t **ok,
+                           uint64_t **ov, int64_t **ow, int64_t *out_n) {
+    *ok = *ov = nullptr;
+    *ow = nullptr;
+    *out_n = 0;
+    if (n <= 0 || nd <= 0) return DBSP_OK;
+    uint64_t *flags, *fscan;
+    HIP_CHECK(dbspk::cache_malloc((void **)&flags, n * sizeof(uint64_t), s));
+    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
+    k_roll_flags<<<grid_for(n), BLK, 0, s>>>(sk, sv, sw, n, dk, dv, nd, before,
+                                             after, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));
+    if (total > 0) {
+        RtLevels t{};
+        int64_t *bufs[RT_MAX_LEVELS] = {};
+        TRY_K(rt_build(s, sw, n, t, bufs));
+        HIP_CHECK(dbspk::cache_malloc((void **)ok, total * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)ov, total * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)ow, total * sizeof(int64_t) + 8, s));
+        k_roll_emit<<<grid_for(n), BLK, 0, s>>>(sk, sv, sw, n, t, before, after,
+                                                flags, fscan, *ok, *ov, *ow);
+        TRY_K(rt_free(s, t, bufs));
+    }
+    *out_n = (int64_t)total;
+    HIP_CHECK(dbspk::cache_free(flags, s));
+    HIP_CHECK(dbspk::cache_free(fscan, s));
     return DBSP_OK;
 }
 

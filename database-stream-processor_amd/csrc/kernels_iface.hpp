@@ -385,6 +385,37 @@ dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
                              uint64_t width, uint64_t *ok, uint64_t *ov,
                              int64_t *ow);
 
+// ---- incremental partitioned rolling aggregate (rolling_aggregate.rs
+// :487-604); times and partitions < 2^32, ranges saturate at 0 / 2^32-1 ----
+// Merged run lists of a consolidated (p, ts)-sorted delta.  *ranges is one
+// 6*n-word device buffer (caller frees with cache_free) holding the columns
+// [gp | glo | ghi | ap | alo | ahi], each n words apart: the gather ranges
+// (p, [ts-before-after, ts+before+after]) in the first n_gather entries of
+// the g columns, the affected ranges (p, [ts-after, ts+before]) in the first
+// n_affected entries of the a columns.  *err = 1 (and no ranges) if a
+// partition or time is >= 2^32.  One host sync.
+dbsp_status roll_ranges(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
+                        int64_t n, uint64_t before, uint64_t after,
+                        uint64_t **ranges, int64_t *n_gather,
+                        int64_t *n_affected, int *err);
+// copy the rows of every spine batch that fall in a range, weights times
+// sign.  mode 0: (k, v) in [(p, lo), (p, hi)]; mode 1: k in
+// [p<<32|lo, p<<32|hi].  Ranges must be disjoint; output is RAW (range-major,
+// batch-minor runs).  Buffers from the big-buffer cache (null when empty).
+dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
+                         const uint64_t *rlo, const uint64_t *rhi, int64_t nr,
+                         const TraceArgs &t, int mode, int64_t sign,
+                         uint64_t **ok, uint64_t **ov, int64_t **ow,
+                         int64_t *out_n);
+// per row (p, ts, w > 0) of the consolidated slice that the delta affects:
+// (p<<32|ts, sum of slice weights of p over [ts-before, ts+after], +1),
+// in slice order (sorted, distinct keys)
+dbsp_status roll_eval_rows(hipStream_t s, const uint64_t *sk,
+                           const uint64_t *sv, const int64_t *sw, int64_t n,
+                           const uint64_t *dk, const uint64_t *dv, int64_t nd,
+                           uint64_t before, uint64_t after, uint64_t **ok,
+                           uint64_t **ov, int64_t **ow, int64_t *out_n);
+
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 
 }  // namespace dbspk

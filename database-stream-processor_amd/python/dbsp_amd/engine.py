@@ -115,6 +115,20 @@ def _L():
         L.dbsp_rolling_agg.restype = i32
         L.dbsp_rolling_agg.argtypes = [vp, ctypes.POINTER(BatchStruct), u64,
                                        ctypes.POINTER(BatchStruct)]
+        L.dbsp_rolling_create.restype = i32
+        L.dbsp_rolling_create.argtypes = [vp, u64, u64, ctypes.POINTER(vp)]
+        L.dbsp_rolling_step.restype = i32
+        L.dbsp_rolling_step.argtypes = [vp, vp, vp, vp, i64,
+                                        ctypes.POINTER(BatchStruct)]
+        L.dbsp_rolling_stats.restype = i32
+        L.dbsp_rolling_stats.argtypes = [vp, ctypes.POINTER(i64),
+                                         ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(i64),
+                                         ctypes.POINTER(ctypes.c_int)]
+        L.dbsp_rolling_destroy.restype = i32
+        L.dbsp_rolling_destroy.argtypes = [vp]
+        L.dbsp_engine_rolling_init.restype = i32
+        L.dbsp_engine_rolling_init.argtypes = [vp, u64, u64]
         L.dbsp_engine_c5_init.restype = i32
         L.dbsp_engine_c5_init.argtypes = [vp, i64, i64, u64]
         L.dbsp_engine_kernel_stats.restype = i32
@@ -364,6 +378,11 @@ class Ctx:
             self.free_batch(x)
         return res
 
+    def rolling_create(self, before, after):
+        """Incremental partitioned rolling aggregate over
+        [ts - before, ts + after] (see `Rolling`)."""
+        return Rolling(self, before, after)
+
     def shard_partition(self, rows, nshards):
         inp = self.upload_rows(rows)
         out = BatchStruct()
@@ -376,6 +395,55 @@ class Ctx:
         for x in (inp, out):
             self.free_batch(x)
         return res, offs
+
+
+class Rolling:
+    """Stateful incremental partitioned rolling aggregate (linear weight-sum;
+    mirror of Stream::partitioned_rolling_aggregate_linear).  Input rows are
+    (k = partition, v = ts, w) with partition, ts < 2^32; each step returns
+    the tick's consolidated output delta (partition<<32 | ts, sum, +-1)."""
+
+    def __init__(self, ctx: Ctx, before: int, after: int):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        _check(self._lib.dbsp_rolling_create(ctx._h, before, after,
+                                             ctypes.byref(h)),
+               "rolling_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):
+                self._lib.dbsp_rolling_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def step(self, rows: np.ndarray) -> np.ndarray:
+        """One tick: raw (unsorted, unconsolidated) delta rows in, output
+        delta out.  Raises (state unchanged) on a partition or ts >= 2^32."""
+        raw = self._ctx.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_rolling_step(self._h, raw.k, raw.v, raw.w,
+                                         raw.len, ctypes.byref(out))
+        self._ctx.free_batch(raw)
+        _check(st, "rolling_step")
+        res = self._ctx.download_rows(out)
+        self._ctx.free_batch(out)
+        return res
+
+    def stats(self):
+        """(in_rows, in_batches, out_rows, out_batches) of the two traces."""
+        ir, orr = ctypes.c_int64(), ctypes.c_int64()
+        ib, ob = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.dbsp_rolling_stats(self._h, ctypes.byref(ir),
+                                            ctypes.byref(ib),
+                                            ctypes.byref(orr),
+                                            ctypes.byref(ob)),
+               "rolling_stats")
+        return ir.value, ib.value, orr.value, ob.value
 
 
 def xxh3_u64(key, seed=0x7F95EF85BE33C337):
@@ -415,6 +483,12 @@ class Engine:
         rows (run_staged(0, steps*n_delta, n_delta) = `steps` ticks)."""
         _check(self._lib.dbsp_engine_c5_init(self._h, n_trace, n_delta, seed),
                "c5_init")
+
+    def rolling_init(self, before, after):
+        """Query 101: the rolling range [date_time - before, date_time +
+        after] in ms (defaults 10000 / 0); rejected after the first step."""
+        _check(self._lib.dbsp_engine_rolling_init(self._h, before, after),
+               "rolling_init")
 
     def step_staged(self, lo, hi):
         _check(self._lib.dbsp_engine_step_staged(self._h, lo, hi), "step")

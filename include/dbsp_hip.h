@@ -176,6 +176,42 @@ dbsp_status dbsp_join(dbsp_ctx *ctx, const dbsp_batch *delta,
 dbsp_status dbsp_rolling_agg(dbsp_ctx *ctx, const dbsp_batch *in,
                              uint64_t width, dbsp_batch *out);
 
+/* Incremental partitioned rolling aggregate, linear weight-sum aggregator:
+ * the stateful operator over the primitive above.  Replaces
+ * PartitionedRollingAggregate::eval (operator/time_series/
+ * rolling_aggregate.rs:487-604) and its two traces (the input trace and the
+ * output trace, rolling_aggregate.rs:286-359).
+ * Input deltas are rows (k = partition, v = ts, w); a value to be summed is
+ * weighed into w beforehand (aggregate/mod.rs:297-323).  partition and ts
+ * must be < 2^32.  range_of(ts) = [sat_sub(ts, before), ts + after], closed
+ * (RelRange::new(Before(before), After(after)), range.rs:93-104); any u64
+ * before/after, the upper end clamped to 2^32-1.
+ * Output deltas are rows (k = partition<<32 | ts, v = sum as i64 bits,
+ * w = +-1): per tick, every previous output at a time the delta can affect
+ * is retracted and every such time whose total input weight is > 0
+ * (!weight.le0(), rolling_aggregate.rs:574) is re-emitted with its new sum,
+ * so a late row updates the aggregates at later times.  Work per tick
+ * follows the affected rows, not the trace. */
+typedef struct dbsp_rolling dbsp_rolling;
+/* rolling_aggregate.rs:286-359 (circuit construction: the operator, its
+ * input trace and the delayed output-trace feedback) */
+dbsp_status dbsp_rolling_create(dbsp_ctx *ctx, uint64_t before, uint64_t after,
+                                dbsp_rolling **out);
+/* rolling_aggregate.rs:487-604 (eval).  k/v/w: n raw (unsorted,
+ * unconsolidated) delta rows in device memory; out: the tick's consolidated
+ * output delta (device arrays owned by the caller, null when empty; host
+ * visible on return).  DBSP_ERR_INVALID, with the operator's state
+ * unchanged, if a partition or ts is >= 2^32 (detected on the device). */
+dbsp_status dbsp_rolling_step(dbsp_rolling *r, const uint64_t *k,
+                              const uint64_t *v, const int64_t *w, int64_t n,
+                              dbsp_batch *out);
+/* rows / spine batches of the input and output traces (Spine introspection,
+ * trace/spine_fueled.rs:107-119); any out pointer may be null */
+dbsp_status dbsp_rolling_stats(dbsp_rolling *r, int64_t *in_rows,
+                               int *in_batches, int64_t *out_rows,
+                               int *out_batches);
+dbsp_status dbsp_rolling_destroy(dbsp_rolling *r);
+
 dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *ctx,
                                    const uint64_t *delta_keys, int64_t nd,
                                    const dbsp_batch *in_trace,
@@ -277,9 +313,20 @@ typedef struct dbsp_engine dbsp_engine;
 /* query: 0, 3, 5, 8 (Nexmark — the same operator DAG as
  * crates/nexmark/src/queries/q{0,3,5,8}.rs over the mirrored API), or 100
  * (config C5: the synthetic 1B-row OrdIndexedZSet x 10M-row delta
- * incremental join + f64 sum aggregate of BASELINE configs[4]). */
+ * incremental join + f64 sum aggregate of BASELINE configs[4]), or 101
+ * (per-auction rolling bid volume:
+ *  bids.map_index(|b| (b.auction, (b.date_time, b.price)))
+ *      .partitioned_rolling_aggregate_linear(...),
+ *  operator/time_series/rolling_aggregate.rs:367-419 over the Nexmark bid
+ *  stream; output rows (auction<<32 | date_time, sum of prices, +-1)). */
 dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
                                int rank, int world);
+
+/* Query 101 range: [date_time - before_ms, date_time + after_ms]
+ * (RelRange, range.rs:93-104).  Defaults 10000 / 0.  DBSP_ERR_INVALID on
+ * another query or after the engine's first step. */
+dbsp_status dbsp_engine_rolling_init(dbsp_engine *e, uint64_t before_ms,
+                                     uint64_t after_ms);
 dbsp_status dbsp_engine_destroy(dbsp_engine *e);
 
 /* C5 (query 100) setup: device-generates the n_trace-row (k, f64-bits, +1)

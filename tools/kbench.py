@@ -6,6 +6,7 @@ join kernels are HBM-bound, and reports achieved algorithmic GB/s against the
 (sorted-unique keys via cumsum of positive gaps — no host staging).
 
 Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
+                       python tools/kbench.py --only rolling [--roll-rows N]
 Prints one JSON line per primitive.
 """
 import argparse
@@ -317,6 +318,130 @@ def bench_c5(ctx, L, n_trace, n_delta, steps=10):
     return res
 
 
+def _rolling_deltas(n_per, parts, n_delta, late_frac, ticks, span, seed):
+    """Per tick: n_delta raw rows (partition, ts, +1), ts near each
+    partition's time frontier (2 * n_per, advancing `span` per tick), and a
+    late_frac share drawn uniformly from the whole past."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    out = []
+    n_late = int(n_delta * late_frac)
+    for t in range(ticks):
+        k = torch.randint(0, parts, (n_delta,), generator=g,
+                          dtype=torch.int64, device="cuda")
+        v = 2 * n_per + t * span + torch.randint(
+            0, span, (n_delta,), generator=g, dtype=torch.int64,
+            device="cuda")
+        if n_late:
+            v[:n_late] = torch.randint(0, 2 * n_per, (n_late,), generator=g,
+                                       dtype=torch.int64, device="cuda")
+        w = torch.ones(n_delta, dtype=torch.int64, device="cuda")
+        out.append((k, v, w))
+    torch.cuda.synchronize()
+    return out
+
+
+def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
+                  ticks=12, warm=2, span=64):
+    """Incremental partitioned rolling aggregate (dbsp_rolling_step) against
+    the only route the batch primitive offers: merge the tick's delta into
+    ONE consolidated integral and run dbsp_rolling_agg over all of it (the
+    diff against the previous result, which that route also needs, is NOT
+    included: the comparison leg is a lower bound of its cost).  Both legs
+    consume the same raw deltas; `warm` leading ticks are excluded.  Times
+    are host-clock around calls that end in a stream synchronise; with
+    DBSP_PROFILE=1 the operator body's hipEvent time (kernel_stats class 3)
+    is reported too."""
+    from dbsp_amd.engine import Engine
+    n_per = max(1, n_trace // parts)
+    n_trace = n_per * parts
+    g = torch.Generator(device="cuda").manual_seed(17)
+    tk = torch.arange(parts, dtype=torch.int64,
+                      device="cuda").repeat_interleave(n_per)
+    tv = (2 * torch.arange(n_per, dtype=torch.int64, device="cuda")).repeat(parts)
+    tw = torch.randint(1, 4, (n_trace,), generator=g, dtype=torch.int64,
+                       device="cuda")
+    deltas = _rolling_deltas(n_per, parts, n_delta, late_frac, warm + ticks,
+                             span, 23)
+    probe = Engine(ctx, query=101)   # reads the context's hipEvent counters
+
+    # ---- incremental operator ----
+    op = ctx.rolling_create(before, after)
+    out = BatchStruct()
+    t0 = time.perf_counter()
+    assert L.dbsp_rolling_step(op._h, tk.data_ptr(), tv.data_ptr(),
+                               tw.data_ptr(), n_trace, ctypes.byref(out)) == 0
+    load_ms = (time.perf_counter() - t0) * 1e3
+    ctx.free_batch(out)
+    inc_ms, inc_ev_ms, rows_out = [], [], []
+    for i, (k, v, w) in enumerate(deltas):
+        ev0 = probe.kernel_stats(3)[0]
+        out = BatchStruct()
+        ctx.sync()
+        t0 = time.perf_counter()
+        assert L.dbsp_rolling_step(op._h, k.data_ptr(), v.data_ptr(),
+                                   w.data_ptr(), n_delta,
+                                   ctypes.byref(out)) == 0
+        dt = (time.perf_counter() - t0) * 1e3
+        if i >= warm:
+            inc_ms.append(dt)
+            inc_ev_ms.append(probe.kernel_stats(3)[0] - ev0)
+            rows_out.append(out.len)
+        ctx.free_batch(out)
+    stats = op.stats()
+    op.close()
+
+    # ---- comparison leg: consolidated integral + batch primitive ----
+    integral = as_batch(tk, tv, tw)
+    owned = False
+    full_ms = []
+    for i, (k, v, w) in enumerate(deltas):
+        ctx.sync()
+        t0 = time.perf_counter()
+        d = BatchStruct()
+        assert L.dbsp_sort_consolidate(ctx._h, k.data_ptr(), v.data_ptr(),
+                                       w.data_ptr(), n_delta,
+                                       ctypes.byref(d)) == 0
+        m = BatchStruct()
+        assert L.dbsp_merge(ctx._h, ctypes.byref(integral), ctypes.byref(d),
+                            ctypes.byref(m)) == 0
+        res = BatchStruct()
+        assert after == 0, "dbsp_rolling_agg covers [ts - width, ts] only"
+        assert L.dbsp_rolling_agg(ctx._h, ctypes.byref(m), before,
+                                  ctypes.byref(res)) == 0
+        ctx.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        if i >= warm:
+            full_ms.append(dt)
+        ctx.free_batch(d)
+        ctx.free_batch(res)
+        if owned:
+            ctx.free_batch(integral)
+        integral, owned = m, True
+    if owned:
+        ctx.free_batch(integral)
+    probe.close()
+
+    def med(x):
+        s = sorted(x)
+        return s[len(s) // 2]
+    return {
+        "primitive": "dbsp_rolling_step (incremental partitioned rolling "
+                     "aggregate) vs merge + dbsp_rolling_agg over the trace",
+        "trace_rows": n_trace, "partitions": parts, "delta_rows": n_delta,
+        "late_frac": late_frac, "before": before, "after": after,
+        "ticks": ticks, "warmup_ticks": warm, "load_ms": round(load_ms, 2),
+        "in_rows": stats[0], "in_batches": stats[1],
+        "out_rows": stats[2], "out_batches": stats[3],
+        "rows_out_per_tick": rows_out,
+        "incremental_ms_per_step": [round(x, 3) for x in inc_ms],
+        "incremental_ms_median": round(med(inc_ms), 3),
+        "incremental_op_hipevent_ms": [round(x, 3) for x in inc_ev_ms],
+        "full_recompute_ms_per_step": [round(x, 3) for x in full_ms],
+        "full_recompute_ms_median": round(med(full_ms), 3),
+        "full_recompute_excludes": "diff against the previous result",
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=500_000_000,
@@ -324,7 +449,16 @@ def main():
     ap.add_argument("--delta", type=int, default=10_000_000)
     ap.add_argument("--sort-rows", type=int, default=50_000_000)
     ap.add_argument("--only", default=None,
-                    choices=["merge", "join", "sort", "incremental", "c5"])
+                    choices=["merge", "join", "sort", "incremental", "c5",
+                             "rolling"])
+    ap.add_argument("--roll-rows", type=int, default=4_000_000,
+                    help="rolling leg: trace rows")
+    ap.add_argument("--roll-parts", type=int, default=1024)
+    ap.add_argument("--roll-delta", type=int, default=40_000)
+    ap.add_argument("--roll-late", type=float, default=0.01)
+    ap.add_argument("--roll-before", type=int, default=200)
+    ap.add_argument("--roll-after", type=int, default=0)
+    ap.add_argument("--roll-ticks", type=int, default=12)
     args = ap.parse_args()
     ctx = Ctx(0)
     L = _L()
@@ -335,9 +469,14 @@ def main():
         "incremental": lambda: bench_incremental(ctx, L, 2 * args.rows,
                                                  args.delta),
         "c5": lambda: bench_c5(ctx, L, 2 * args.rows, args.delta),
+        "rolling": lambda: bench_rolling(ctx, L, args.roll_rows,
+                                         args.roll_parts, args.roll_delta,
+                                         args.roll_late, args.roll_before,
+                                         args.roll_after, args.roll_ticks),
     }
     for name, leg in legs.items():
-        if args.only is None or args.only == name:
+        # the rolling leg runs on request only: a bare run keeps its legs
+        if args.only == name or (args.only is None and name != "rolling"):
             print(json.dumps(leg()))
     ctx.close()
 
