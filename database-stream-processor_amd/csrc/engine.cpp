@@ -584,7 +584,10 @@ struct Spine {
             TRY(merge2(c, below, top, merged));
             free_batch(c, top);
             free_batch(c, below);
-            if (merged.n > 0) batches.push_back(merged);
+            if (merged.n > 0)
+                batches.push_back(merged);
+            else
+                free_batch(c, merged);
         }
         return DBSP_OK;
     }
@@ -610,6 +613,37 @@ struct RollingOp {
     // out: the tick's consolidated output delta (p<<32|ts, sum, +-1).
     // DBSP_ERR_INVALID (state unchanged) if a partition or time is >= 2^32.
     dbsp_status step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out);
+
+    // Watermark-bounded state (partitioned_rolling_aggregate_with_watermark,
+    // rolling_aggregate.rs:155-220 and :286-321).  wm only grows; both
+    // spines may drop their rows below lower_bound() = wm - (before + after):
+    // a row at ts >= wm affects times >= wm - after, whose sums and
+    // retractions read nothing below the bound.
+    // A sweep is a few launches plus a length sync, not worth it for fewer
+    // dead rows than this; the break-even has not been measured.
+    static constexpr int64_t SWEEP_FLOOR = 4096;
+    uint64_t wm = 0;
+    int64_t late_rows = 0, sweeps = 0;
+    int64_t in_live = 0, out_live = 0;  // rows after each spine's last sweep
+
+    static uint64_t bound_of(uint64_t wm_, uint64_t before_, uint64_t after_) {
+        const uint64_t both = before_ + after_;
+        if (both < before_ || both > wm_) return 0;
+        return wm_ - both;
+    }
+    uint64_t lower_bound() const { return bound_of(wm, before, after); }
+
+    // step() with the watermark raised to max(wm, x) first.  Delta rows
+    // below the new watermark are dropped whole and counted in late_rows
+    // (the reference only "does not expect" them, rolling_aggregate.rs
+    // :126-129; dropping is this operator's choice).  On DBSP_ERR_INVALID
+    // nothing changes, the watermark and the counters included.
+    dbsp_status step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
+                        DevBatch &out);
+    // sweep one spine at lower_bound(): mode 0 = in_sp, 1 = out_sp
+    dbsp_status sweep(dbsp_ctx *c, int mode);
+    // sweep the spines that outgrew 2 * live + SWEEP_FLOOR
+    dbsp_status sweep_policy(dbsp_ctx *c);
 
     void clear(dbsp_ctx *c) {
         in_sp.clear(c);
@@ -1164,6 +1198,8 @@ struct dbsp_engine {
     // query 101 state: per-auction rolling bid volume
     RollingOp roll;
     bool roll_stepped = false;  // rolling_init is rejected after a step
+    bool roll_lateness_on = false;  // watermark-bounded state (off by default)
+    uint64_t roll_lateness = 0;
     int64_t c5_n_delta = 0;
     uint64_t c5_seed = 0;
     uint64_t c5_delta_stride = 0;
@@ -2359,10 +2395,106 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     return DBSP_OK;
 }
 
+// rows of one batch with time >= bound, in order (modes as truncate_spine)
+static dbsp_status truncate_batch(dbsp_ctx *c, const DevBatch &in, int mode,
+                                  uint64_t bound, DevBatch &out) {
+    out = DevBatch{};
+    if (in.n == 0) return DBSP_OK;
+    TraceArgs t{};
+    t.nb = 1;
+    t.k[0] = in.k;
+    t.v[0] = in.v;
+    t.w[0] = in.w;
+    t.n[0] = in.n;
+    return dbspk::truncate_spine(c->stream, t, mode, bound, &out.k, &out.v,
+                                 &out.w, &out.n);
+}
+
+dbsp_status RollingOp::step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
+                               DevBatch &out) {
+    out = DevBatch{};
+    const uint64_t nwm = std::max(wm, x);
+    int64_t dropped = 0;
+    if (nwm > 0 && delta.n > 0) {
+        // stable, so the survivors are still a consolidated delta
+        DevBatch surv;
+        TRY(truncate_batch(c, delta, 0, nwm, surv));
+        dropped = delta.n - surv.n;
+        const dbsp_status st = step(c, surv, out);
+        free_batch(c, surv);
+        if (st != DBSP_OK) return st;
+    } else {
+        TRY(step(c, delta, out));
+    }
+    wm = nwm;
+    late_rows += dropped;
+    return sweep_policy(c);
+}
+
+dbsp_status RollingOp::sweep(dbsp_ctx *c, int mode) {
+    Spine &sp = mode == 0 ? in_sp : out_sp;
+    if ((int)sp.batches.size() > MAX_TRACE_BATCHES)
+        TRY(sp.consolidate_all(c));
+    const int nb = (int)sp.batches.size();
+    if (nb > 0) {
+        TraceArgs t{};
+        t.nb = nb;
+        for (int b = 0; b < nb; b++) {
+            t.k[b] = sp.batches[b].k;
+            t.v[b] = sp.batches[b].v;
+            t.w[b] = sp.batches[b].w;
+            t.n[b] = sp.batches[b].n;
+        }
+        uint64_t *ok[MAX_TRACE_BATCHES], *ov[MAX_TRACE_BATCHES];
+        int64_t *ow[MAX_TRACE_BATCHES], on[MAX_TRACE_BATCHES];
+        TRY(dbspk::truncate_spine(c->stream, t, mode, lower_bound(), ok, ov,
+                                  ow, on));
+        std::vector<DevBatch> old;
+        old.swap(sp.batches);
+        for (auto &b : old) free_batch(c, b);
+        // empty batches are dropped and the survivors (at most half of what
+        // a policy sweep read) merged into one batch: rows are counted per
+        // batch, so only a consolidated spine has live = rows, without
+        // retraction/insertion pairs still waiting for a merge.  One batch
+        // satisfies size[i] >= 2 * size[i+1] trivially.
+        for (int b = 0; b < nb; b++)
+            if (on[b] > 0)
+                sp.batches.push_back(DevBatch{ok[b], ov[b], ow[b], on[b]});
+        TRY(sp.consolidate_all(c));
+    }
+    (mode == 0 ? in_live : out_live) = sp.total();
+    sweeps++;
+    return DBSP_OK;
+}
+
+// Doubling rule: amortised O(1) per inserted row, and a spine never holds
+// more than 2 * live + SWEEP_FLOOR plus the rows added since its last sweep.
+dbsp_status RollingOp::sweep_policy(dbsp_ctx *c) {
+    if (lower_bound() == 0) return DBSP_OK;  // no row can be below it
+    if (in_sp.total() > 2 * in_live + SWEEP_FLOOR) TRY(sweep(c, 0));
+    if (out_sp.total() > 2 * out_live + SWEEP_FLOOR) TRY(sweep(c, 1));
+    return DBSP_OK;
+}
+
 struct dbsp_rolling {
     dbsp_ctx *ctx = nullptr;
     RollingOp op;
 };
+
+extern "C" dbsp_status dbsp_truncate_below(dbsp_ctx *c, const dbsp_batch *in,
+                                           int mode, uint64_t bound,
+                                           dbsp_batch *out) {
+    if (!c || !in || !out || in->len < 0 || (mode != 0 && mode != 1))
+        return DBSP_ERR_INVALID;
+    DevBatch ib{in->k, in->v, in->w, in->len}, res;
+    TRY(truncate_batch(c, ib, mode, bound, res));
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    out->k = res.k;
+    out->v = res.v;
+    out->w = res.w;
+    out->len = res.n;
+    return DBSP_OK;
+}
 
 extern "C" dbsp_status dbsp_rolling_create(dbsp_ctx *c, uint64_t before,
                                            uint64_t after, dbsp_rolling **out) {
@@ -2375,20 +2507,33 @@ extern "C" dbsp_status dbsp_rolling_create(dbsp_ctx *c, uint64_t before,
     return DBSP_OK;
 }
 
+// a step that does not advance the watermark: step_wm with watermark 0
 extern "C" dbsp_status dbsp_rolling_step(dbsp_rolling *r, const uint64_t *k,
                                          const uint64_t *v, const int64_t *w,
                                          int64_t n, dbsp_batch *out) {
     if (!r || !out || n < 0) return DBSP_ERR_INVALID;
-    dbsp_ctx *c = r->ctx;
     *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
     if (n == 0) return DBSP_OK;
+    return dbsp_rolling_step_wm(r, k, v, w, n, 0, out);
+}
+
+extern "C" dbsp_status dbsp_rolling_step_wm(dbsp_rolling *r, const uint64_t *k,
+                                            const uint64_t *v,
+                                            const int64_t *w, int64_t n,
+                                            uint64_t watermark,
+                                            dbsp_batch *out) {
+    if (!r || !out || n < 0) return DBSP_ERR_INVALID;
+    dbsp_ctx *c = r->ctx;
+    *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
     DevBatch raw, delta, res;
-    TRY(alloc_batch(c, n, raw));
-    HIP_CHECK_ST(hipMemcpyAsync(raw.k, k, n * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_CHECK_ST(hipMemcpyAsync(raw.v, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIP_CHECK_ST(hipMemcpyAsync(raw.w, w, n * 8, hipMemcpyDeviceToDevice, c->stream));
-    TRY(sort_consolidate_batch(c, raw, delta));
-    const dbsp_status st = r->op.step(c, delta, res);
+    if (n > 0) {
+        TRY(alloc_batch(c, n, raw));
+        HIP_CHECK_ST(hipMemcpyAsync(raw.k, k, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_CHECK_ST(hipMemcpyAsync(raw.v, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIP_CHECK_ST(hipMemcpyAsync(raw.w, w, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        TRY(sort_consolidate_batch(c, raw, delta));
+    }
+    const dbsp_status st = r->op.step_wm(c, delta, watermark, res);
     free_batch(c, delta);
     HIP_CHECK_ST(hipStreamSynchronize(c->stream));
     if (st != DBSP_OK) return st;
@@ -2408,6 +2553,27 @@ extern "C" dbsp_status dbsp_rolling_stats(dbsp_rolling *r, int64_t *in_rows,
     if (in_batches) *in_batches = (int)r->op.in_sp.batches.size();
     if (out_rows) *out_rows = r->op.out_sp.total();
     if (out_batches) *out_batches = (int)r->op.out_sp.batches.size();
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_compact(dbsp_rolling *r) {
+    if (!r) return DBSP_ERR_INVALID;
+    TRY(r->op.sweep(r->ctx, 0));
+    TRY(r->op.sweep(r->ctx, 1));
+    HIP_CHECK_ST(hipStreamSynchronize(r->ctx->stream));
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_wm_stats(dbsp_rolling *r,
+                                             uint64_t *watermark,
+                                             uint64_t *lower_bound,
+                                             int64_t *late_rows,
+                                             int64_t *sweeps) {
+    if (!r) return DBSP_ERR_INVALID;
+    if (watermark) *watermark = r->op.wm;
+    if (lower_bound) *lower_bound = r->op.lower_bound();
+    if (late_rows) *late_rows = r->op.late_rows;
+    if (sweeps) *sweeps = r->op.sweeps;
     return DBSP_OK;
 }
 
@@ -2432,10 +2598,46 @@ static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
     e->roll_stepped = true;
     DevBatch d, dummy;
     TRY(build_deltas(e, d_ev, n, d, dummy, false));
-    const dbsp_status st = e->roll.step(c, d, e->output);
+    dbsp_status st;
+    if (e->roll_lateness_on) {
+        // watermark_monotonic(|ts| ts.saturating_sub(lateness)) (watermark.rs
+        // :33-75): the maximum includes this tick's own rows; step_wm keeps
+        // it monotone.  Sharded ranks see their own bids only, so each rank
+        // runs on its rank-local watermark: no collective.
+        uint64_t x = 0;
+        if (d.n > 0) {
+            uint64_t mm[4];
+            TRY(dbspk::minmax_rows(c->stream, d.k, d.v, d.n, mm));
+            x = mm[3] > e->roll_lateness ? mm[3] - e->roll_lateness : 0;
+        }
+        st = e->roll.step_wm(c, d, x, e->output);
+    } else {
+        st = e->roll.step(c, d, e->output);
+    }
     free_batch(c, d);
     HIP_CHECK_ST(hipStreamSynchronize(c->stream));
     return st;
+}
+
+extern "C" dbsp_status dbsp_engine_rolling_lateness(dbsp_engine *e,
+                                                    uint64_t lateness_ms) {
+    if (!e || e->query != 101 || e->roll_stepped) return DBSP_ERR_INVALID;
+    e->roll_lateness = lateness_ms;
+    e->roll_lateness_on = true;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e,
+                                                 int64_t *in_rows,
+                                                 int64_t *out_rows,
+                                                 int64_t *late_rows,
+                                                 int64_t *sweeps) {
+    if (!e || e->query != 101) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = e->roll.in_sp.total();
+    if (out_rows) *out_rows = e->roll.out_sp.total();
+    if (late_rows) *late_rows = e->roll.late_rows;
+    if (sweeps) *sweeps = e->roll.sweeps;
+    return DBSP_OK;
 }
 
 extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,

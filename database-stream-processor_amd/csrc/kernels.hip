@@ -4506,6 +4506,184 @@ dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
     return DBSP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Order-preserving truncation of a spine (TraceBounds lower bound,
+// operator/trace.rs:463-607): every batch compacted to its rows whose time
+// is >= bound.  The dead rows are a prefix of each partition's run, so they
+// are interleaved through a batch: a stable stream compaction, not a slice.
+//   k_trunc_count   one block per TRUNC_TILE rows of one batch, tiles laid
+//                   out batch-major; reads the 8-byte time column only
+//   scan_exclusive  over the tile counts of the whole spine
+//   k_trunc_totals  per-batch totals out of the scanned counts (one readback)
+//   k_trunc_emit    same tiling; ranks by wave64 ballot inside the block and
+//                   by the scanned count across blocks
+// A tile is BLK lanes x TRUNC_ITEMS passes with lane-consecutive rows per
+// pass, so every load is a coalesced 8 B/lane stream and the kept rows of a
+// wave land contiguously.  No tile looks at another tile's state.
+// ---------------------------------------------------------------------------
+
+#define TRUNC_ITEMS 8
+#define TRUNC_TILE (BLK * TRUNC_ITEMS)  // 2048 rows per block
+#define TRUNC_WAVES (BLK / WAVE)
+
+struct TruncArgs {
+    TraceArgs t;
+    int64_t blk0[MAX_TRACE_BATCHES + 1];  // first tile of batch b; [nb] = all
+    int mode;        // 0: time = v; 1: time = low 32 bits of k
+    uint64_t bound;
+};
+struct TruncOut {
+    uint64_t *k[MAX_TRACE_BATCHES];
+    uint64_t *v[MAX_TRACE_BATCHES];
+    int64_t *w[MAX_TRACE_BATCHES];
+};
+
+__device__ inline int trunc_batch_of(const TruncArgs &a, int64_t blk) {
+    int b = 0;
+    while (b + 1 < a.t.nb && blk >= a.blk0[b + 1]) b++;
+    return b;
+}
+
+__global__ void __launch_bounds__(BLK)
+k_trunc_count(TruncArgs a, uint64_t *counts) {
+    __shared__ uint32_t wave_cnt[TRUNC_WAVES];
+    const int64_t blk = blockIdx.x;
+    const int b = trunc_batch_of(a, blk);
+    const uint64_t *tc = a.mode == 0 ? a.t.v[b] : a.t.k[b];
+    const uint64_t mask = a.mode == 0 ? ~0ull : ROLL_TMAX;
+    const int64_t n = a.t.n[b];
+    const int64_t base = (blk - a.blk0[b]) * TRUNC_TILE + threadIdx.x;
+    uint32_t c = 0;  // wave-uniform
+#pragma unroll
+    for (int it = 0; it < TRUNC_ITEMS; it++) {
+        const int64_t i = base + it * BLK;
+        const bool keep = i < n && (tc[i] & mask) >= a.bound;
+        c += (uint32_t)__popcll(__ballot(keep));
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) wave_cnt[threadIdx.x / WAVE] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < TRUNC_WAVES; w++) sum += wave_cnt[w];
+        counts[blk] = sum;
+    }
+}
+
+__global__ void k_trunc_totals(TruncArgs a, const uint64_t *offsets,
+                               int64_t *totals) {
+    const int b = threadIdx.x;
+    if (b < a.t.nb)
+        totals[b] = (int64_t)(offsets[a.blk0[b + 1]] - offsets[a.blk0[b]]);
+}
+
+// offsets: exclusive scan of the tile counts, one entry past the last tile
+__global__ void __launch_bounds__(BLK)
+k_trunc_emit(TruncArgs a, const uint64_t *offsets, TruncOut o) {
+    __shared__ uint64_t pre[TRUNC_ITEMS * TRUNC_WAVES];
+    const int64_t blk = blockIdx.x;
+    const uint64_t off0 = offsets[blk];
+    if (offsets[blk + 1] == off0) return;  // nothing of this tile survives
+    const int b = trunc_batch_of(a, blk);
+    const uint64_t *tc = a.mode == 0 ? a.t.v[b] : a.t.k[b];
+    const uint64_t *oc = a.mode == 0 ? a.t.k[b] : a.t.v[b];
+    uint64_t *otc = a.mode == 0 ? o.v[b] : o.k[b];
+    uint64_t *ooc = a.mode == 0 ? o.k[b] : o.v[b];
+    const int64_t *wc = a.t.w[b];
+    int64_t *owc = o.w[b];
+    const uint64_t mask = a.mode == 0 ? ~0ull : ROLL_TMAX;
+    const int64_t n = a.t.n[b];
+    const int64_t base = (blk - a.blk0[b]) * TRUNC_TILE + threadIdx.x;
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    uint64_t tv[TRUNC_ITEMS], bal[TRUNC_ITEMS];
+#pragma unroll
+    for (int it = 0; it < TRUNC_ITEMS; it++) {
+        const int64_t i = base + it * BLK;
+        tv[it] = i < n ? tc[i] : 0;
+        bal[it] = __ballot(i < n && (tv[it] & mask) >= a.bound);
+        if (lane == 0)
+            pre[it * TRUNC_WAVES + wid] = (uint64_t)__popcll(bal[it]);
+    }
+    __syncthreads();
+    // rows ascend with (pass, wave, lane), and so does the pre[] index
+    if (threadIdx.x < WAVE) {
+        const bool in = threadIdx.x < TRUNC_ITEMS * TRUNC_WAVES;
+        uint64_t tot;
+        const uint64_t ex = wave_scan_excl(in ? pre[threadIdx.x] : 0, tot);
+        if (in) pre[threadIdx.x] = ex;
+    }
+    __syncthreads();
+    // position inside the batch's own output
+    const int64_t dst0 = (int64_t)(off0 - offsets[a.blk0[b]]);
+    const uint64_t below = (1ull << lane) - 1;
+#pragma unroll
+    for (int it = 0; it < TRUNC_ITEMS; it++) {
+        if (!((bal[it] >> lane) & 1)) continue;
+        const int64_t i = base + it * BLK;
+        const int64_t d = dst0 + (int64_t)pre[it * TRUNC_WAVES + wid] +
+                          __popcll(bal[it] & below);
+        otc[d] = tv[it];
+        ooc[d] = oc[i];
+        owc[d] = wc[i];
+    }
+}
+
+dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
+                           uint64_t bound, uint64_t **ok, uint64_t **ov,
+                           int64_t **ow, int64_t *out_n) {
+    if (t.nb < 0 || t.nb > MAX_TRACE_BATCHES || (mode != 0 && mode != 1))
+        return DBSP_ERR_INVALID;
+    TruncArgs a{};
+    a.t = t;
+    a.mode = mode;
+    a.bound = bound;
+    int64_t nblk = 0;
+    for (int b = 0; b < t.nb; b++) {
+        ok[b] = ov[b] = nullptr;
+        ow[b] = nullptr;
+        out_n[b] = 0;
+        if (t.n[b] < 0) return DBSP_ERR_INVALID;
+        a.blk0[b] = nblk;
+        nblk += ceil_div(t.n[b], TRUNC_TILE);
+    }
+    a.blk0[t.nb] = nblk;
+    if (nblk == 0) return DBSP_OK;
+    if (nblk >= (int64_t)1 << 31) return DBSP_ERR_INVALID;  // grid.x limit
+    // counts[nblk] = 0 so the scan leaves the grand total there; the
+    // per-batch totals follow in the same buffer
+    uint64_t *counts;
+    HIP_CHECK(dbspk::cache_malloc(
+        (void **)&counts,
+        (nblk + 1 + MAX_TRACE_BATCHES) * sizeof(uint64_t), s));
+    int64_t *d_tot = (int64_t *)(counts + nblk + 1);
+    HIP_CHECK(hipMemsetAsync(counts + nblk, 0, sizeof(uint64_t), s));
+    k_trunc_count<<<dim3((uint32_t)nblk), BLK, 0, s>>>(a, counts);
+    TRY_K(scan_exclusive(s, counts, counts, nblk + 1, nullptr));
+    k_trunc_totals<<<1, WAVE, 0, s>>>(a, counts, d_tot);
+    int64_t h_tot[MAX_TRACE_BATCHES];
+    HIP_CHECK(hipMemcpyAsync(h_tot, d_tot, t.nb * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // the one length sync
+    TruncOut o{};
+    int64_t kept = 0;
+    for (int b = 0; b < t.nb; b++) {
+        const int64_t m = h_tot[b];
+        if (m < 0 || m > t.n[b]) return DBSP_ERR_INTERNAL;
+        out_n[b] = m;
+        kept += m;
+        if (m == 0) continue;
+        HIP_CHECK(dbspk::cache_malloc((void **)&ok[b], m * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)&ov[b], m * sizeof(uint64_t) + 8, s));
+        HIP_CHECK(dbspk::cache_malloc((void **)&ow[b], m * sizeof(int64_t) + 8, s));
+        o.k[b] = ok[b];
+        o.v[b] = ov[b];
+        o.w[b] = ow[b];
+    }
+    if (kept > 0)
+        k_trunc_emit<<<dim3((uint32_t)nblk), BLK, 0, s>>>(a, counts, o);
+    HIP_CHECK(dbspk::cache_free(counts, s));
+    return DBSP_OK;
+}
+
 dbsp_status roll_eval_rows(hipStream_t s, const uint64_t *sk,
                            const uint64_t *sv, const int64_t *sw, int64_t n,
                            const uint64_t *dk, const uint64_t *dv, int64_t nd,

@@ -407,6 +407,15 @@ dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
                          const TraceArgs &t, int mode, int64_t sign,
                          uint64_t **ok, uint64_t **ov, int64_t **ow,
                          int64_t *out_n);
+// keep the rows of every spine batch whose time is >= bound, in order
+// (trace.rs:463-607 lower bound).  mode 0: time = v (rows (p, ts, w));
+// mode 1: time = k & 0xffffffff (rows (p<<32|ts, sum, w)).  ok/ov/ow/out_n
+// are caller arrays of t.nb entries: batch b's survivors in fresh buffers
+// from the big-buffer cache (null when none survive).  Stable, so a
+// consolidated batch stays consolidated.  One host sync for all lengths.
+dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
+                           uint64_t bound, uint64_t **ok, uint64_t **ov,
+                           int64_t **ow, int64_t *out_n);
 // per row (p, ts, w > 0) of the consolidated slice that the delta affects:
 // (p<<32|ts, sum of slice weights of p over [ts-before, ts+after], +1),
 // in slice order (sorted, distinct keys)

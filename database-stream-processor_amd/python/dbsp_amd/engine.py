@@ -127,8 +127,29 @@ def _L():
                                          ctypes.POINTER(ctypes.c_int)]
         L.dbsp_rolling_destroy.restype = i32
         L.dbsp_rolling_destroy.argtypes = [vp]
+        L.dbsp_rolling_step_wm.restype = i32
+        L.dbsp_rolling_step_wm.argtypes = [vp, vp, vp, vp, i64, u64,
+                                           ctypes.POINTER(BatchStruct)]
+        L.dbsp_rolling_compact.restype = i32
+        L.dbsp_rolling_compact.argtypes = [vp]
+        L.dbsp_rolling_wm_stats.restype = i32
+        L.dbsp_rolling_wm_stats.argtypes = [vp, ctypes.POINTER(u64),
+                                            ctypes.POINTER(u64),
+                                            ctypes.POINTER(i64),
+                                            ctypes.POINTER(i64)]
+        L.dbsp_truncate_below.restype = i32
+        L.dbsp_truncate_below.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                          ctypes.c_int, u64,
+                                          ctypes.POINTER(BatchStruct)]
         L.dbsp_engine_rolling_init.restype = i32
         L.dbsp_engine_rolling_init.argtypes = [vp, u64, u64]
+        L.dbsp_engine_rolling_lateness.restype = i32
+        L.dbsp_engine_rolling_lateness.argtypes = [vp, u64]
+        L.dbsp_engine_rolling_stats.restype = i32
+        L.dbsp_engine_rolling_stats.argtypes = [vp, ctypes.POINTER(i64),
+                                                ctypes.POINTER(i64),
+                                                ctypes.POINTER(i64),
+                                                ctypes.POINTER(i64)]
         L.dbsp_engine_c5_init.restype = i32
         L.dbsp_engine_c5_init.argtypes = [vp, i64, i64, u64]
         L.dbsp_engine_kernel_stats.restype = i32
@@ -378,6 +399,19 @@ class Ctx:
             self.free_batch(x)
         return res
 
+    def truncate_below(self, rows, mode, bound):
+        """Rows whose time is >= bound, in order.  mode 0: time = v (rows
+        (partition, ts, w)); mode 1: time = k & 0xffffffff."""
+        inp = self.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_truncate_below(self._h, ctypes.byref(inp), mode,
+                                           bound, ctypes.byref(out))
+        self.free_batch(inp)
+        _check(st, "truncate_below")
+        res = self.download_rows(out)
+        self.free_batch(out)
+        return res
+
     def rolling_create(self, before, after):
         """Incremental partitioned rolling aggregate over
         [ts - before, ts + after] (see `Rolling`)."""
@@ -421,18 +455,43 @@ class Rolling:
     def __del__(self):
         self.close()
 
-    def step(self, rows: np.ndarray) -> np.ndarray:
+    def step(self, rows: np.ndarray, watermark=None) -> np.ndarray:
         """One tick: raw (unsorted, unconsolidated) delta rows in, output
-        delta out.  Raises (state unchanged) on a partition or ts >= 2^32."""
+        delta out.  Raises (state unchanged) on a partition or ts >= 2^32.
+
+        With a watermark the operator first raises its own to
+        max(current, watermark), drops and counts the rows below it, and
+        afterwards may delete trace rows below watermark - (before + after)
+        (see `wm_stats`, `compact`).  None leaves the watermark where it is."""
         raw = self._ctx.upload_rows(rows)
         out = BatchStruct()
-        st = self._lib.dbsp_rolling_step(self._h, raw.k, raw.v, raw.w,
-                                         raw.len, ctypes.byref(out))
+        if watermark is None:
+            st = self._lib.dbsp_rolling_step(self._h, raw.k, raw.v, raw.w,
+                                             raw.len, ctypes.byref(out))
+        else:
+            st = self._lib.dbsp_rolling_step_wm(self._h, raw.k, raw.v, raw.w,
+                                                raw.len, watermark,
+                                                ctypes.byref(out))
         self._ctx.free_batch(raw)
         _check(st, "rolling_step")
         res = self._ctx.download_rows(out)
         self._ctx.free_batch(out)
         return res
+
+    def compact(self):
+        """Delete the trace rows below the current bound now."""
+        _check(self._lib.dbsp_rolling_compact(self._h), "rolling_compact")
+
+    def wm_stats(self):
+        """(watermark, lower_bound, late_rows, sweeps)."""
+        wm, lb = ctypes.c_uint64(), ctypes.c_uint64()
+        late, sw = ctypes.c_int64(), ctypes.c_int64()
+        _check(self._lib.dbsp_rolling_wm_stats(self._h, ctypes.byref(wm),
+                                               ctypes.byref(lb),
+                                               ctypes.byref(late),
+                                               ctypes.byref(sw)),
+               "rolling_wm_stats")
+        return wm.value, lb.value, late.value, sw.value
 
     def stats(self):
         """(in_rows, in_batches, out_rows, out_batches) of the two traces."""
@@ -489,6 +548,19 @@ class Engine:
         after] in ms (defaults 10000 / 0); rejected after the first step."""
         _check(self._lib.dbsp_engine_rolling_init(self._h, before, after),
                "rolling_init")
+
+    def rolling_lateness(self, ms):
+        """Query 101: bound the operator's state by the watermark
+        max(bid date_time so far) - ms; rejected after the first step."""
+        _check(self._lib.dbsp_engine_rolling_lateness(self._h, ms),
+               "rolling_lateness")
+
+    def rolling_stats(self):
+        """Query 101: (in_rows, out_rows, late_rows, sweeps)."""
+        vals = [ctypes.c_int64() for _ in range(4)]
+        _check(self._lib.dbsp_engine_rolling_stats(
+            self._h, *[ctypes.byref(x) for x in vals]), "rolling_stats")
+        return tuple(x.value for x in vals)
 
     def step_staged(self, lo, hi):
         _check(self._lib.dbsp_engine_step_staged(self._h, lo, hi), "step")

@@ -212,6 +212,48 @@ dbsp_status dbsp_rolling_stats(dbsp_rolling *r, int64_t *in_rows,
                                int *out_batches);
 dbsp_status dbsp_rolling_destroy(dbsp_rolling *r);
 
+/* Watermark-bounded state (partitioned_rolling_aggregate_with_watermark,
+ * rolling_aggregate.rs:155-220 and :286-321).  The operator keeps a monotone
+ * watermark wm (0 at creation) and the bound
+ * lb = sat_sub(wm, before + after), 0 if before + after overflows u64.
+ * Rows of both traces with time < lb may be deleted: a row at ts >= wm only
+ * affects times >= wm - after, whose sums and retractions read nothing
+ * below lb, so the per-tick output equals the unbounded operator's as long
+ * as every row has ts >= wm.  A step with watermark x:
+ *   1. wm' = max(wm, x);
+ *   2. rows of the consolidated delta with ts < wm' are dropped whole and
+ *      counted (the reference only "does not expect" them,
+ *      rolling_aggregate.rs:126-129; dropping is this library's choice);
+ *   3. the dbsp_rolling_step tick on the surviving rows; on its
+ *      DBSP_ERR_INVALID nothing changes, wm and the counters included;
+ *   4. each trace whose rows exceed 2 * (rows after its previous sweep)
+ *      + 4096 is swept at lb (the TraceBounds lower bound, operator/
+ *      trace.rs:463-607, as an order-preserving device compaction) and its
+ *      surviving batches merged into one; no sweep while lb = 0.
+ * n == 0 still advances the watermark and may sweep.  dbsp_rolling_step is
+ * this call with watermark 0. */
+dbsp_status dbsp_rolling_step_wm(dbsp_rolling *r, const uint64_t *k,
+                                 const uint64_t *v, const int64_t *w, int64_t n,
+                                 uint64_t watermark, dbsp_batch *out);
+/* sweep both traces at the current bound now, whatever the policy says
+ * (trace.rs:463-607) */
+dbsp_status dbsp_rolling_compact(dbsp_rolling *r);
+/* watermark.rs:33-75 state and the bound derived from it
+ * (rolling_aggregate.rs:199-204), rows dropped as late, traces swept; any
+ * pointer may be null */
+dbsp_status dbsp_rolling_wm_stats(dbsp_rolling *r, uint64_t *watermark,
+                                  uint64_t *lower_bound, int64_t *late_rows,
+                                  int64_t *sweeps);
+
+/* TraceBounds val/key lower bound applied to one batch (operator/trace.rs
+ * :463-607): out = the rows of `in` whose time is >= bound, in order (so a
+ * consolidated batch stays consolidated).  mode 0: time = v (rows
+ * (partition, ts, w)); mode 1: time = k & 0xffffffff (rows
+ * (partition<<32 | ts, sum, w)).  Device arrays in and out; out is owned by
+ * the caller, null when empty. */
+dbsp_status dbsp_truncate_below(dbsp_ctx *ctx, const dbsp_batch *in, int mode,
+                                uint64_t bound, dbsp_batch *out);
+
 dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *ctx,
                                    const uint64_t *delta_keys, int64_t nd,
                                    const dbsp_batch *in_trace,
@@ -327,6 +369,19 @@ dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
  * another query or after the engine's first step. */
 dbsp_status dbsp_engine_rolling_init(dbsp_engine *e, uint64_t before_ms,
                                      uint64_t after_ms);
+/* watermark_monotonic(|ts| ts.saturating_sub(lateness_ms)) over the bid stream
+ * (watermark.rs:33-75) feeding partitioned_rolling_aggregate_with_watermark
+ * (rolling_aggregate.rs:155-220): per tick the watermark is the largest bid
+ * time seen so far, this tick's rows included, minus lateness_ms, and the
+ * step is dbsp_rolling_step_wm.  Sharded ranks use their rank-local maximum
+ * (no collective).  Off by default; DBSP_ERR_INVALID on another query or
+ * after the first step. */
+dbsp_status dbsp_engine_rolling_lateness(dbsp_engine *e, uint64_t lateness_ms);
+/* query 101 trace rows and watermark counters (Spine introspection,
+ * trace/spine_fueled.rs:107-119); any out pointer may be null */
+dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e, int64_t *in_rows,
+                                      int64_t *out_rows, int64_t *late_rows,
+                                      int64_t *sweeps);
 dbsp_status dbsp_engine_destroy(dbsp_engine *e);
 
 /* C5 (query 100) setup: device-generates the n_trace-row (k, f64-bits, +1)

@@ -7,6 +7,7 @@ join kernels are HBM-bound, and reports achieved algorithmic GB/s against the
 
 Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
                        python tools/kbench.py --only rolling [--roll-rows N]
+                       python tools/kbench.py --only rolling_wm
 Prints one JSON line per primitive.
 """
 import argparse
@@ -442,6 +443,163 @@ def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
     }
 
 
+def _med(x):
+    s = sorted(x)
+    return s[len(s) // 2]
+
+
+def bench_rolling_wm_operator(ctx, L, parts, n_delta, late_frac, before,
+                              after, ticks, span, lateness, every):
+    """Watermark-bounded operator (dbsp_rolling_step_wm) against the
+    unbounded one (dbsp_rolling_step) of the same build on one frontier
+    stream: tick t draws its times from [t*span, (t+1)*span) past a base of
+    `lateness` and passes the watermark (t+1)*span - 1 (the largest time the
+    tick can hold minus the lateness, so no readback); a late_frac share of
+    its rows is drawn from between that watermark and the tick's frontier
+    instead (late, but inside the lateness: no row is dropped).
+    Host clock around calls that end in a stream synchronise."""
+    assert lateness > span
+    g = torch.Generator(device="cuda").manual_seed(29)
+    n_late = int(n_delta * late_frac)
+    deltas = []
+    for t in range(ticks):
+        k = torch.randint(0, parts, (n_delta,), generator=g,
+                          dtype=torch.int64, device="cuda")
+        v = lateness + t * span + torch.randint(
+            0, span, (n_delta,), generator=g, dtype=torch.int64,
+            device="cuda")
+        wm = (t + 1) * span - 1
+        if n_late:
+            v[:n_late] = wm + torch.randint(
+                0, lateness - span + 1, (n_late,), generator=g,
+                dtype=torch.int64, device="cuda")
+        w = torch.ones(n_delta, dtype=torch.int64, device="cuda")
+        deltas.append((k, v, w, wm))
+    torch.cuda.synchronize()
+    legs = {}
+    for name in ("bounded", "unbounded"):
+        op = ctx.rolling_create(before, after)
+        ms, rows, rows_out, peak = [], [], 0, [0, 0]
+        for t, (k, v, w, wm) in enumerate(deltas):
+            out = BatchStruct()
+            ctx.sync()
+            t0 = time.perf_counter()
+            if name == "bounded":
+                st = L.dbsp_rolling_step_wm(op._h, k.data_ptr(), v.data_ptr(),
+                                            w.data_ptr(), n_delta, wm,
+                                            ctypes.byref(out))
+            else:
+                st = L.dbsp_rolling_step(op._h, k.data_ptr(), v.data_ptr(),
+                                         w.data_ptr(), n_delta,
+                                         ctypes.byref(out))
+            ms.append((time.perf_counter() - t0) * 1e3)
+            assert st == 0
+            rows_out += out.len
+            ctx.free_batch(out)
+            s = op.stats()
+            peak = [max(peak[0], s[0]), max(peak[1], s[2])]
+            if (t + 1) % every == 0:
+                rows.append({"tick": t + 1, "in_rows": s[0], "out_rows": s[2]})
+        q = max(1, ticks // 4)
+        wm, lb, late, sweeps = op.wm_stats()
+        legs[name] = {
+            "rows_every_%d_ticks" % every: rows,
+            "in_rows_max": peak[0], "out_rows_max": peak[1],
+            "ms_median_first_quarter": round(_med(ms[:q]), 3),
+            "ms_median_last_quarter": round(_med(ms[-q:]), 3),
+            "ms_max": round(max(ms), 3),
+            "rows_out_total": rows_out, "watermark": wm, "lower_bound": lb,
+            "late_rows": late, "sweeps": sweeps,
+        }
+        op.close()
+    assert legs["bounded"]["rows_out_total"] == \
+        legs["unbounded"]["rows_out_total"]
+    return {
+        "primitive": "dbsp_rolling_step_wm (watermark-bounded state) vs "
+                     "dbsp_rolling_step on one frontier stream",
+        "partitions": parts, "delta_rows": n_delta, "late_frac": late_frac,
+        "before": before, "after": after, "ticks": ticks, "span": span,
+        "lateness": lateness, **legs,
+    }
+
+
+def bench_truncate(ctx, L, n, reps=5, run=64):
+    """dbsp_truncate_below (mode 0) on n consolidated rows (p, ts, +-1) in
+    partitions of `run` rows with the first half of every partition below the
+    bound, against device-to-device hipMemcpyAsync calls over the same
+    buffers whose sizes add up to 24n + 24*kept bytes (the three input
+    columns and the three output columns, each copied into scratch).  A copy
+    of B bytes reads B and writes B; the kernel's own model is 8n (count
+    pass) + 24n (emit reads) + 24*kept (emit writes).  One untimed warm-up
+    call each; host clock around calls that end in a synchronise."""
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_size_t, ctypes.c_int,
+                                   ctypes.c_void_p]
+    reps = int(os.environ.get("KB_REPS", reps))
+    i = torch.arange(n, dtype=torch.int64, device="cuda")
+    k, v = i // run, i % run
+    w = torch.where(i % 3 == 0, -1, 1).to(torch.int64)
+    del i
+    scratch = torch.empty(n, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    b = as_batch(k, v, w)
+    times, kept, out = [], 0, None
+    for r in range(reps + 1):
+        if out is not None:
+            ctx.free_batch(out)
+        out = BatchStruct()
+        ctx.sync()
+        t0 = time.perf_counter()
+        assert L.dbsp_truncate_below(ctx._h, ctypes.byref(b), 0, run // 2,
+                                     ctypes.byref(out)) == 0
+        dt = time.perf_counter() - t0
+        if r:
+            times.append(dt)
+        kept = out.len
+    pieces = [(k.data_ptr(), 8 * n), (v.data_ptr(), 8 * n),
+              (w.data_ptr(), 8 * n), (out.k, 8 * kept), (out.v, 8 * kept),
+              (out.w, 8 * kept)]
+    ctimes = []
+    for r in range(reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for src, nbytes in pieces:
+            assert hip.hipMemcpyAsync(scratch.data_ptr(), src, nbytes, 3,
+                                      None) == 0       # 3 = device to device
+        torch.cuda.synchronize()
+        if r:
+            ctimes.append(time.perf_counter() - t0)
+    ctx.free_batch(out)
+    algo = 8.0 * n + 24.0 * n + 24.0 * kept
+    copy_bytes = 24.0 * n + 24.0 * kept
+    return {
+        "primitive": "dbsp_truncate_below (order-preserving spine "
+                     "truncation) vs device-to-device hipMemcpyAsync",
+        "rows": n, "kept": kept, "partition_rows": run,
+        "rep_ms": [round(t * 1e3, 3) for t in times],
+        "ms_min": round(min(times) * 1e3, 3),
+        "ms_median": round(_med(times) * 1e3, 3),
+        "algo_GB": round(algo / 1e9, 3),
+        "achieved_GBs": round(algo / min(times) / 1e9, 1),
+        "frac_of_peak": round(algo / min(times) / 1e9 / HBM_PEAK_GBS, 4),
+        "copy_bytes": int(copy_bytes),
+        "copy_rep_ms": [round(t * 1e3, 3) for t in ctimes],
+        "copy_ms_min": round(min(ctimes) * 1e3, 3),
+        "copy_ms_median": round(_med(ctimes) * 1e3, 3),
+        "copy_moved_GBs": round(2 * copy_bytes / min(ctimes) / 1e9, 1),
+    }
+
+
+def bench_rolling_wm(ctx, L, args):
+    yield bench_rolling_wm_operator(ctx, L, args.roll_parts, args.roll_delta,
+                                    args.roll_late, args.roll_before,
+                                    args.roll_after, args.wm_ticks, 64,
+                                    args.wm_lateness, args.wm_every)
+    for n in args.trunc_rows:
+        yield bench_truncate(ctx, L, n)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=500_000_000,
@@ -450,7 +608,15 @@ def main():
     ap.add_argument("--sort-rows", type=int, default=50_000_000)
     ap.add_argument("--only", default=None,
                     choices=["merge", "join", "sort", "incremental", "c5",
-                             "rolling"])
+                             "rolling", "rolling_wm"])
+    ap.add_argument("--wm-ticks", type=int, default=200,
+                    help="rolling_wm leg: ticks of the frontier stream")
+    ap.add_argument("--wm-lateness", type=int, default=1024)
+    ap.add_argument("--wm-every", type=int, default=25,
+                    help="rolling_wm leg: record trace rows every N ticks")
+    ap.add_argument("--trunc-rows", type=int, nargs="*",
+                    default=[4_000_000, 16_000_000, 64_000_000],
+                    help="rolling_wm leg: dbsp_truncate_below sizes")
     ap.add_argument("--roll-rows", type=int, default=4_000_000,
                     help="rolling leg: trace rows")
     ap.add_argument("--roll-parts", type=int, default=1024)
@@ -478,6 +644,9 @@ def main():
         # the rolling leg runs on request only: a bare run keeps its legs
         if args.only == name or (args.only is None and name != "rolling"):
             print(json.dumps(leg()))
+    if args.only == "rolling_wm":       # on request only, as the rolling leg
+        for res in bench_rolling_wm(ctx, L, args):
+            print(json.dumps(res), flush=True)
     ctx.close()
 
 
