@@ -63,6 +63,65 @@ struct KernelStat {
     int64_t launches = 0;
 };
 
+// Length-slot layout of dbsp_ctx::d_len / h_len (int64 slots; the one
+// description of it).  Kernels leave lengths, totals and -1 poison/overflow
+// sentinels in the device slots; the host reads them from the pinned mirror
+// after a readback (read_len below), normally at the same index.
+//
+//   [LEN_OP ..)          ops that sync at once (sized sorts and merges, the
+//                        aggregate's join count) borrow up to SORT_BATCH_MAX
+//                        slots from the start of tick base 0 (they alias
+//                        that base's first offsets)
+//   [sb, sb + 18)        one chained tick, sb = LEN_BASE0 or LEN_BASE1 (q3's
+//                        pipelined trains ping-pong; everything else uses
+//                        LEN_BASE0).  Offsets inside a base are the L_* below
+//   [LEN_ROUND, +4)      spine-insert merge rounds: their readback can be
+//                        consumed after the next train's 18-slot readback
+//                        has landed, so it cannot live inside a base
+//   the rest up to LEN_SLOTS is unused padding
+enum : int {
+    LEN_SLOTS = 44,
+    LEN_OP = 0,
+    LEN_BASE0 = 0,
+    LEN_BASE1 = 18,
+    LEN_TICK = 18,       // slots per tick base (= the train's one readback)
+    LEN_ROUND = 36,
+    LEN_ROUND_N = MERGE_BATCH_MAX,
+    // offsets inside a tick base
+    L_PLAN = 0,          // 0..2: q3 join-plan count totals (-1: lost spec)
+    L_EMIT_TOTAL = 3,    // fused emit: combined row total (or -1)
+    L_EMIT_FLAG = 4,     // fused emit: nonzero = capacity overflow
+    L_DENSE = 5,         // q5: chained dense-sort length of the bid delta
+    L_FINAL = 6,         // output (final) sort length
+    L_WIN = 7,           // single-spine window total (q5, window_vs_spine)
+    L_RAW = 8,           // 8/9: flatmap raw lengths of streams A/B
+    L_DELTA = 10,        // 10/11: consolidated delta lengths (-1: overflow)
+    L_WIN2 = 12,         // 12/13: q8's two window totals (-1: lost spec)
+    L_MINMAX = 12,       // 12..15: q5's {kmin, vmin, kmax, vmax} of the bids
+    L_XCHG = 16,         // 16/17: framed-exchange receive totals (-1:
+                         // frame overflow); q3's unsharded train reuses them
+                         // for its two accumulator-merge lengths
+    // q3's second readback (q3_chain_emits) copies device offsets
+    // [L_EMIT_TOTAL, L_FINAL] to HOST offsets shifted by LH_TAIL_SHIFT, so
+    // the first readback's copies of plan totals and delta lengths stay
+    // intact for the verdict.  Host offsets 12..15 are free in a q3 tick
+    // (L_WIN2 / L_MINMAX belong to q8 / q5).
+    LH_TAIL_SHIFT = 9,
+    LH_TAIL_N = L_FINAL - L_EMIT_TOTAL + 1,
+    LH_EMIT_TOTAL = L_EMIT_TOTAL + LH_TAIL_SHIFT,  // 12
+    LH_EMIT_FLAG = L_EMIT_FLAG + LH_TAIL_SHIFT,    // 13
+    LH_FINAL = L_FINAL + LH_TAIL_SHIFT,            // 15
+};
+static_assert(LEN_BASE1 + LEN_TICK <= LEN_ROUND &&
+                  LEN_ROUND + LEN_ROUND_N <= LEN_SLOTS,
+              "both tick bases and the round slots fit the allocation");
+static_assert(LEN_BASE0 + LEN_TICK <= LEN_BASE1, "tick bases overlap");
+static_assert(LH_EMIT_TOTAL > L_DELTA + 1 &&
+                  LH_EMIT_TOTAL + LH_TAIL_N <= L_XCHG,
+              "second-readback host range stays inside its base, clear of "
+              "the slots the verdict still reads");
+static_assert(LEN_OP + SORT_BATCH_MAX <= LEN_TICK, "op scratch inside base 0");
+
 struct dbsp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -75,12 +134,10 @@ struct dbsp_ctx {
     bool force_shard = false;  // exercise the full partition+alltoallv path
                                // even at world=1 (self-exchange; test hook)
     // persistent length scratch (device + pinned host)
-    int64_t *d_len = nullptr;   // 44 device length slots: two 18-slot tick
-                                // bases (0 and 18: chained-tick lengths,
-                                // sb+16/17 = framed-exchange totals) +
-                                // 36-39 spine-insert rounds
+    int64_t *d_len = nullptr;  // LEN_SLOTS slots, layout above
     int64_t *h_len = nullptr;
-    int64_t *d_mid = nullptr;  // merge_mid per-WG count scratch (2 pairs)
+    int64_t *d_mid = nullptr;  // merge_mid per-WG count scratch
+                               // (MERGE_BATCH_MAX pairs)
     int timer_depth = 0;  // ScopedTimer nesting guard (shared event pair)
     // per-tick transient bump arena (reset at each engine tick; falls back to
     // the stream-ordered pool when exhausted)
@@ -98,14 +155,34 @@ struct dbsp_ctx {
     // deferred spine-insert round (train path): the last small-merge round's
     // length readback is resolved at the NEXT insert/step on a near-empty
     // stream instead of blocking behind the next tick's freshly enqueued
-    // train (h_len[36..39] hold its counts until then)
+    // train (the LEN_ROUND host slots hold its counts until then)
     hipEvent_t ev_insert = nullptr;
     int pend_n = 0;
     void *pend_spine[4] = {};
     uint64_t *pend_k[4] = {}, *pend_v[4] = {};
     int64_t *pend_w[4] = {};
-    int pend_slot[4] = {};  // h_len slot (36+s) holding each result length
+    int pend_slot[4] = {};  // LEN_ROUND + s holds each result length
 };
+
+// Length readback: copy `count` device slots from `first` to host slots from
+// `host_first`; with sync, wait for them.  Every read of h_len follows one.
+static dbsp_status read_len_to(dbsp_ctx *c, int host_first, int first,
+                               int count, bool sync) {
+    HIP_CHECK_ST(hipMemcpyAsync(c->h_len + host_first, c->d_len + first,
+                                count * sizeof(int64_t),
+                                hipMemcpyDeviceToHost, c->stream));
+    if (sync) HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return DBSP_OK;
+}
+static inline dbsp_status read_len(dbsp_ctx *c, int first, int count,
+                                   bool sync = true) {
+    return read_len_to(c, first, first, count, sync);
+}
+// a host length slot whose kernel poisons it (-1) on a broken fused barrier
+static inline dbsp_status checked_len(dbsp_ctx *c, int slot, int64_t &n) {
+    n = c->h_len[slot];
+    return n < 0 ? DBSP_ERR_INTERNAL : DBSP_OK;
+}
 
 static void *arena_alloc(dbsp_ctx *c, size_t bytes) {
     bytes = (bytes + 255) & ~(size_t)255;
@@ -115,6 +192,13 @@ static void *arena_alloc(dbsp_ctx *c, size_t bytes) {
     void *p = c->arena + c->arena_base + c->arena_off;
     c->arena_off += bytes;
     return p;
+}
+
+// restart the bump arena in the half that does not start at `base` (two
+// ticks' transients are live at once); an unsplit arena just restarts
+static inline void arena_other_half(dbsp_ctx *c, size_t base) {
+    if (c->arena_half) c->arena_base = base ? 0 : c->arena_half;
+    c->arena_off = 0;
 }
 
 static inline bool in_arena(dbsp_ctx *c, const void *p) {
@@ -162,15 +246,16 @@ extern "C" dbsp_status dbsp_ctx_create(dbsp_ctx **out, int device) {
     c->profile = p && p[0] == '1';
     const char *fs = getenv("DBSP_FORCE_SHARD");
     c->force_shard = fs && fs[0] == '1';
-    HIP_CHECK_ST(hipMalloc(&c->d_len, 44 * sizeof(int64_t)));
-    HIP_CHECK_ST(hipMalloc(&c->d_mid, 4 * MERGE_MID_SCRATCH * sizeof(int64_t)));
+    HIP_CHECK_ST(hipMalloc(&c->d_len, LEN_SLOTS * sizeof(int64_t)));
+    HIP_CHECK_ST(hipMalloc(&c->d_mid, MERGE_BATCH_MAX * MERGE_MID_SCRATCH *
+                                          sizeof(int64_t)));
     c->arena_sz = (size_t)512 << 20;
     c->arena_half = c->arena_sz / 2;
     if (hipMalloc(&c->arena, c->arena_sz) != hipSuccess) {
         c->arena = nullptr;
         c->arena_sz = 0;
     }
-    HIP_CHECK_ST(hipHostMalloc(&c->h_len, 44 * sizeof(int64_t)));
+    HIP_CHECK_ST(hipHostMalloc(&c->h_len, LEN_SLOTS * sizeof(int64_t)));
     *out = c;
     return DBSP_OK;
 }
@@ -290,26 +375,106 @@ static dbsp_status alloc_batch(dbsp_ctx *c, int64_t n, DevBatch &b,
     return DBSP_OK;
 }
 
-// concat batches into one (raw, unsorted use)
+// device-to-device copy of n rows' three columns to dst rows [off, off + n)
+static dbsp_status copy_cols(dbsp_ctx *c, const DevBatch &dst, int64_t off,
+                             const uint64_t *k, const uint64_t *v,
+                             const void *w, int64_t n) {
+    if (n == 0) return DBSP_OK;
+    HIP_CHECK_ST(hipMemcpyAsync(dst.k + off, k, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(dst.v + off, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(dst.w + off, w, n * 8, hipMemcpyDeviceToDevice, c->stream));
+    return DBSP_OK;
+}
+
+// concat batches into one freshly allocated batch (raw, unsorted use)
 static dbsp_status concat_batches(dbsp_ctx *c, const std::vector<DevBatch> &in,
-                                  DevBatch &out) {
+                                  DevBatch &out, bool transient = false) {
     int64_t total = 0;
     for (auto &b : in) total += b.n;
-    TRY(alloc_batch(c, total, out));
+    TRY(alloc_batch(c, total, out, transient));
     int64_t off = 0;
     for (auto &b : in) {
-        if (b.n == 0) continue;
-        HIP_CHECK_ST(hipMemcpyAsync(out.k + off, b.k, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(out.v + off, b.v, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(out.w + off, b.w, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
+        TRY(copy_cols(c, out, off, b.k, b.v, b.w, b.n));
         off += b.n;
     }
     out.n = total;
     return DBSP_OK;
 }
 
+static inline void put_batch(dbsp_batch *out, const DevBatch &b) {
+    out->k = b.k; out->v = b.v; out->w = b.w; out->len = b.n;
+}
+static inline DevBatch as_batch(const dbsp_batch *b) {
+    return DevBatch{b->k, b->v, b->w, b->len};
+}
+
+// ---- launch-descriptor fills ----
+
+// slot i of a fused sort: in -> out through scratch.  n_dev (a device length
+// slot) overrides the host length, which then stays 0.
+static inline void sort_slot(SortArgs &sa, int i, const DevBatch &in,
+                             const DevBatch &scratch, const DevBatch &out,
+                             const int64_t *n_dev = nullptr) {
+    sa.kin[i] = in.k; sa.vin[i] = in.v; sa.win[i] = in.w;
+    sa.n[i] = n_dev ? 0 : in.n;
+    sa.n_dev[i] = n_dev;
+    sa.tk[i] = scratch.k; sa.tv[i] = scratch.v; sa.tw[i] = scratch.w;
+    sa.ok[i] = out.k; sa.ov[i] = out.v; sa.ow[i] = out.w;
+}
+
+// pair p of a batched merge: a + b -> out.  dnb (a device length slot)
+// overrides b's host length, which then stays 0.
+static inline void merge_pair(MergeArgs &ma, int p, const DevBatch &a,
+                              const DevBatch &b, const DevBatch &out,
+                              const int64_t *dnb = nullptr) {
+    ma.ak[p] = a.k; ma.av[p] = a.v; ma.aw[p] = a.w; ma.na[p] = a.n;
+    ma.bk[p] = b.k; ma.bv[p] = b.v; ma.bw[p] = b.w;
+    ma.nb[p] = dnb ? 0 : b.n;
+    ma.dnb[p] = dnb;
+    ma.ok[p] = out.k; ma.ov[p] = out.v; ma.ow[p] = out.w;
+}
+
+static inline void trace_push(TraceArgs &t, const DevBatch &b) {
+    t.k[t.nb] = b.k; t.v[t.nb] = b.v; t.w[t.nb] = b.w; t.n[t.nb] = b.n;
+    t.nb++;
+}
+static inline TraceArgs trace_args_one(const DevBatch &b) {
+    TraceArgs t{};
+    trace_push(t, b);
+    return t;
+}
+
+// the weight type's three merge kernels (tiny single-WG, fixed-grid mid,
+// multi-block two-pass); f64 weights travel as their bit patterns
+struct MergeOps {
+    dbsp_status (*small)(hipStream_t, const MergeArgs &);
+    dbsp_status (*mid)(hipStream_t, const MergeArgs &, int64_t *);
+    dbsp_status (*rows)(hipStream_t, const uint64_t *, const uint64_t *,
+                        const int64_t *, int64_t, const uint64_t *,
+                        const uint64_t *, const int64_t *, int64_t,
+                        uint64_t **, uint64_t **, int64_t **, int64_t *);
+};
+static dbsp_status merge_rows_f64_bits(hipStream_t s, const uint64_t *ak,
+                                       const uint64_t *av, const int64_t *aw,
+                                       int64_t na, const uint64_t *bk,
+                                       const uint64_t *bv, const int64_t *bw,
+                                       int64_t nb, uint64_t **ok, uint64_t **ov,
+                                       int64_t **ow, int64_t *out_n) {
+    return dbspk::merge_rows_f64(s, ak, av, (const double *)aw, na, bk, bv,
+                                 (const double *)bw, nb, ok, ov, (double **)ow,
+                                 out_n);
+}
+static const MergeOps MERGE_I64 = {dbspk::merge_small_batch,
+                                   dbspk::merge_mid_batch, dbspk::merge_rows};
+// (config C5's weighted integral spine; position-fixed reduction orders,
+// algebra/floats.rs:24 zero elimination)
+static const MergeOps MERGE_F64 = {dbspk::merge_small_batch_f64,
+                                   dbspk::merge_mid_batch_f64,
+                                   merge_rows_f64_bits};
+
 static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
-                                 const DevBatch &b, DevBatch &out);
+                                 const DevBatch &b, DevBatch &out,
+                                 const MergeOps &ops = MERGE_I64);
 
 // medium raw batches (8192 < n <= 64k): chunk into <=8 fused single-WG sorts
 // in ONE launch, then a batched single-WG merge tree (3 launches, 1 sync per
@@ -324,17 +489,13 @@ static dbsp_status sort_medium(dbsp_ctx *c, DevBatch raw, DevBatch &out) {
         int64_t len = std::min<int64_t>(8192, raw.n - lo);
         TRY(alloc_batch(c, len, scratch[i], true));
         TRY(alloc_batch(c, len, chunks[i], true));
-        sa.kin[i] = raw.k + lo; sa.vin[i] = raw.v + lo; sa.win[i] = raw.w + lo;
-        sa.n[i] = len;
-        sa.tk[i] = scratch[i].k; sa.tv[i] = scratch[i].v; sa.tw[i] = scratch[i].w;
-        sa.ok[i] = chunks[i].k; sa.ov[i] = chunks[i].v; sa.ow[i] = chunks[i].w;
+        sort_slot(sa, i, DevBatch{raw.k + lo, raw.v + lo, raw.w + lo, len},
+                  scratch[i], chunks[i]);
     }
-    sa.d_len = c->d_len;
+    sa.d_len = c->d_len + LEN_OP;
     TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, nch * sizeof(int64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < nch; i++) chunks[i].n = c->h_len[i];
+    TRY(read_len(c, LEN_OP, nch));
+    for (int i = 0; i < nch; i++) chunks[i].n = c->h_len[LEN_OP + i];
     free_batch(c, raw);
     for (auto &sc : scratch) free_batch(c, sc);
     // batched pairwise merge rounds
@@ -355,10 +516,7 @@ static dbsp_status sort_medium(dbsp_ctx *c, DevBatch raw, DevBatch &out) {
             bool final_round = (cur.size() == 2);
             TRY(alloc_batch(c, a.n + b.n, res, !final_round));
             MergeArgs &mx = a.n + b.n <= 4096 ? ma : mm;
-            int p = mx.np++;
-            mx.ak[p] = a.k; mx.av[p] = a.v; mx.aw[p] = a.w; mx.na[p] = a.n;
-            mx.bk[p] = b.k; mx.bv[p] = b.v; mx.bw[p] = b.w; mx.nb[p] = b.n;
-            mx.ok[p] = res.k; mx.ov[p] = res.v; mx.ow[p] = res.w;
+            merge_pair(mx, mx.np++, a, b, res);
             ismid.push_back(&mx == &mm);
             results.push_back(res);
         }
@@ -367,19 +525,14 @@ static dbsp_status sort_medium(dbsp_ctx *c, DevBatch raw, DevBatch &out) {
                 int ps = 0, pm = ma.np;
                 for (bool m : ismid) slots.push_back(m ? pm++ : ps++);
             }
-            ma.d_len = c->d_len;
-            mm.d_len = c->d_len + ma.np;
+            ma.d_len = c->d_len + LEN_OP;
+            mm.d_len = c->d_len + LEN_OP + ma.np;
             if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma));
             if (mm.np > 0)
                 TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid));
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                        (ma.np + mm.np) * sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            for (size_t p = 0; p < results.size(); p++) {
-                results[p].n = c->h_len[slots[p]];
-                if (results[p].n < 0) return DBSP_ERR_INTERNAL;
-            }
+            TRY(read_len(c, LEN_OP, ma.np + mm.np));
+            for (size_t p = 0; p < results.size(); p++)
+                TRY(checked_len(c, LEN_OP + slots[p], results[p].n));
             for (size_t j = 0; j < 2 * results.size(); j++)
                 free_batch(c, cur[j]);
             next.insert(next.end(), results.begin(), results.end());
@@ -439,15 +592,11 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
         TRY(alloc_batch(c, raw.n, res));
         SortArgs sa{};
         sa.nb = 1;
-        sa.kin[0] = raw.k; sa.vin[0] = raw.v; sa.win[0] = raw.w; sa.n[0] = raw.n;
-        sa.tk[0] = scratch.k; sa.tv[0] = scratch.v; sa.tw[0] = scratch.w;
-        sa.ok[0] = res.k; sa.ov[0] = res.v; sa.ow[0] = res.w;
-        sa.d_len = c->d_len;
+        sort_slot(sa, 0, raw, scratch, res);
+        sa.d_len = c->d_len + LEN_OP;
         TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        res.n = *c->h_len;
+        TRY(read_len(c, LEN_OP, 1));
+        res.n = c->h_len[LEN_OP];
         free_batch(c, raw);
         free_batch(c, scratch);
         out = res;
@@ -465,7 +614,8 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
 }
 
 static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
-                                 const DevBatch &b, DevBatch &out) {
+                                 const DevBatch &b, DevBatch &out,
+                                 const MergeOps &ops) {
     ScopedTimer t(c, 1, (double)(a.n + b.n) * 48.0);
     // three bands: tiny pairs (<= 4k) in one single-WG launch; mid pairs
     // (<= 32k) in the fixed-grid multi-WG merge (a 16k single-WG merge
@@ -476,59 +626,19 @@ static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
         TRY(alloc_batch(c, a.n + b.n, res));
         MergeArgs ma{};
         ma.np = 1;
-        ma.ak[0] = a.k; ma.av[0] = a.v; ma.aw[0] = a.w; ma.na[0] = a.n;
-        ma.bk[0] = b.k; ma.bv[0] = b.v; ma.bw[0] = b.w; ma.nb[0] = b.n;
-        ma.ok[0] = res.k; ma.ov[0] = res.v; ma.ow[0] = res.w;
-        ma.d_len = c->d_len;
+        merge_pair(ma, 0, a, b, res);
+        ma.d_len = c->d_len + LEN_OP;
         if (a.n + b.n <= 4096)
-            TRY(dbspk::merge_small_batch(c->stream, ma));
+            TRY(ops.small(c->stream, ma));
         else
-            TRY(dbspk::merge_mid_batch(c->stream, ma, c->d_mid));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        res.n = *c->h_len;
-        if (res.n < 0) return DBSP_ERR_INTERNAL;  // fused-barrier poison
+            TRY(ops.mid(c->stream, ma, c->d_mid));
+        TRY(read_len(c, LEN_OP, 1));
+        TRY(checked_len(c, LEN_OP, res.n));  // fused-barrier poison
         out = res;
         return DBSP_OK;
     }
-    TRY(dbspk::merge_rows(c->stream, a.k, a.v, a.w, a.n, b.k, b.v, b.w, b.n,
-                          &out.k, &out.v, &out.w, &out.n));
-    return DBSP_OK;
-}
-
-// f64-weighted twin of merge_batches (config C5's weighted integral spine;
-// position-fixed reduction orders, algebra/floats.rs:24 zero elimination)
-static dbsp_status merge_batches_f64(dbsp_ctx *c, const DevBatch &a,
-                                     const DevBatch &b, DevBatch &out) {
-    ScopedTimer t(c, 1, (double)(a.n + b.n) * 48.0);
-    if (a.n + b.n <= 32768) {
-        DevBatch res;
-        TRY(alloc_batch(c, a.n + b.n, res));
-        MergeArgs ma{};
-        ma.np = 1;
-        ma.ak[0] = a.k; ma.av[0] = a.v; ma.aw[0] = a.w; ma.na[0] = a.n;
-        ma.bk[0] = b.k; ma.bv[0] = b.v; ma.bw[0] = b.w; ma.nb[0] = b.n;
-        ma.ok[0] = res.k; ma.ov[0] = res.v; ma.ow[0] = res.w;
-        ma.d_len = c->d_len;
-        if (a.n + b.n <= 4096)
-            TRY(dbspk::merge_small_batch_f64(c->stream, ma));
-        else
-            TRY(dbspk::merge_mid_batch_f64(c->stream, ma, c->d_mid));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        res.n = *c->h_len;
-        if (res.n < 0) return DBSP_ERR_INTERNAL;  // fused-barrier poison
-        out = res;
-        return DBSP_OK;
-    }
-    double *rw;
-    TRY(dbspk::merge_rows_f64(c->stream, a.k, a.v, (const double *)a.w, a.n,
-                              b.k, b.v, (const double *)b.w, b.n, &out.k,
-                              &out.v, &rw, &out.n));
-    out.w = (int64_t *)rw;
-    return DBSP_OK;
+    return ops.rows(c->stream, a.k, a.v, a.w, a.n, b.k, b.v, b.w, b.n, &out.k,
+                    &out.v, &out.w, &out.n);
 }
 
 // Spine: stack of consolidated batches; invariant size[i] >= 2*size[i+1]
@@ -545,8 +655,13 @@ struct Spine {
 
     dbsp_status merge2(dbsp_ctx *c, const DevBatch &a, const DevBatch &b,
                        DevBatch &out) const {
-        return wf64 ? merge_batches_f64(c, a, b, out)
-                    : merge_batches(c, a, b, out);
+        return merge_batches(c, a, b, out, wf64 ? MERGE_F64 : MERGE_I64);
+    }
+
+    // more batches than a TraceArgs holds: merge down to one
+    dbsp_status cap_batches(dbsp_ctx *c) {
+        if ((int)batches.size() > MAX_TRACE_BATCHES) return consolidate_all(c);
+        return DBSP_OK;
     }
 
     dbsp_status insert(dbsp_ctx *c, DevBatch b) {
@@ -561,14 +676,7 @@ struct Spine {
             if (top.n * 2 < below.n) break;  // geometric invariant holds
             DevBatch merged;
             TRY(merge2(c, below, top, merged));
-            free_batch(c, top);
-            free_batch(c, below);
-            batches.pop_back();
-            batches.pop_back();
-            if (merged.n > 0)
-                batches.push_back(merged);
-            else
-                free_batch(c, merged);
+            replace_top2(c, merged);
         }
         return DBSP_OK;
     }
@@ -576,20 +684,23 @@ struct Spine {
     // exhaustive merge to a single batch (consolidate.rs:33-47 semantics)
     dbsp_status consolidate_all(dbsp_ctx *c) {
         while (batches.size() >= 2) {
-            DevBatch top = batches.back();
-            batches.pop_back();
-            DevBatch below = batches.back();
-            batches.pop_back();
             DevBatch merged;
-            TRY(merge2(c, below, top, merged));
-            free_batch(c, top);
-            free_batch(c, below);
-            if (merged.n > 0)
-                batches.push_back(merged);
-            else
-                free_batch(c, merged);
+            TRY(merge2(c, batches[batches.size() - 2], batches.back(), merged));
+            replace_top2(c, merged);
         }
         return DBSP_OK;
+    }
+
+    // the two topmost batches give way to their merge (dropped when empty)
+    void replace_top2(dbsp_ctx *c, DevBatch merged) {
+        free_batch(c, batches.back());
+        batches.pop_back();
+        free_batch(c, batches.back());
+        batches.pop_back();
+        if (merged.n > 0)
+            batches.push_back(merged);
+        else
+            free_batch(c, merged);
     }
 
     void clear(dbsp_ctx *c) {
@@ -597,6 +708,14 @@ struct Spine {
         batches.clear();
     }
 };
+
+// a spine's non-empty batches as a kernel argument
+static TraceArgs trace_args_of(const Spine &sp) {
+    TraceArgs t{};
+    for (auto &b : sp.batches)
+        if (b.n != 0) trace_push(t, b);
+    return t;
+}
 
 // Incremental partitioned rolling aggregate with the linear weight-sum
 // aggregator (PartitionedRollingAggregate::eval, operator/time_series/
@@ -661,31 +780,19 @@ extern "C" dbsp_status dbsp_sort_consolidate(dbsp_ctx *c, const uint64_t *k_in,
                                              dbsp_batch *out) {
     DevBatch raw;
     TRY(alloc_batch(c, n, raw));
-    if (n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(raw.k, k_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.v, v_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.w, w_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
+    TRY(copy_cols(c, raw, 0, k_in, v_in, w_in, n));
     DevBatch res;
     TRY(sort_consolidate_batch(c, raw, res));
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
 extern "C" dbsp_status dbsp_merge(dbsp_ctx *c, const dbsp_batch *a,
                                   const dbsp_batch *b, dbsp_batch *out) {
-    DevBatch ab{a->k, a->v, a->w, a->len};
-    DevBatch bb{b->k, b->v, b->w, b->len};
     DevBatch res;
-    TRY(merge_batches(c, ab, bb, res));
+    TRY(merge_batches(c, as_batch(a), as_batch(b), res));
     TRY(dbsp_ctx_sync(c));
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -699,10 +806,7 @@ extern "C" dbsp_status dbsp_join(dbsp_ctx *c, const dbsp_batch *delta,
                              trace->k, trace->v, trace->w, trace->len, proj,
                              param, &res.k, &res.v, &res.w, &res.n));
     }
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -741,7 +845,7 @@ extern "C" dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *c,
                                       out_trace->k, out_trace->v, out_trace->w,
                                       out_trace->len, &res.k, &res.v, &res.w,
                                       &res.n));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -757,7 +861,7 @@ extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
                                    out_trace->k, out_trace->v, out_trace->w,
                                    out_trace->len, &res.k, &res.v, &res.w,
                                    &res.n));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -773,7 +877,7 @@ extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
                                batch->len, have_prev, s0, e0, s1, e1, &res.k,
                                &res.v, &res.w, &res.n));
     }
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -797,14 +901,10 @@ extern "C" dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *c,
                                                  dbsp_batch *out) {
     DevBatch raw;
     TRY(alloc_batch(c, n > 0 ? n : 1, raw, true));
-    if (n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(raw.k, k_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.v, v_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.w, w_in, n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
+    TRY(copy_cols(c, raw, 0, k_in, v_in, w_in, n));
     raw.n = n;
     if (n == 0) {
-        out->k = nullptr; out->v = nullptr; out->w = nullptr; out->len = 0;
+        put_batch(out, DevBatch{});
         return DBSP_OK;
     }
     if (n <= 8192) {
@@ -813,15 +913,12 @@ extern "C" dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *c,
         TRY(alloc_batch(c, n, res));
         SortArgs sa{};
         sa.nb = 1;
-        sa.kin[0] = raw.k; sa.vin[0] = raw.v; sa.win[0] = raw.w; sa.n[0] = n;
-        sa.tk[0] = scratch.k; sa.tv[0] = scratch.v; sa.tw[0] = scratch.w;
-        sa.ok[0] = res.k; sa.ov[0] = res.v; sa.ow[0] = res.w;
-        sa.d_len = c->d_len;
+        sort_slot(sa, 0, raw, scratch, res);
+        sa.d_len = c->d_len + LEN_OP;
         TRY(dbspk::sort_cons_small_batch_f64(c->stream, sa));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        out->k = res.k; out->v = res.v; out->w = res.w; out->len = *c->h_len;
+        TRY(read_len(c, LEN_OP, 1));
+        res.n = c->h_len[LEN_OP];
+        put_batch(out, res);
         return DBSP_OK;
     }
     // big path: the radix sort moves the weight column bitwise; the
@@ -849,15 +946,12 @@ extern "C" dbsp_status dbsp_merge_f64(dbsp_ctx *c, const dbsp_batch *a,
         TRY(alloc_batch(c, a->len + b->len, res));
         MergeArgs ma{};
         ma.np = 1;
-        ma.ak[0] = a->k; ma.av[0] = a->v; ma.aw[0] = a->w; ma.na[0] = a->len;
-        ma.bk[0] = b->k; ma.bv[0] = b->v; ma.bw[0] = b->w; ma.nb[0] = b->len;
-        ma.ok[0] = res.k; ma.ov[0] = res.v; ma.ow[0] = res.w;
-        ma.d_len = c->d_len;
+        merge_pair(ma, 0, as_batch(a), as_batch(b), res);
+        ma.d_len = c->d_len + LEN_OP;
         TRY(dbspk::merge_small_batch_f64(c->stream, ma));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        out->k = res.k; out->v = res.v; out->w = res.w; out->len = *c->h_len;
+        TRY(read_len(c, LEN_OP, 1));
+        res.n = c->h_len[LEN_OP];
+        put_batch(out, res);
         return DBSP_OK;
     }
     uint64_t *rk, *rv;
@@ -887,7 +981,7 @@ extern "C" dbsp_status dbsp_agg_linear_upsert_f64(dbsp_ctx *c,
                                                   const dbsp_batch *out_trace,
                                                   dbsp_batch *out) {
     if (nd == 0) {
-        out->k = nullptr; out->v = nullptr; out->w = nullptr; out->len = 0;
+        put_batch(out, DevBatch{});
         return DBSP_OK;
     }
     double *acc;
@@ -912,22 +1006,12 @@ extern "C" dbsp_status dbsp_agg_linear_upsert_f64(dbsp_ctx *c,
                                       &retr.w, &retr.n));
     DevBatch res;
     TRY(alloc_batch(c, ins.n + retr.n, res));
-    res.n = 0;
-    if (ins.n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(res.k, ins.k, ins.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(res.v, ins.v, ins.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(res.w, ins.w, ins.n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (retr.n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(res.k + ins.n, retr.k, retr.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(res.v + ins.n, retr.v, retr.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(res.w + ins.n, retr.w, retr.n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    res.n = ins.n + retr.n;
+    TRY(copy_cols(c, res, 0, ins.k, ins.v, ins.w, ins.n));
+    TRY(copy_cols(c, res, ins.n, retr.k, retr.v, retr.w, retr.n));
     free_batch(c, ins);
     free_batch(c, retr);
     TRY(dbsp_ctx_sync(c));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -936,18 +1020,12 @@ extern "C" dbsp_status dbsp_distinct_inc(dbsp_ctx *c, const dbsp_batch *delta,
                                          int n_batches, dbsp_batch *out) {
     if (n_batches > MAX_TRACE_BATCHES) return DBSP_ERR_INVALID;
     TraceArgs t{};
-    for (int i = 0; i < n_batches; i++) {
-        if (trace_batches[i].len == 0) continue;
-        t.k[t.nb] = trace_batches[i].k;
-        t.v[t.nb] = trace_batches[i].v;
-        t.w[t.nb] = trace_batches[i].w;
-        t.n[t.nb] = trace_batches[i].len;
-        t.nb++;
-    }
+    for (int i = 0; i < n_batches; i++)
+        if (trace_batches[i].len != 0) trace_push(t, as_batch(&trace_batches[i]));
     DevBatch res;
     TRY(dbspk::distinct_inc_rows(c->stream, delta->k, delta->v, delta->w,
                                  delta->len, t, &res.k, &res.v, &res.w, &res.n));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -1100,14 +1178,13 @@ static dbsp_status shard_exchange(dbsp_ctx *c, DevBatch local, DevBatch &out,
         TRY(alloc_batch(c, c->world, r1, true));
         TRY(dbspk::frames_unpack_pair(c->stream, frecv, c->world, P, 1, r0.k,
                                       r0.v, r0.w, r1.k, r1.v, r1.w,
-                                      c->d_len + 16, c->d_len + 17));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 16, c->d_len + 16, 2 * 8,
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+                                      c->d_len + L_XCHG,
+                                      c->d_len + L_XCHG + 1));
+        TRY(read_len(c, L_XCHG, 2));
         HIP_CHECK_ST(dbspk::cache_free(fsend, c->stream));
         HIP_CHECK_ST(dbspk::cache_free(frecv, c->stream));
-        if (c->h_len[16] >= 0) {
-            r0.n = c->h_len[16];
+        if (c->h_len[L_XCHG] >= 0) {
+            r0.n = c->h_len[L_XCHG];
             free_batch(c, parts);
             TRY(sort_consolidate_batch(c, r0, out));
             return DBSP_OK;
@@ -1143,16 +1220,23 @@ struct Q3Train {
     bool pending = false;
     const dbsp_event *ev = nullptr;
     int64_t n = -1;
-    int sb = 0, evi = 0;
-    int next_sb = 18, next_evi = 0;
+    int sb = LEN_BASE0, evi = 0;  // length-slot base and event index in use
+    int next_sb = LEN_BASE1, next_evi = 0;
     DevBatch rawA, rawP, oA, oP, comb_chain;
     // in-train accumulator merge results (acc side + this tick's delta side);
-    // lengths land in d_len[sb+16, sb+17] with the train's 18-slot readback
+    // lengths land in the base's L_XCHG pair with the train's readback
     DevBatch res[2];
     Q3Plan plans[3];
     int np = 0;
     size_t arena_base = 0, arena_off = 0;
 };
+// release the batches a train owns (its deltas and accumulator merges)
+static void q3_train_drop(dbsp_ctx *c, Q3Train &T) {
+    free_batch(c, T.oA);
+    free_batch(c, T.oP);
+    free_batch(c, T.res[0]);
+    free_batch(c, T.res[1]);
+}
 
 struct dbsp_engine {
     dbsp_ctx *ctx = nullptr;
@@ -1298,10 +1382,7 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
     }
     if (e->train.pending) {
         (void)hipStreamSynchronize(c->stream);
-        free_batch(c, e->train.oA);
-        free_batch(c, e->train.oP);
-        free_batch(c, e->train.res[0]);
-        free_batch(c, e->train.res[1]);
+        q3_train_drop(c, e->train);
     }
     if (e->out_store.k) free_batch(c, e->out_store);
     if (e->d_events) (void)dbspk::cache_free(e->d_events, c->stream);
@@ -1392,19 +1473,13 @@ static dbsp_status sort_two_small(dbsp_ctx *c, DevBatch rawA, DevBatch rawB,
     TRY(alloc_batch(c, rawB.n > 0 ? rawB.n : 1, oB));
     SortArgs sa{};
     sa.nb = 2;
-    sa.kin[0] = rawA.k; sa.vin[0] = rawA.v; sa.win[0] = rawA.w; sa.n[0] = rawA.n;
-    sa.kin[1] = rawB.k; sa.vin[1] = rawB.v; sa.win[1] = rawB.w; sa.n[1] = rawB.n;
-    sa.tk[0] = sA.k; sa.tv[0] = sA.v; sa.tw[0] = sA.w;
-    sa.tk[1] = sB.k; sa.tv[1] = sB.v; sa.tw[1] = sB.w;
-    sa.ok[0] = oA.k; sa.ov[0] = oA.v; sa.ow[0] = oA.w;
-    sa.ok[1] = oB.k; sa.ov[1] = oB.v; sa.ow[1] = oB.w;
-    sa.d_len = c->d_len;
+    sort_slot(sa, 0, rawA, sA, oA);
+    sort_slot(sa, 1, rawB, sB, oB);
+    sa.d_len = c->d_len + LEN_OP;
     TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, 2 * sizeof(int64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    oA.n = c->h_len[0];
-    oB.n = c->h_len[1];
+    TRY(read_len(c, LEN_OP, 2));
+    oA.n = c->h_len[LEN_OP];
+    oB.n = c->h_len[LEN_OP + 1];
     free_batch(c, rawA);
     free_batch(c, rawB);
     free_batch(c, sA);
@@ -1412,6 +1487,14 @@ static dbsp_status sort_two_small(dbsp_ctx *c, DevBatch rawA, DevBatch rawB,
     dA = oA;
     dB = oB;
     return DBSP_OK;
+}
+
+// sort+consolidate two raw batches: fused when both fit one workgroup
+static dbsp_status sort_pair(dbsp_ctx *c, DevBatch r0, DevBatch r1,
+                             DevBatch &o0, DevBatch &o1) {
+    if (r0.n <= 8192 && r1.n <= 8192) return sort_two_small(c, r0, r1, o0, o1);
+    TRY(sort_consolidate_batch(c, r0, o0));
+    return sort_consolidate_batch(c, r1, o1);
 }
 
 // shard+exchange BOTH streams with one grouped counts phase and one grouped
@@ -1474,23 +1557,16 @@ static dbsp_status shard_exchange_pair(dbsp_ctx *c, DevBatch l0, DevBatch l1,
         TRY(alloc_batch(c, world * P1, r1, true));
         TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, r0.k,
                                       r0.v, r0.w, r1.k, r1.v, r1.w,
-                                      c->d_len + 16, c->d_len + 17));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 16, c->d_len + 16, 2 * 8,
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+                                      c->d_len + L_XCHG,
+                                      c->d_len + L_XCHG + 1));
+        TRY(read_len(c, L_XCHG, 2));
         HIP_CHECK_ST(dbspk::cache_free(fsend, c->stream));
         HIP_CHECK_ST(dbspk::cache_free(frecv, c->stream));
-        const int64_t tot0 = c->h_len[16], tot1 = c->h_len[17];
+        const int64_t tot0 = c->h_len[L_XCHG], tot1 = c->h_len[L_XCHG + 1];
         if (tot0 >= 0 && tot1 >= 0) {
             r0.n = tot0;
             r1.n = tot1;
-            if (r0.n <= 8192 && r1.n <= 8192) {
-                TRY(sort_two_small(c, r0, r1, o0, o1));
-            } else {
-                TRY(sort_consolidate_batch(c, r0, o0));
-                TRY(sort_consolidate_batch(c, r1, o1));
-            }
-            return DBSP_OK;
+            return sort_pair(c, r0, r1, o0, o1);
         }
         // overflow sentinel: fall through to the dynamic exchange on the
         // retained partitioned buffers (all ranks take this same branch)
@@ -1561,13 +1637,7 @@ static dbsp_status shard_exchange_pair(dbsp_ctx *c, DevBatch l0, DevBatch l1,
     HIP_CHECK_ST(dbspk::cache_free(d_all, c->stream));
     r0.n = tot0;
     r1.n = tot1;
-    if (r0.n <= 8192 && r1.n <= 8192) {
-        TRY(sort_two_small(c, r0, r1, o0, o1));
-    } else {
-        TRY(sort_consolidate_batch(c, r0, o0));
-        TRY(sort_consolidate_batch(c, r1, o1));
-    }
-    return DBSP_OK;
+    return sort_pair(c, r0, r1, o0, o1);
 }
 
 // flatmap events slice into up to two raw streams, then sort+consolidate
@@ -1586,6 +1656,50 @@ static bool staged_cols(dbsp_engine *e, const dbsp_event *d_ev,
            e->ev_cols[3] + off, e->ev_cols[4] + off, e->ev_cols[5] + off,
            (const int64_t *)(e->ev_cols[6] + off)};
     return true;
+}
+
+// chained flatmap: allocate both raw streams (transient) and launch the
+// flatmap with its two row counters left on device at d_len[sb + L_RAW..]
+static dbsp_status flatmap_chain(dbsp_engine *e, const dbsp_event *d_ev,
+                                 int64_t n, DevBatch &rawA, DevBatch &rawB,
+                                 int sb = LEN_BASE0) {
+    dbsp_ctx *c = e->ctx;
+    const int64_t cap = n > 0 ? n : 1;
+    TRY(alloc_batch(c, cap, rawA, true));
+    TRY(alloc_batch(c, cap, rawB, true));
+    dbspk::EventCols cols{};
+    const bool hc = staged_cols(e, d_ev, cols);
+    return dbspk::flatmap_events_chain(c->stream, d_ev, hc ? &cols : nullptr,
+                                       n, e->query, rawA.k, rawA.v, rawA.w,
+                                       rawB.k, rawB.v, rawB.w,
+                                       (uint64_t *)(c->d_len + sb + L_RAW));
+}
+
+// speculative fused sort of two chained streams: input lengths read from the
+// device slots nA/nB, output lengths (or -1) left at d_len[sb + L_DELTA..];
+// oA/oB stay pending (n = -1) until the caller's readback
+static dbsp_status sort_pair_chain(dbsp_ctx *c, const DevBatch &inA,
+                                   const DevBatch &inB, int64_t capA,
+                                   int64_t capB, const int64_t *nA,
+                                   const int64_t *nB, int sb, int64_t n_events,
+                                   DevBatch &oA, DevBatch &oB) {
+    DevBatch sA, sB;
+    TRY(alloc_batch(c, capA, sA, true));
+    TRY(alloc_batch(c, capB, sB, true));
+    TRY(alloc_batch(c, capA, oA));
+    TRY(alloc_batch(c, capB, oB));
+    SortArgs sa{};
+    sa.nb = 2;
+    sort_slot(sa, 0, inA, sA, oA, nA);
+    sort_slot(sa, 1, inB, sB, oB, nB);
+    sa.d_len = c->d_len + sb + L_DELTA;
+    {
+        ScopedTimer t(c, 0, (double)n_events * 48.0);
+        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+    }
+    oA.n = -1;
+    oB.n = -1;
+    return DBSP_OK;
 }
 
 static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
@@ -1624,12 +1738,10 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
     } else {
         DevBatch rawA, rawB, oA, oB;
         TRY(build_deltas_chain(e, d_ev, n, rawA, rawB, oA, oB));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, 18 * sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-        if (c->h_len[10] < 0 || c->h_len[11] < 0) {
-            rawA.n = c->h_len[8];
-            rawB.n = c->h_len[9];
+        TRY(read_len(c, LEN_BASE0, LEN_TICK));
+        if (c->h_len[L_DELTA] < 0 || c->h_len[L_DELTA + 1] < 0) {
+            rawA.n = c->h_len[L_RAW];
+            rawB.n = c->h_len[L_RAW + 1];
             free_batch(c, oA);
             free_batch(c, oB);
             TRY(sort_consolidate_batch(c, rawA, d0));
@@ -1639,8 +1751,8 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
                 free_batch(c, rawB);
             }
         } else {
-            oA.n = c->h_len[10];
-            oB.n = c->h_len[11];
+            oA.n = c->h_len[L_DELTA];
+            oB.n = c->h_len[L_DELTA + 1];
             d0 = oA;
             if (want_two) d1 = oB;
             else free_batch(c, oB);
@@ -1668,53 +1780,25 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
     return DBSP_OK;
 }
 
-// Chained variant (single-rank): flatmap counters stay on device
-// (d_len[8..9]), the fused sort launches behind them reading its lengths
-// from the device (outputs at d_len[10..11], -1 on overflow), and no sync
-// happens here — the caller reads everything at its one tick sync and
-// re-sorts through the sized paths if the speculation lost.
+// Chained variant (single-rank): flatmap counters stay on device (L_RAW),
+// the fused sort launches behind them reading its lengths from the device
+// (outputs at L_DELTA, -1 on overflow), and no sync happens here — the
+// caller reads everything at its one tick sync and re-sorts through the
+// sized paths if the speculation lost.
 static dbsp_status build_deltas_chain(dbsp_engine *e, const dbsp_event *d_ev,
                                       int64_t n, DevBatch &rawA, DevBatch &rawB,
                                       DevBatch &oA, DevBatch &oB, int sb) {
     dbsp_ctx *c = e->ctx;
-    int64_t cap = n > 0 ? n : 1;
-    TRY(alloc_batch(c, cap, rawA, true));
-    TRY(alloc_batch(c, cap, rawB, true));
-    dbspk::EventCols cols{};
-    const bool hc = staged_cols(e, d_ev, cols);
-    TRY(dbspk::flatmap_events_chain(c->stream, d_ev, hc ? &cols : nullptr, n,
-                                    e->query, rawA.k, rawA.v, rawA.w, rawB.k,
-                                    rawB.v, rawB.w,
-                                    (uint64_t *)(c->d_len + sb + 8)));
-    DevBatch sA, sB;
-    TRY(alloc_batch(c, cap, sA, true));
-    TRY(alloc_batch(c, cap, sB, true));
-    TRY(alloc_batch(c, cap, oA));
-    TRY(alloc_batch(c, cap, oB));
-    SortArgs sa{};
-    sa.nb = 2;
-    sa.kin[0] = rawA.k; sa.vin[0] = rawA.v; sa.win[0] = rawA.w;
-    sa.kin[1] = rawB.k; sa.vin[1] = rawB.v; sa.win[1] = rawB.w;
-    sa.n_dev[0] = c->d_len + sb + 8;
-    sa.n_dev[1] = c->d_len + sb + 9;
-    sa.tk[0] = sA.k; sa.tv[0] = sA.v; sa.tw[0] = sA.w;
-    sa.tk[1] = sB.k; sa.tv[1] = sB.v; sa.tw[1] = sB.w;
-    sa.ok[0] = oA.k; sa.ov[0] = oA.v; sa.ow[0] = oA.w;
-    sa.ok[1] = oB.k; sa.ov[1] = oB.v; sa.ow[1] = oB.w;
-    sa.d_len = c->d_len + sb + 10;
-    {
-        ScopedTimer t(c, 0, (double)n * 48.0);
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    }
-    oA.n = -1;  // pending: d_len[sb+10], d_len[sb+11]
-    oB.n = -1;
-    return DBSP_OK;
+    const int64_t cap = n > 0 ? n : 1;
+    TRY(flatmap_chain(e, d_ev, n, rawA, rawB, sb));
+    return sort_pair_chain(c, rawA, rawB, cap, cap, c->d_len + sb + L_RAW,
+                           c->d_len + sb + L_RAW + 1, sb, n, oA, oB);
 }
 
 // Sharded chained front (q3-class pair streams): flatmap -> hash-scatter
 // straight into fixed frames (device counters, no pre-sort — shard.rs
 // consolidates POST-exchange) -> one equal-count ncclAllToAll -> unpack
-// (receive totals at d_len[16..17]) -> speculative fused sorts reading those
+// (receive totals at the L_XCHG pair) -> speculative fused sorts reading those
 // totals.  The round-1 sharded tick ran the explicit path with ~7 host
 // syncs (partition offsets, counts allgather, totals, sorts...); this one
 // syncs ONCE at the caller like the unsharded chain.  Overflow anywhere
@@ -1728,14 +1812,8 @@ static dbsp_status build_deltas_chain_sharded(
     dbsp_ctx *c = e->ctx;
     const int world = c->world;
     const int64_t cap = n > 0 ? n : 1;
-    TRY(alloc_batch(c, cap, rawA, true));
-    TRY(alloc_batch(c, cap, rawB, true));
-    dbspk::EventCols cols{};
-    const bool hc = staged_cols(e, d_ev, cols);
-    TRY(dbspk::flatmap_events_chain(c->stream, d_ev, hc ? &cols : nullptr, n,
-                                    e->query, rawA.k, rawA.v, rawA.w, rawB.k,
-                                    rawB.v, rawB.w,
-                                    (uint64_t *)(c->d_len + 8)));
+    int64_t *const raw_len = c->d_len + L_RAW, *const tot = c->d_len + L_XCHG;
+    TRY(flatmap_chain(e, d_ev, n, rawA, rawB));
     // frame capacities from the deterministic event mix (config.rs:128-143)
     const int64_t P0 = 2 * (n / 50 + 64) / world + 512;
     const int64_t P1 = 2 * (3 * n / 50 + 64) / world + 512;
@@ -1745,9 +1823,9 @@ static dbsp_status build_deltas_chain_sharded(
                                      c->stream));
     HIP_CHECK_ST(dbspk::cache_malloc((void **)&frecv, (size_t)world * S * 8,
                                      c->stream));
-    TRY(dbspk::shard_frames_chain(c->stream, rawA.k, rawA.v, rawA.w,
-                                  c->d_len + 8, rawB.k, rawB.v, rawB.w,
-                                  c->d_len + 9, world, P0, P1, cap, fsend));
+    TRY(dbspk::shard_frames_chain(c->stream, rawA.k, rawA.v, rawA.w, raw_len,
+                                  rawB.k, rawB.v, rawB.w, raw_len + 1, world,
+                                  P0, P1, cap, fsend));
     if (ncclAllToAll(fsend, frecv, (size_t)S, ncclUint64, c->comm,
                      c->stream) != ncclSuccess)
         return DBSP_ERR_INTERNAL;
@@ -1756,52 +1834,18 @@ static dbsp_status build_deltas_chain_sharded(
     TRY(alloc_batch(c, capB, recvB, true));
     TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, recvA.k,
                                   recvA.v, recvA.w, recvB.k, recvB.v, recvB.w,
-                                  c->d_len + 16, c->d_len + 17));
+                                  tot, tot + 1));
     HIP_CHECK_ST(dbspk::cache_free(fsend, c->stream));
     HIP_CHECK_ST(dbspk::cache_free(frecv, c->stream));
-    DevBatch sA, sB;
-    TRY(alloc_batch(c, capA, sA, true));
-    TRY(alloc_batch(c, capB, sB, true));
-    TRY(alloc_batch(c, capA, oA));
-    TRY(alloc_batch(c, capB, oB));
-    SortArgs sa{};
-    sa.nb = 2;
-    sa.kin[0] = recvA.k; sa.vin[0] = recvA.v; sa.win[0] = recvA.w;
-    sa.kin[1] = recvB.k; sa.vin[1] = recvB.v; sa.win[1] = recvB.w;
-    sa.n_dev[0] = c->d_len + 16;
-    sa.n_dev[1] = c->d_len + 17;
-    sa.tk[0] = sA.k; sa.tv[0] = sA.v; sa.tw[0] = sA.w;
-    sa.tk[1] = sB.k; sa.tv[1] = sB.v; sa.tw[1] = sB.w;
-    sa.ok[0] = oA.k; sa.ov[0] = oA.v; sa.ow[0] = oA.w;
-    sa.ok[1] = oB.k; sa.ov[1] = oB.v; sa.ow[1] = oB.w;
-    sa.d_len = c->d_len + 10;
-    {
-        ScopedTimer t(c, 0, (double)n * 48.0);
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    }
-    oA.n = -1;  // pending: d_len[10], d_len[11]
-    oB.n = -1;
-    return DBSP_OK;
+    return sort_pair_chain(c, recvA, recvB, capA, capB, tot, tot + 1,
+                           LEN_BASE0, n, oA, oB);
 }
 
 // join delta against a whole spine in one count/emit pair (join is linear in
 // the trace; spine read path = the reference's CursorList)
-static dbsp_status join_vs_spine(dbsp_ctx *c, const DevBatch &delta,
-                                 Spine &spine, int proj, uint64_t param,
+static dbsp_status join_vs_trace(dbsp_ctx *c, const DevBatch &delta,
+                                 const TraceArgs &t, int proj, uint64_t param,
                                  std::vector<DevBatch> &outs) {
-    if (delta.n == 0 || spine.batches.empty()) return DBSP_OK;
-    if ((int)spine.batches.size() > MAX_TRACE_BATCHES)
-        TRY(spine.consolidate_all(c));
-    TraceArgs t{};
-    for (auto &b : spine.batches) {
-        if (b.n == 0) continue;
-        t.k[t.nb] = b.k;
-        t.v[t.nb] = b.v;
-        t.w[t.nb] = b.w;
-        t.n[t.nb] = b.n;
-        t.nb++;
-    }
-    if (t.nb == 0) return DBSP_OK;
     DevBatch o;
     ScopedTimer timer(c, 2, (double)delta.n * 24.0);
     TRY(dbspk::join_spine_rows(c->stream, delta.k, delta.v, delta.w, delta.n, t,
@@ -1810,34 +1854,43 @@ static dbsp_status join_vs_spine(dbsp_ctx *c, const DevBatch &delta,
     else free_batch(c, o);
     return DBSP_OK;
 }
+static dbsp_status join_vs_spine(dbsp_ctx *c, const DevBatch &delta,
+                                 Spine &spine, int proj, uint64_t param,
+                                 std::vector<DevBatch> &outs) {
+    if (delta.n == 0 || spine.batches.empty()) return DBSP_OK;
+    TRY(spine.cap_batches(c));
+    const TraceArgs t = trace_args_of(spine);
+    if (t.nb == 0) return DBSP_OK;
+    return join_vs_trace(c, delta, t, proj, param, outs);
+}
+// delta ⋈ delta: the other side's tick batch stands in as a one-batch trace
+static dbsp_status join_vs_batch(dbsp_ctx *c, const DevBatch &delta,
+                                 const DevBatch &other, int proj,
+                                 uint64_t param, std::vector<DevBatch> &outs) {
+    if (delta.n <= 0 || other.n <= 0) return DBSP_OK;
+    return join_vs_trace(c, delta, trace_args_one(other), proj, param, outs);
+}
+
+// gather raw result batches (consumed) into one raw transient batch; a single
+// batch is handed through as it is
+static dbsp_status gather_raw(dbsp_ctx *c, std::vector<DevBatch> &outs,
+                              DevBatch &cat) {
+    if (outs.size() == 1) {
+        cat = outs[0];
+    } else {
+        TRY(concat_batches(c, outs, cat, true));
+        for (auto &b : outs) free_batch(c, b);
+    }
+    outs.clear();
+    return DBSP_OK;
+}
 
 // consolidate a list of raw result batches into one batch
 static dbsp_status finalize_raw(dbsp_ctx *c, std::vector<DevBatch> &outs,
                                 DevBatch &out) {
-    if (outs.size() == 1) {
-        DevBatch only = outs[0];
-        outs.clear();
-        return sort_consolidate_batch(c, only, out);
-    }
     DevBatch cat;
-    {
-        int64_t total = 0;
-        for (auto &b : outs) total += b.n;
-        TRY(alloc_batch(c, total, cat, true));
-        int64_t off = 0;
-        for (auto &b : outs) {
-            if (b.n == 0) continue;
-            HIP_CHECK_ST(hipMemcpyAsync(cat.k + off, b.k, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIP_CHECK_ST(hipMemcpyAsync(cat.v + off, b.v, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIP_CHECK_ST(hipMemcpyAsync(cat.w + off, b.w, b.n * 8, hipMemcpyDeviceToDevice, c->stream));
-            off += b.n;
-        }
-        cat.n = total;
-    }
-    for (auto &b : outs) free_batch(c, b);
-    outs.clear();
-    TRY(sort_consolidate_batch(c, cat, out));
-    return DBSP_OK;
+    TRY(gather_raw(c, outs, cat));
+    return sort_consolidate_batch(c, cat, out);
 }
 
 // last key of a consolidated batch (watermark: fast_forward_keys,
@@ -1853,6 +1906,36 @@ static dbsp_status last_key(dbsp_ctx *c, const DevBatch &b, uint64_t *out,
     return DBSP_OK;
 }
 
+// One spine's window launch plan: the spine (capped to MAX_TRACE_BATCHES) as
+// a kernel argument, and the region table the ranges kernel fills — three
+// regions per spine batch plus the tick batch, 5 int64 each — carved from
+// the arena (null when it is exhausted).
+struct WindowPlan {
+    TraceArgs ta;
+    int nreg = 0;
+    int64_t *table = nullptr;
+};
+static dbsp_status window_plan(dbsp_ctx *c, Spine &sp, WindowPlan &wp) {
+    TRY(sp.cap_batches(c));
+    wp.ta = trace_args_of(sp);
+    wp.nreg = 3 * wp.ta.nb + 1;
+    wp.table = (int64_t *)arena_alloc(c, (size_t)wp.nreg * 5 * 8 + 8);
+    return DBSP_OK;
+}
+// emit a planned window's `total` rows (ranges already in the table) into a
+// transient batch appended to raw
+static dbsp_status window_emit(dbsp_ctx *c, const WindowPlan &wp,
+                               int64_t total, const DevBatch &batch,
+                               std::vector<DevBatch> &raw) {
+    if (total <= 0) return DBSP_OK;
+    DevBatch o;
+    TRY(alloc_batch(c, total, o, true));
+    TRY(dbspk::window_emit_multi(c->stream, wp.ta, batch.k, batch.v, batch.w,
+                                 wp.table, wp.nreg, total, o.k, o.v, o.w));
+    raw.push_back(o);
+    return DBSP_OK;
+}
+
 // window over a spine: one ranges launch covers every spine batch's three
 // regions plus the tick-batch region, one emit launch copies them all
 static dbsp_status window_vs_spine(dbsp_ctx *c, Spine &trace,
@@ -1860,42 +1943,31 @@ static dbsp_status window_vs_spine(dbsp_ctx *c, Spine &trace,
                                    uint64_t s0, uint64_t e0, uint64_t s1,
                                    uint64_t e1, std::vector<DevBatch> &outs) {
     ScopedTimer t(c, 4, 0.0);
-    if ((int)trace.batches.size() > MAX_TRACE_BATCHES)
-        TRY(trace.consolidate_all(c));
-    TraceArgs ta{};
-    for (auto &b : trace.batches) {
-        if (b.n == 0) continue;
-        ta.k[ta.nb] = b.k;
-        ta.v[ta.nb] = b.v;
-        ta.w[ta.nb] = b.w;
-        ta.n[ta.nb] = b.n;
-        ta.nb++;
-    }
-    int nreg = 3 * ta.nb + 1;
-    int64_t *table = (int64_t *)arena_alloc(c, (size_t)nreg * 5 * 8 + 8);
+    WindowPlan wp;
+    TRY(window_plan(c, trace, wp));
     DevBatch tmp_table;
-    if (!table) {
+    if (!wp.table) {
         // fallback scratch: the ranges kernel writes 5 int64 per region + 8
         // bytes through .k, and alloc_batch's k column is n*8+8 bytes
-        TRY(alloc_batch(c, nreg * 5, tmp_table));
-        table = (int64_t *)tmp_table.k;
+        TRY(alloc_batch(c, wp.nreg * 5, tmp_table));
+        wp.table = (int64_t *)tmp_table.k;
     }
-    TRY(dbspk::window_ranges_multi(c->stream, ta, batch.k, batch.n,
-                                   have_prev ? 1 : 0, s0, e0, s1, e1, table,
-                                   c->d_len + 7));
-    HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 7, c->d_len + 7, sizeof(int64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    int64_t total = c->h_len[7];
-    if (total > 0) {
-        DevBatch o;
-        TRY(alloc_batch(c, total, o, true));
-        TRY(dbspk::window_emit_multi(c->stream, ta, batch.k, batch.v, batch.w,
-                                     table, nreg, total, o.k, o.v, o.w));
-        outs.push_back(o);
-    }
+    TRY(dbspk::window_ranges_multi(c->stream, wp.ta, batch.k, batch.n,
+                                   have_prev ? 1 : 0, s0, e0, s1, e1, wp.table,
+                                   c->d_len + L_WIN));
+    TRY(read_len(c, L_WIN, 1));
+    TRY(window_emit(c, wp, c->h_len[L_WIN], batch, outs));
     if (tmp_table.k) free_batch(c, tmp_table);
     return DBSP_OK;
+}
+// the same with the bounds the device watermark published (the no-arena
+// fallback of the chained ticks; e->h_bounds was just read back)
+static dbsp_status window_vs_spine_bounds(dbsp_ctx *c, Spine &trace,
+                                          const DevBatch &batch,
+                                          const unsigned long long *hb,
+                                          std::vector<DevBatch> &outs) {
+    return window_vs_spine(c, trace, batch, hb[4] != 0, hb[0], hb[1], hb[2],
+                           hb[3], outs);
 }
 
 // map + sort/consolidate (copies; input retained)
@@ -1917,12 +1989,7 @@ static dbsp_status map_sorted(dbsp_ctx *c, const DevBatch &in, int mode,
 static dbsp_status copy_batch(dbsp_ctx *c, const DevBatch &in, DevBatch &out) {
     TRY(alloc_batch(c, in.n > 0 ? in.n : 1, out));
     out.n = in.n;
-    if (in.n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(out.k, in.k, in.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(out.v, in.v, in.n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(out.w, in.w, in.n * 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    return DBSP_OK;
+    return copy_cols(c, out, 0, in.k, in.v, in.w, in.n);
 }
 
 // linear aggregate + upsert over spines (aggregate/mod.rs:479-547 +
@@ -1957,14 +2024,8 @@ static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
     // contract (upsert.rs:180-195) — in one count/emit pair over the whole
     // spine instead of a scan pipeline per batch.
     if (!out_trace.batches.empty()) {
-        if ((int)out_trace.batches.size() > MAX_TRACE_BATCHES)
-            TRY(out_trace.consolidate_all(c));
-        TraceArgs t{};
-        for (auto &b : out_trace.batches) {
-            if (b.n == 0) continue;
-            t.k[t.nb] = b.k; t.v[t.nb] = b.v; t.w[t.nb] = b.w;
-            t.n[t.nb] = b.n; t.nb++;
-        }
+        TRY(out_trace.cap_batches(c));
+        const TraceArgs t = trace_args_of(out_trace);
         if (t.nb > 0) {
             // synthetic delta columns: v = 0, w = -1
             uint64_t *dv = (uint64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
@@ -1993,12 +2054,10 @@ static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
                 jca.t[0] = t;
                 jca.cnts[0] = cnts;
                 jca.offsets[0] = offsets;
-                jca.d_total = c->d_len;
+                jca.d_total = c->d_len + LEN_OP;
                 TRY(dbspk::join_count_scan_batch(c->stream, jca));
-                HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, 8,
-                                            hipMemcpyDeviceToHost, c->stream));
-                HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-                int64_t total = c->h_len[0];
+                TRY(read_len(c, LEN_OP, 1));
+                int64_t total = c->h_len[LEN_OP];
                 if (total > 0) {
                     DevBatch o;
                     TRY(alloc_batch(c, total, o, true));
@@ -2059,14 +2118,8 @@ static dbsp_status agg_linear_spine_f64(dbsp_ctx *c, const DevBatch &delta,
     // retractions: probe the (i64-weighted) output trace with (key, _, -1)
     // rows under proj (k, v2) — the upsert contract (upsert.rs:180-195)
     if (!out_trace.batches.empty()) {
-        if ((int)out_trace.batches.size() > MAX_TRACE_BATCHES)
-            TRY(out_trace.consolidate_all(c));
-        TraceArgs t{};
-        for (auto &b : out_trace.batches) {
-            if (b.n == 0) continue;
-            t.k[t.nb] = b.k; t.v[t.nb] = b.v; t.w[t.nb] = b.w;
-            t.n[t.nb] = b.n; t.nb++;
-        }
+        TRY(out_trace.cap_batches(c));
+        const TraceArgs t = trace_args_of(out_trace);
         if (t.nb > 0) {
             uint64_t *dv = (uint64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
             int64_t *dw = (int64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
@@ -2146,12 +2199,7 @@ static dbsp_status spine_rounds(dbsp_ctx *c, Spine *const *sps, int ns,
                 DevBatch res;
                 TRY(alloc_batch(c, tot, res));
                 MergeArgs &mx = tot <= 4096 ? ma : mm;
-                int p = mx.np++;
-                mx.ak[p] = below.k; mx.av[p] = below.v; mx.aw[p] = below.w;
-                mx.na[p] = below.n;
-                mx.bk[p] = top.k; mx.bv[p] = top.v; mx.bw[p] = top.w;
-                mx.nb[p] = top.n;
-                mx.ok[p] = res.k; mx.ov[p] = res.v; mx.ow[p] = res.w;
+                merge_pair(mx, mx.np++, below, top, res);
                 midofj[nbatched] = tot > 4096;
                 results[nbatched] = res;
                 owners[nbatched] = &sp;
@@ -2159,32 +2207,25 @@ static dbsp_status spine_rounds(dbsp_ctx *c, Spine *const *sps, int ns,
             } else {
                 DevBatch res;
                 TRY(merge_batches(c, below, top, res));
-                free_batch(c, top);
-                free_batch(c, below);
-                sp.batches.pop_back();
-                sp.batches.pop_back();
-                if (res.n > 0) sp.batches.push_back(res);
-                else free_batch(c, res);
+                sp.replace_top2(c, res);
             }
         }
         if (nbatched > 0) {
-            // dedicated insert slots (36-39): the hook below may enqueue the
-            // next tick's full train, whose 18-slot readback would otherwise
-            // overwrite h_len[0..3] before this round's merge lengths are
-            // consumed after the event wait.  Slots: small pairs first,
-            // then mid pairs.
+            // dedicated insert slots (LEN_ROUND): the hook below may enqueue
+            // the next tick's full train, whose LEN_TICK-slot readback would
+            // otherwise overwrite the op slots before this round's merge
+            // lengths are consumed after the event wait.  Slots: small pairs
+            // first, then mid pairs.
             {
                 int ps = 0, pm = ma.np;
                 for (int j = 0; j < nbatched; j++)
                     slotofj[j] = midofj[j] ? pm++ : ps++;
             }
-            ma.d_len = c->d_len + 36;
-            mm.d_len = c->d_len + 36 + ma.np;
+            ma.d_len = c->d_len + LEN_ROUND;
+            mm.d_len = c->d_len + LEN_ROUND + ma.np;
             if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma));
             if (mm.np > 0) TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid));
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 36, c->d_len + 36,
-                                        (ma.np + mm.np) * sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
+            TRY(read_len(c, LEN_ROUND, ma.np + mm.np, /*sync=*/false));
             if (defer && hook && !*hook_fired) {
                 (void)hipEventRecord(c->ev_insert, c->stream);
                 TRY((*hook)());
@@ -2208,17 +2249,8 @@ static dbsp_status spine_rounds(dbsp_ctx *c, Spine *const *sps, int ns,
                 HIP_CHECK_ST(hipStreamSynchronize(c->stream));
             }
             for (int j = 0; j < nbatched; j++) {
-                Spine &sp = *owners[j];
-                results[j].n = c->h_len[36 + slotofj[j]];
-                if (results[j].n < 0) return DBSP_ERR_INTERNAL;
-                DevBatch top = sp.batches.back();
-                sp.batches.pop_back();
-                DevBatch below = sp.batches.back();
-                sp.batches.pop_back();
-                free_batch(c, top);
-                free_batch(c, below);
-                if (results[j].n > 0) sp.batches.push_back(results[j]);
-                else free_batch(c, results[j]);
+                TRY(checked_len(c, LEN_ROUND + slotofj[j], results[j].n));
+                owners[j]->replace_top2(c, results[j]);
             }
         }
     }
@@ -2226,7 +2258,7 @@ static dbsp_status spine_rounds(dbsp_ctx *c, Spine *const *sps, int ns,
 }
 
 // consume a deferred insert round: pop the merged pair, publish the result
-// (length from h_len[36..39], valid once ev_insert has fired), then run any
+// (length from the LEN_ROUND host slots, valid once ev_insert has fired), then run any
 // cascade rounds synchronously — the stream is near-empty at every call
 // site, so these cost only the merge kernels themselves
 static dbsp_status resolve_pending_insert(dbsp_ctx *c) {
@@ -2238,17 +2270,9 @@ static dbsp_status resolve_pending_insert(dbsp_ctx *c) {
     c->pend_n = 0;
     for (int j = 0; j < np; j++) {
         Spine &sp = *(Spine *)c->pend_spine[j];
-        DevBatch res{c->pend_k[j], c->pend_v[j], c->pend_w[j],
-                     c->h_len[36 + c->pend_slot[j]]};
-        if (res.n < 0) return DBSP_ERR_INTERNAL;
-        DevBatch top = sp.batches.back();
-        sp.batches.pop_back();
-        DevBatch below = sp.batches.back();
-        sp.batches.pop_back();
-        free_batch(c, top);
-        free_batch(c, below);
-        if (res.n > 0) sp.batches.push_back(res);
-        else free_batch(c, res);
+        DevBatch res{c->pend_k[j], c->pend_v[j], c->pend_w[j], 0};
+        TRY(checked_len(c, LEN_ROUND + c->pend_slot[j], res.n));
+        sp.replace_top2(c, res);
         bool dup = false;
         for (int i = 0; i < no; i++) dup |= owners[i] == &sp;
         if (!dup) owners[no++] = &sp;
@@ -2305,19 +2329,6 @@ static void engine_free_output(dbsp_engine *e) {
     e->output_is_store = false;
 }
 
-static TraceArgs trace_args_of(Spine &sp) {
-    TraceArgs t{};
-    for (auto &b : sp.batches) {
-        if (b.n == 0) continue;
-        t.k[t.nb] = b.k;
-        t.v[t.nb] = b.v;
-        t.w[t.nb] = b.w;
-        t.n[t.nb] = b.n;
-        t.nb++;
-    }
-    return t;
-}
-
 // ---- incremental partitioned rolling aggregate (rolling_aggregate.rs
 // :487-604) ----
 // Per tick, over a consolidated delta D of nd rows:
@@ -2353,10 +2364,8 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
         TRY(copy_batch(c, delta, cpy));
         TRY(in_sp.insert(c, cpy));
     }
-    if ((int)in_sp.batches.size() > MAX_TRACE_BATCHES)
-        TRY(in_sp.consolidate_all(c));
-    if ((int)out_sp.batches.size() > MAX_TRACE_BATCHES)
-        TRY(out_sp.consolidate_all(c));
+    TRY(in_sp.cap_batches(c));
+    TRY(out_sp.cap_batches(c));
     // gather + consolidate the slice of the input integral
     DevBatch raw, slice;
     TRY(dbspk::range_gather(c->stream, rb, rb + n, rb + 2 * n, n_gather,
@@ -2400,14 +2409,8 @@ static dbsp_status truncate_batch(dbsp_ctx *c, const DevBatch &in, int mode,
                                   uint64_t bound, DevBatch &out) {
     out = DevBatch{};
     if (in.n == 0) return DBSP_OK;
-    TraceArgs t{};
-    t.nb = 1;
-    t.k[0] = in.k;
-    t.v[0] = in.v;
-    t.w[0] = in.w;
-    t.n[0] = in.n;
-    return dbspk::truncate_spine(c->stream, t, mode, bound, &out.k, &out.v,
-                                 &out.w, &out.n);
+    return dbspk::truncate_spine(c->stream, trace_args_one(in), mode, bound,
+                                 &out.k, &out.v, &out.w, &out.n);
 }
 
 dbsp_status RollingOp::step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
@@ -2433,18 +2436,11 @@ dbsp_status RollingOp::step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
 
 dbsp_status RollingOp::sweep(dbsp_ctx *c, int mode) {
     Spine &sp = mode == 0 ? in_sp : out_sp;
-    if ((int)sp.batches.size() > MAX_TRACE_BATCHES)
-        TRY(sp.consolidate_all(c));
+    TRY(sp.cap_batches(c));
     const int nb = (int)sp.batches.size();
     if (nb > 0) {
-        TraceArgs t{};
-        t.nb = nb;
-        for (int b = 0; b < nb; b++) {
-            t.k[b] = sp.batches[b].k;
-            t.v[b] = sp.batches[b].v;
-            t.w[b] = sp.batches[b].w;
-            t.n[b] = sp.batches[b].n;
-        }
+        TraceArgs t{};  // every batch, empty ones too: outputs are per batch
+        for (auto &b : sp.batches) trace_push(t, b);
         uint64_t *ok[MAX_TRACE_BATCHES], *ov[MAX_TRACE_BATCHES];
         int64_t *ow[MAX_TRACE_BATCHES], on[MAX_TRACE_BATCHES];
         TRY(dbspk::truncate_spine(c->stream, t, mode, lower_bound(), ok, ov,
@@ -2489,10 +2485,7 @@ extern "C" dbsp_status dbsp_truncate_below(dbsp_ctx *c, const dbsp_batch *in,
     DevBatch ib{in->k, in->v, in->w, in->len}, res;
     TRY(truncate_batch(c, ib, mode, bound, res));
     HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -2528,9 +2521,7 @@ extern "C" dbsp_status dbsp_rolling_step_wm(dbsp_rolling *r, const uint64_t *k,
     DevBatch raw, delta, res;
     if (n > 0) {
         TRY(alloc_batch(c, n, raw));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.k, k, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.v, v, n * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(raw.w, w, n * 8, hipMemcpyDeviceToDevice, c->stream));
+        TRY(copy_cols(c, raw, 0, k, v, w, n));
         TRY(sort_consolidate_batch(c, raw, delta));
     }
     const dbsp_status st = r->op.step_wm(c, delta, watermark, res);
@@ -2538,10 +2529,7 @@ extern "C" dbsp_status dbsp_rolling_step_wm(dbsp_rolling *r, const uint64_t *k,
     HIP_CHECK_ST(hipStreamSynchronize(c->stream));
     if (st != DBSP_OK) return st;
     if (res.n == 0) free_batch(c, res);
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = res.n;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -2665,7 +2653,6 @@ extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
 // from the second readback and replayed explicitly; a lost sort speculation
 // re-sorts through the sized paths.  Sharded ranks keep the explicit path
 // (the exchange needs host lengths).
-// ---- q3 tick (queries/q3.rs:35-63) ----
 //
 // Pipelined TRAINS (round 2): for run_staged loops the ENTIRE next tick's
 // launch train (flatmap -> speculative fused sorts -> 3-plan join count ->
@@ -2678,8 +2665,8 @@ extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
 // work (the round-1 trace showed 53 us gaps before the join probes and
 // 63 us before the insert merges — fat-kernarg hipLaunchKernel time, not
 // sync latency) overlaps the previous train's GPU execution.  Trains
-// ping-pong the 18-slot length bases (0 / 18), the tick events and the
-// arena halves; the spine-insert rounds use dedicated slots 36-39.
+// ping-pong the length-slot bases (LEN_BASE0 / LEN_BASE1), the tick events
+// and the arena halves; the spine-insert rounds use the LEN_ROUND slots.
 // Per-tick stepping (no next_ev), sharded ranks, oversized ticks and lost
 // speculations all run the unpipelined body below, which is the round-1
 // path unchanged.
@@ -2688,7 +2675,7 @@ static constexpr int64_t Q3_EMIT_CAP = 32768;
 
 // Build the three bilinear join plans against the CURRENT spines (callers
 // guarantee the spine state is the one tick t's probes must read) and
-// enqueue count(+scan).  spec: delta lengths still on device at d_len[sb+10/11].
+// enqueue count(+scan).  spec: delta lengths still on device (L_DELTA of sb).
 static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
                                  bool spec, int sb, int64_t n_cap,
                                  Q3Plan plans[3], int &np, int &jca_np,
@@ -2704,10 +2691,8 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
         plans[np++] = {1, trace_args_of(e->a_int), DBSP_PROJ_HI_V1_LO_V2,
                        nullptr, nullptr, false, false, -1};
     if (haveA && haveP) {
-        TraceArgs t{};
-        t.nb = 1;
-        t.k[0] = dP.k; t.v[0] = dP.v; t.w[0] = dP.w;
-        t.n[0] = spec ? 0 : dP.n;
+        TraceArgs t = trace_args_one(dP);
+        if (spec) t.n[0] = 0;  // read from the device (tn_dev below)
         plans[np++] = {0, t, DBSP_PROJ_HI_V2_LO_V1, nullptr, nullptr, false,
                        true, -1};
     }
@@ -2730,9 +2715,8 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
             pl.slot = jca.np;
             jca.dk[jca.np] = d.k;
             jca.nd[jca.np] = spec ? 0 : d.n;
-            if (spec)
-                jca.nd_dev[jca.np] = c->d_len + sb + (pl.which == 0 ? 10 : 11);
-            if (spec && pl.dd) jca.tn_dev[jca.np] = c->d_len + sb + 11;
+            if (spec) jca.nd_dev[jca.np] = c->d_len + sb + L_DELTA + pl.which;
+            if (spec && pl.dd) jca.tn_dev[jca.np] = c->d_len + sb + L_DELTA + 1;
             jca.t[jca.np] = pl.t;
             jca.cnts[jca.np] = pl.cnts;
             jca.offsets[jca.np] = pl.offsets;
@@ -2741,15 +2725,15 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     }
     jca_np = jca.np;
     if (arena_ok) {
-        jca.d_total = c->d_len + sb;
+        jca.d_total = c->d_len + sb + L_PLAN;
         if (jca.np > 0) TRY(dbspk::join_count_scan_batch(c->stream, jca));
     }
     return DBSP_OK;
 }
 
 // chained emits + output consolidate behind the device-side totals; the
-// verdicts (emit total / overflow flag / output length) land at
-// h_len[sb+12..15] via the second readback
+// verdicts (emit total / overflow flag / output length) land in base sb's
+// host LH_* slots via the second readback
 static dbsp_status q3_chain_emits(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
                                   Q3Plan plans[3], int np, int sb,
                                   DevBatch &comb_chain, bool &ok) {
@@ -2772,17 +2756,17 @@ static dbsp_status q3_chain_emits(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
         fa.dk[s2] = d.k;
         fa.dv[s2] = d.v;
         fa.dw[s2] = d.w;
-        fa.nd_dev[s2] = c->d_len + sb + (pl.which == 0 ? 10 : 11);
+        fa.nd_dev[s2] = c->d_len + sb + L_DELTA + pl.which;
         fa.t[s2] = pl.t;
-        fa.tn_dev[s2] = pl.dd ? c->d_len + sb + 11 : nullptr;
+        fa.tn_dev[s2] = pl.dd ? c->d_len + sb + L_DELTA + 1 : nullptr;
         fa.cnts[s2] = pl.cnts;
         fa.offsets[s2] = pl.offsets;
         fa.proj[s2] = pl.proj;
     }
-    fa.totals = c->d_len + sb;
+    fa.totals = c->d_len + sb + L_PLAN;
     fa.cap = Q3_EMIT_CAP;
-    fa.d_total = c->d_len + sb + 3;
-    fa.d_flag = c->d_len + sb + 4;
+    fa.d_total = c->d_len + sb + L_EMIT_TOTAL;
+    fa.d_flag = c->d_len + sb + L_EMIT_FLAG;
     fa.ok = comb_chain.k;
     fa.ov = comb_chain.v;
     fa.ow = comb_chain.w;
@@ -2793,19 +2777,13 @@ static dbsp_status q3_chain_emits(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     }
     SortArgs sa{};
     sa.nb = 1;
-    sa.kin[0] = comb_chain.k;
-    sa.vin[0] = comb_chain.v;
-    sa.win[0] = comb_chain.w;
-    sa.n_dev[0] = c->d_len + sb + 3;
-    sa.tk[0] = scr.k; sa.tv[0] = scr.v; sa.tw[0] = scr.w;
-    sa.ok[0] = e->out_store.k;
-    sa.ov[0] = e->out_store.v;
-    sa.ow[0] = e->out_store.w;
-    sa.d_len = c->d_len + sb + 6;
+    sort_slot(sa, 0, comb_chain, scr, e->out_store,
+              c->d_len + sb + L_EMIT_TOTAL);
+    sa.d_len = c->d_len + sb + L_FINAL;
     TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    HIP_CHECK_ST(hipMemcpyAsync(c->h_len + sb + 12, c->d_len + sb + 3,
-                                4 * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                c->stream));
+    // the second readback: device L_EMIT_TOTAL..L_FINAL -> host LH_*
+    TRY(read_len_to(c, sb + LH_EMIT_TOTAL, sb + L_EMIT_TOTAL, LH_TAIL_N,
+                    /*sync=*/false));
     ok = true;
     return DBSP_OK;
 }
@@ -2856,6 +2834,85 @@ static dbsp_status q3_emit_explicit(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
 
 static void q3_maybe_enqueue_train(dbsp_engine *e);
 
+// ---- tick pieces shared by q3 / q5 / q8 ----
+
+static inline void publish_store(dbsp_engine *e, int64_t n) {
+    e->output = e->out_store;
+    e->output.n = n;
+    e->output_is_store = true;
+}
+
+// Asynchronous final consolidate, first half: when the tick's raw result
+// rows fit one workgroup (and `allow`), gather them and launch the fused
+// sort into the reused out_store, with its length copy queued but not
+// waited for — the spine inserts that follow overlap it and their sync
+// covers the copy.  Otherwise outs is left for final_finish.
+static dbsp_status final_begin(dbsp_engine *e, std::vector<DevBatch> &outs,
+                               bool allow, bool &async) {
+    dbsp_ctx *c = e->ctx;
+    int64_t cat_n = 0;
+    for (auto &b : outs) cat_n += b.n;
+    async = allow && cat_n > 0 && cat_n <= 8192;
+    if (!async) return DBSP_OK;
+    ScopedTimer t0(c, 0, (double)cat_n * 48.0);
+    DevBatch cat, scratch;
+    TRY(gather_raw(c, outs, cat));
+    TRY(alloc_batch(c, cat_n, scratch, true));
+    if (e->out_cap < cat_n) {
+        if (e->out_store.k) free_batch(c, e->out_store);
+        e->out_cap = std::max<int64_t>(2 * cat_n, 8192);
+        TRY(alloc_batch(c, e->out_cap, e->out_store));
+    }
+    SortArgs sa{};
+    sa.nb = 1;
+    sort_slot(sa, 0, cat, scratch, e->out_store);
+    sa.d_len = c->d_len + L_FINAL;
+    TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+    return read_len(c, L_FINAL, 1, /*sync=*/false);
+}
+// second half, after the inserts: publish the store with the length that
+// has landed by now, or consolidate outs through the sized paths
+static dbsp_status final_finish(dbsp_engine *e, std::vector<DevBatch> &outs,
+                                bool async) {
+    if (!async) return finalize_raw(e->ctx, outs, e->output);
+    publish_store(e, e->ctx->h_len[L_FINAL]);
+    return DBSP_OK;
+}
+
+// speculation verdict of a chained q3 tick from its first readback (H = the
+// host slots of its base): a delta overflowed the fused sort, or a plan's
+// count saw a negative length
+static bool q3_spec_lost(const int64_t *H, const Q3Plan *plans, int np) {
+    if (H[L_DELTA] < 0 || H[L_DELTA + 1] < 0) return true;
+    for (int i = 0; i < np; i++)
+        if (plans[i].slot >= 0 && H[L_PLAN + plans[i].slot] < 0) return true;
+    return false;
+}
+
+// publish a chained q3 tick's output from its second readback (host LH_*
+// slots of base sb; the caller has waited past it)
+static dbsp_status q3_publish_chained(dbsp_engine *e, int sb, DevBatch &dA,
+                                      DevBatch &dP, Q3Plan plans[3], int np,
+                                      const int64_t slot_totals[3],
+                                      DevBatch &comb_chain) {
+    dbsp_ctx *c = e->ctx;
+    const int64_t *H = c->h_len + sb;
+    if (H[LH_EMIT_FLAG] != 0) {
+        // combined emits exceeded the capacity buffer: replay explicitly
+        // from the still-valid counts/offsets
+        std::vector<DevBatch> outs;
+        TRY(q3_emit_explicit(e, dA, dP, plans, np, slot_totals, outs));
+        return finalize_raw(c, outs, e->output);
+    }
+    if (H[LH_FINAL] >= 0) {
+        publish_store(e, H[LH_FINAL]);
+        return DBSP_OK;
+    }
+    // the output overflowed the fused sort: sized sort of the emitted rows
+    comb_chain.n = H[LH_EMIT_TOTAL];
+    return sort_consolidate_batch(c, comb_chain, e->output);
+}
+
 // the unpipelined tick body (round-1 path): deltas are already built;
 // plans/count/emits run in-step at slot base 0
 static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
@@ -2863,6 +2920,7 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
                            DevBatch rawP, DevBatch recvA, DevBatch recvP,
                            bool chain, bool shard_chain) {
     dbsp_ctx *c = e->ctx;
+    const int64_t *H = c->h_len + LEN_BASE0;
     std::vector<DevBatch> outs;
     bool chain_emits = false;
     DevBatch comb_chain{};
@@ -2871,186 +2929,93 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
     int np = 0;
     {
         ScopedTimer timer(c, 2, (double)n * 24.0);
-        if ((int)e->p_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->p_int.consolidate_all(c));
-        if ((int)e->a_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->a_int.consolidate_all(c));
+        TRY(e->p_int.cap_batches(c));
+        TRY(e->a_int.cap_batches(c));
         bool spec = chain;
         for (;;) {
             int jca_np = 0;
             bool arena_ok = true;
-            TRY(q3_plan_count(e, dA, dP, spec, 0, n, plans, np, jca_np,
+            TRY(q3_plan_count(e, dA, dP, spec, LEN_BASE0, n, plans, np, jca_np,
                               arena_ok));
-            if (spec && !arena_ok) {
-                HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                            18 * sizeof(int64_t),
-                                            hipMemcpyDeviceToHost, c->stream));
-                HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            } else {
-                HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                            18 * sizeof(int64_t),
-                                            hipMemcpyDeviceToHost, c->stream));
-                if (spec && jca_np > 0) {
-                    (void)hipEventRecord(c->ev_sync2, c->stream);
-                    TRY(q3_chain_emits(e, dA, dP, plans, np, 0, comb_chain,
-                                       chain_emits));
-                    (void)hipEventSynchronize(c->ev_sync2);
-                } else {
-                    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-                }
+            // one readback carries the plan totals and the delta lengths;
+            // with chained emits behind it the host wakes at an event
+            // recorded right after the copy instead of a full sync
+            const bool emits = spec && arena_ok && jca_np > 0;
+            TRY(read_len(c, LEN_BASE0, LEN_TICK, /*sync=*/!emits));
+            if (emits) {
+                (void)hipEventRecord(c->ev_sync2, c->stream);
+                TRY(q3_chain_emits(e, dA, dP, plans, np, LEN_BASE0, comb_chain,
+                                   chain_emits));
+                (void)hipEventSynchronize(c->ev_sync2);
             }
-            for (int i = 0; i < np && i < 3; i++) slot_totals[i] = c->h_len[i];
+            for (int i = 0; i < np && i < 3; i++)
+                slot_totals[i] = H[L_PLAN + i];
             if (!spec) break;
-            bool lost = !arena_ok || c->h_len[10] < 0 || c->h_len[11] < 0;
-            for (int i = 0; i < np && !lost; i++)
-                if (plans[i].slot >= 0 && c->h_len[plans[i].slot] < 0)
-                    lost = true;
-            if (!lost) {
-                dA.n = c->h_len[10];
-                dP.n = c->h_len[11];
+            if (arena_ok && !q3_spec_lost(H, plans, np)) {
+                dA.n = H[L_DELTA];
+                dP.n = H[L_DELTA + 1];
                 e->spec_fail = 0;
                 break;
             }
+            // lost: rebuild the deltas with host lengths from the furthest
+            // stage that held (received frames, else the raw streams), then
+            // go round once more without speculation
             e->spec_fail++;
             chain_emits = false;  // the chained emits bailed on the flag
             free_batch(c, dA);
             free_batch(c, dP);
-            if (shard_chain) {
-                if (c->h_len[16] < 0 || c->h_len[17] < 0) {
-                    rawA.n = c->h_len[8];
-                    rawP.n = c->h_len[9];
+            if (shard_chain && H[L_XCHG] >= 0 && H[L_XCHG + 1] >= 0) {
+                recvA.n = H[L_XCHG];
+                recvP.n = H[L_XCHG + 1];
+                TRY(sort_consolidate_batch(c, recvA, dA));
+                TRY(sort_consolidate_batch(c, recvP, dP));
+            } else {
+                rawA.n = H[L_RAW];
+                rawP.n = H[L_RAW + 1];
+                if (shard_chain) {
                     TRY(shard_exchange_pair(c, rawA, rawP, dA, dP));
                 } else {
-                    recvA.n = c->h_len[16];
-                    recvP.n = c->h_len[17];
-                    TRY(sort_consolidate_batch(c, recvA, dA));
-                    TRY(sort_consolidate_batch(c, recvP, dP));
-                    recvA = DevBatch{};
-                    recvP = DevBatch{};
+                    TRY(sort_consolidate_batch(c, rawA, dA));
+                    TRY(sort_consolidate_batch(c, rawP, dP));
                 }
-                rawA = DevBatch{};
-                rawP = DevBatch{};
-                spec = false;
-                continue;
             }
-            rawA.n = c->h_len[8];
-            rawP.n = c->h_len[9];
-            TRY(sort_consolidate_batch(c, rawA, dA));
-            TRY(sort_consolidate_batch(c, rawP, dP));
-            rawA = DevBatch{};
-            rawP = DevBatch{};
+            rawA = rawP = recvA = recvP = DevBatch{};
             spec = false;
         }
         for (int i = 0; i < np; i++)
             if (plans[i].dd) plans[i].t.n[0] = dP.n;
     }
     engine_free_output(e);
-    if (chain_emits) {
-        // the hook enqueues the NEXT tick's train mid-insert (after this
-        // tick's merge launches, before their wait): probing the
-        // pre-cascade batch list is Z-set-identical to the merged state,
-        // and single-stream ordering keeps any recycled buffers safe.  The
-        // insert's event sync (recorded pre-hook) covers this tick's
-        // readbacks, so the verdict reads below are complete.
-        std::function<dbsp_status()> hook = [&]() -> dbsp_status {
-            q3_maybe_enqueue_train(e);
-            return DBSP_OK;
-        };
-        // classic insert re-levels the spine: the accumulator identity is
-        // lost (a train enqueued by the hook merges from empty)
-        e->q3_acc[0] = e->q3_acc[1] = DevBatch{};
-        TRY(spines_insert_pair(c, e->a_int, dA, e->p_int, dP, &hook));
-        const int64_t flag = c->h_len[13];
-        if (flag == 0) {
-            const int64_t out_n = c->h_len[15];
-            if (out_n >= 0) {
-                e->output = e->out_store;
-                e->output.n = out_n;
-                e->output_is_store = true;
-            } else {
-                comb_chain.n = c->h_len[12];
-                TRY(sort_consolidate_batch(c, comb_chain, e->output));
-            }
-        } else {
-            TRY(q3_emit_explicit(e, dA, dP, plans, np, slot_totals, outs));
-            TRY(finalize_raw(c, outs, e->output));
-        }
+    // The hook enqueues the NEXT tick's train mid-insert (after this tick's
+    // merge launches, before their wait): probing the pre-cascade batch
+    // list is Z-set-identical to the merged state, and single-stream
+    // ordering keeps any recycled buffers safe.  The insert's event sync
+    // (recorded pre-hook) covers this tick's readbacks, so the length reads
+    // after it are complete.  Sharded ranks run no trains.
+    std::function<dbsp_status()> hook = [&]() -> dbsp_status {
+        q3_maybe_enqueue_train(e);
         return DBSP_OK;
+    };
+    // a classic insert re-levels the spine: the accumulator identity is
+    // lost (a train enqueued by the hook merges from empty)
+    e->q3_acc[0] = e->q3_acc[1] = DevBatch{};
+    if (chain_emits) {
+        TRY(spines_insert_pair(c, e->a_int, dA, e->p_int, dP, &hook));
+        return q3_publish_chained(e, LEN_BASE0, dA, dP, plans, np, slot_totals,
+                                  comb_chain);
     }
     // explicit path (sharded ranks and lost speculations)
     TRY(q3_emit_explicit(e, dA, dP, plans, np, slot_totals, outs));
-    int64_t cat_n = 0;
-    for (auto &b : outs) cat_n += b.n;
-    bool async_final = cat_n > 0 && cat_n <= 8192;
-    DevBatch res;
-    if (async_final) {
-        ScopedTimer t0(c, 0, (double)cat_n * 48.0);
-        DevBatch cat, scratch;
-        if (outs.size() == 1) {
-            cat = outs[0];
-            outs.clear();
-        } else {
-            TRY(alloc_batch(c, cat_n, cat, true));
-            int64_t off = 0;
-            for (auto &b : outs) {
-                if (b.n == 0) continue;
-                HIP_CHECK_ST(hipMemcpyAsync(cat.k + off, b.k, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.v + off, b.v, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.w + off, b.w, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                off += b.n;
-            }
-            for (auto &b : outs) free_batch(c, b);
-            outs.clear();
-        }
-        TRY(alloc_batch(c, cat_n, scratch, true));
-        if (e->out_cap < cat_n) {
-            if (e->out_store.k) free_batch(c, e->out_store);
-            e->out_cap = std::max<int64_t>(2 * cat_n, 8192);
-            TRY(alloc_batch(c, e->out_cap, e->out_store));
-        }
-        res = e->out_store;
-        SortArgs sa{};
-        sa.nb = 1;
-        sa.kin[0] = cat.k; sa.vin[0] = cat.v; sa.win[0] = cat.w; sa.n[0] = cat_n;
-        sa.tk[0] = scratch.k; sa.tv[0] = scratch.v; sa.tw[0] = scratch.w;
-        sa.ok[0] = res.k; sa.ov[0] = res.v; sa.ow[0] = res.w;
-        sa.d_len = c->d_len + 6;
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    }
-    if (async_final)
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 6, c->d_len + 6,
-                                    sizeof(int64_t), hipMemcpyDeviceToHost,
-                                    c->stream));
+    bool async_final = false;
+    TRY(final_begin(e, outs, true, async_final));
     if (!sharding_on(c)) {
-        std::function<dbsp_status()> hook = [&]() -> dbsp_status {
-            q3_maybe_enqueue_train(e);
-            return DBSP_OK;
-        };
-        e->q3_acc[0] = e->q3_acc[1] = DevBatch{};
         TRY(spines_insert_pair(c, e->a_int, dA, e->p_int, dP, &hook));
-        if (async_final) {
-            res.n = c->h_len[6];
-            e->output = res;
-            e->output_is_store = true;
-        } else {
-            TRY(finalize_raw(c, outs, e->output));
-        }
     } else {
-        e->q3_acc[0] = e->q3_acc[1] = DevBatch{};
         TRY(spines_insert_pair(c, e->a_int, dA, e->p_int, dP));
-        if (async_final) {
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            res.n = c->h_len[6];
-            e->output = res;
-            e->output_is_store = true;
-        } else {
-            TRY(finalize_raw(c, outs, e->output));
-        }
+        // no hook, so no event wait that covers the length copy
+        if (async_final) HIP_CHECK_ST(hipStreamSynchronize(c->stream));
     }
-    return DBSP_OK;
+    return final_finish(e, outs, async_final);
 }
 
 // enqueue the NEXT tick's full train (called after this tick's inserts have
@@ -3062,15 +3027,9 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
     const int sb = T.next_sb;
     const int evi = T.next_evi;
     const size_t save_base = c->arena_base, save_off = c->arena_off;
-    c->arena_base = c->arena_half ? (save_base ? 0 : c->arena_half) : save_base;
-    c->arena_off = 0;
+    arena_other_half(c, save_base);
     auto bail = [&](void) {
-        free_batch(c, T.oA);
-        free_batch(c, T.oP);
-        free_batch(c, T.res[0]);
-        free_batch(c, T.res[1]);
-        T.oA = DevBatch{};
-        T.oP = DevBatch{};
+        q3_train_drop(c, T);
         c->arena_base = save_base;
         c->arena_off = save_off;
         T.pending = false;
@@ -3097,26 +3056,20 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
     // round that left the GPU idle ~45 us at every tick boundary.
     {
         MergeArgs ma{};
-        // result lengths ride in sb+16/17 (the framed-exchange totals slots,
-        // unused on the unsharded train path) so the train's single 18-slot
-        // readback carries them — no extra D2H
-        const int slot_base = sb + 16;
         for (int s = 0; s < 2; s++) {
             DevBatch &acc = e->q3_acc[s];
-            DevBatch &delta = s == 0 ? T.oA : T.oP;
             if (alloc_batch(c, acc.n + n, T.res[s]) != DBSP_OK) {
                 bail();
                 return DBSP_OK;
             }
-            ma.ak[s] = acc.k; ma.av[s] = acc.v; ma.aw[s] = acc.w;
-            ma.na[s] = acc.n;
-            ma.bk[s] = delta.k; ma.bv[s] = delta.v; ma.bw[s] = delta.w;
-            ma.nb[s] = 0;
-            ma.dnb[s] = c->d_len + sb + (s == 0 ? 10 : 11);
-            ma.ok[s] = T.res[s].k; ma.ov[s] = T.res[s].v; ma.ow[s] = T.res[s].w;
+            merge_pair(ma, s, acc, s == 0 ? T.oA : T.oP, T.res[s],
+                       c->d_len + sb + L_DELTA + s);
             ma.np++;
         }
-        ma.d_len = c->d_len + slot_base;
+        // result lengths ride in the base's L_XCHG pair (unused on the
+        // unsharded train path) so the train's single LEN_TICK-slot readback
+        // carries them — no extra D2H
+        ma.d_len = c->d_len + sb + L_XCHG;
         ScopedTimer timer(c, 1, (double)(e->q3_acc[0].n + e->q3_acc[1].n +
                                          2 * n) * 48.0);
         TRY(dbspk::merge_mid_batch(c->stream, ma, c->d_mid));
@@ -3132,9 +3085,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         bail();
         return DBSP_OK;  // fall back: next step runs the unpipelined body
     }
-    HIP_CHECK_ST(hipMemcpyAsync(c->h_len + sb, c->d_len + sb,
-                                18 * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                c->stream));
+    TRY(read_len(c, sb, LEN_TICK, /*sync=*/false));
     (void)hipEventRecord(c->ev_tick[evi], c->stream);
     bool emits_ok = false;
     TRY(q3_chain_emits(e, T.oA, T.oP, T.plans, T.np, sb, T.comb_chain,
@@ -3143,7 +3094,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         bail();
         return DBSP_OK;
     }
-    // tail barrier: the commit's output-length reads (h_len[sb+12..15]) are
+    // tail barrier: the commit's output-length reads (host LH_* slots) are
     // written by the emit chain's SECOND readback, which ev_tick does not
     // cover — the commit waits this event just before consuming them
     (void)hipEventRecord(c->ev_tail[evi], c->stream);
@@ -3156,7 +3107,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
     T.n = n;
     T.sb = sb;
     T.evi = evi;
-    T.next_sb = sb == 0 ? 18 : 0;
+    T.next_sb = sb == LEN_BASE0 ? LEN_BASE1 : LEN_BASE0;
     T.next_evi = evi ^ 1;
     return DBSP_OK;
 }
@@ -3189,34 +3140,24 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     double t0 = prof ? host_us() : 0;
     dbsp_ctx *c = e->ctx;
     Q3Train T = e->train;
-    e->train.pending = false;
-    e->train.oA = DevBatch{};
-    e->train.oP = DevBatch{};
-    e->train.res[0] = DevBatch{};
-    e->train.res[1] = DevBatch{};
+    e->train.pending = false;  // T owns the batches now
+    e->train.oA = e->train.oP = DevBatch{};
+    e->train.res[0] = e->train.res[1] = DevBatch{};
     // commit-side transients go to the half the train is NOT using
-    c->arena_base =
-        c->arena_half ? (T.arena_base ? 0 : c->arena_half) : c->arena_base;
-    c->arena_off = 0;
+    arena_other_half(c, T.arena_base);
     (void)hipEventSynchronize(c->ev_tick[T.evi]);
     double t1 = prof ? host_us() : 0;
-    int64_t H[18];
+    int64_t H[LEN_TICK];  // the train's first readback (later ones reuse h_len)
     memcpy(H, c->h_len + T.sb, sizeof(H));
-    bool lost = H[10] < 0 || H[11] < 0;
-    for (int i = 0; i < T.np && !lost; i++)
-        if (T.plans[i].slot >= 0 && H[T.plans[i].slot] < 0) lost = true;
-    if (lost) {
+    if (q3_spec_lost(H, T.plans, T.np)) {
         e->spec_fail++;
-        free_batch(c, T.oA);
-        free_batch(c, T.oP);
-        free_batch(c, T.res[0]);
-        free_batch(c, T.res[1]);
+        q3_train_drop(c, T);
         // re-materialize the deltas from the raw flatmap outputs (arena of
         // the train's half — untouched until the next enqueue) and replay
         // the tick explicitly
         DevBatch dA, dP;
-        T.rawA.n = H[8];
-        T.rawP.n = H[9];
+        T.rawA.n = H[L_RAW];
+        T.rawP.n = H[L_RAW + 1];
         TRY(sort_consolidate_batch(c, T.rawA, dA));
         TRY(sort_consolidate_batch(c, T.rawP, dP));
         return q3_body(e, T.ev, T.n, dA, dP, DevBatch{}, DevBatch{},
@@ -3224,8 +3165,8 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     }
     e->spec_fail = 0;
     DevBatch dA = T.oA, dP = T.oP;
-    dA.n = H[10];
-    dP.n = H[11];
+    dA.n = H[L_DELTA];
+    dP.n = H[L_DELTA + 1];
     for (int i = 0; i < T.np; i++)
         if (T.plans[i].dd) T.plans[i].t.n[0] = dP.n;
     engine_free_output(e);
@@ -3243,7 +3184,7 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     for (int s = 0; s < 2; s++) {
         Spine &sp = s == 0 ? e->a_int : e->p_int;
         DevBatch res = T.res[s];
-        res.n = H[16 + s];
+        res.n = H[L_XCHG + s];  // the in-train accumulator merge's length
         DevBatch acc = e->q3_acc[s];
         if (acc.n > 0) {  // the top batch is the consumed accumulator
             sp.batches.pop_back();
@@ -3283,26 +3224,10 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     // this tick's output lengths land with the emit chain's second
     // readback, past ev_tick — wait the tail before consuming them
     (void)hipEventSynchronize(c->ev_tail[T.evi]);
-    const int64_t flag = c->h_len[T.sb + 13];
-    if (flag == 0) {
-        const int64_t out_n = c->h_len[T.sb + 15];
-        if (out_n >= 0) {
-            e->output = e->out_store;
-            e->output.n = out_n;
-            e->output_is_store = true;
-        } else {
-            T.comb_chain.n = c->h_len[T.sb + 12];
-            TRY(sort_consolidate_batch(c, T.comb_chain, e->output));
-        }
-    } else {
-        // combined emits exceeded the capacity buffer: replay explicitly
-        // from the still-valid counts/offsets
-        int64_t slot_totals[3] = {0, 0, 0};
-        for (int i = 0; i < T.np && i < 3; i++) slot_totals[i] = H[i];
-        std::vector<DevBatch> outs;
-        TRY(q3_emit_explicit(e, dA, dP, T.plans, T.np, slot_totals, outs));
-        TRY(finalize_raw(c, outs, e->output));
-    }
+    int64_t slot_totals[3] = {0, 0, 0};
+    for (int i = 0; i < T.np && i < 3; i++) slot_totals[i] = H[L_PLAN + i];
+    TRY(q3_publish_chained(e, T.sb, dA, dP, T.plans, T.np, slot_totals,
+                           T.comb_chain));
     // the deltas were folded into res by the in-train merge (they are NOT
     // in the spine); free once the output paths above are done with them
     free_batch(c, dA);
@@ -3316,11 +3241,8 @@ static dbsp_status q3_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         if (e->train.ev == d_ev && e->train.n == n) return q3_commit_train(e);
         // stale train (out-of-band step): drain its enqueued work, discard
         (void)hipStreamSynchronize(c->stream);
-        free_batch(c, e->train.oA);
-        free_batch(c, e->train.oP);
-        free_batch(c, e->train.res[0]);
-        free_batch(c, e->train.res[1]);
-            e->train.pending = false;
+        q3_train_drop(c, e->train);
+        e->train.pending = false;
     }
     const bool shard_chain =
         sharding_on(c) && c->world <= 8 && n <= 131072 && e->spec_fail < 3;
@@ -3339,30 +3261,95 @@ static dbsp_status q3_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
                    shard_chain);
 }
 
+// ---- q5 / q8: pipelined front half, device watermark ----
+
+// Take the pipelined front (launched during the previous tick's tail): true
+// if it was built for exactly this tick.  A stale one (out-of-band step) is
+// discarded; q5 fronts hold only arena transients, so only q8's sorted
+// outputs need freeing.
+static bool take_front(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
+    if (!e->front.pending) return false;
+    e->front.pending = false;
+    if (e->front.ev == d_ev && e->front.n == n) return true;
+    free_batch(e->ctx, e->front.oA);
+    free_batch(e->ctx, e->front.oB);
+    return false;
+}
+
+// Run `build` — the launches of the NEXT tick's front half, filling
+// e->front's batches — in the arena half this tick is not using, and mark
+// the front pending for (next_ev, next_n) if it queued cleanly.  Called from
+// the tail insert's hook, so the launches overlap this tick's host-side tail.
+template <class Build>
+static dbsp_status enqueue_front(dbsp_engine *e, Build build) {
+    dbsp_ctx *c = e->ctx;
+    const size_t save_base = c->arena_base, save_off = c->arena_off;
+    arena_other_half(c, save_base);
+    const dbsp_status st = build();
+    e->front.arena_base = c->arena_base;
+    e->front.arena_off = c->arena_off;
+    c->arena_base = save_base;
+    c->arena_off = save_off;
+    if (st == DBSP_OK) {
+        e->front.pending = true;
+        e->front.ev = e->next_ev;
+        e->front.n = e->next_n;
+    }
+    return st;
+}
+
+// readback of the bounds the device watermark published
+// {s0, e0, s1, e1, have_prev, err}
+static dbsp_status read_bounds(dbsp_engine *e, bool sync) {
+    HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds, 6 * sizeof(uint64_t),
+                                hipMemcpyDeviceToHost, e->ctx->stream));
+    if (sync) HIP_CHECK_ST(hipStreamSynchronize(e->ctx->stream));
+    return DBSP_OK;
+}
+
+// Explicit-path watermark (sharded exchange / chain fallback): the tick's
+// local max event time — the last key of the time-keyed delta d — reduces
+// across ranks ON THE STREAM (q8.rs:63-65 as an RCCL allreduce feeding
+// k_wm_update_g) and the bounds are published device-side into the same
+// state words the chained path uses, so flipping between the modes never
+// desyncs the watermark.
+static dbsp_status wm_update_global(dbsp_engine *e, const DevBatch &d,
+                                    uint64_t width, uint64_t tumble,
+                                    uint64_t lag) {
+    dbsp_ctx *c = e->ctx;
+    unsigned long long *gslot = e->d_wm + 10;
+    if (d.n > 0) {
+        HIP_CHECK_ST(hipMemcpyAsync(gslot, d.k + d.n - 1, sizeof(uint64_t),
+                                    hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        HIP_CHECK_ST(hipMemsetAsync(gslot, 0, sizeof(uint64_t), c->stream));
+    }
+    if (sharding_on(c) &&
+        ncclAllReduce(gslot, gslot, 1, ncclUint64, ncclMax, c->comm,
+                      c->stream) != ncclSuccess)
+        return DBSP_ERR_INTERNAL;
+    return dbspk::wm_update_g(c->stream, gslot, width, tumble, lag, e->d_wm,
+                              e->d_bounds);
+}
+
 // ---- q8 tick (queries/q8.rs:48-93) ----
 static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
     constexpr uint64_t TUMBLE_MS = 10000;
+    const int64_t *H = c->h_len + LEN_BASE0;
     // Single-rank ticks chain flatmap -> sorts -> device watermark -> window
     // ranges with ONE sync; the watermark lives in e->d_wm so the bounds
     // never round-trip to the host on the fast path.  Sharded ranks keep the
     // explicit path (the watermark allreduce and exchange need host values).
-    bool use_front = e->front.pending && e->front.ev == d_ev &&
-                     e->front.n == n;
-    if (e->front.pending && !use_front) {  // stale pipelined front: discard
-        free_batch(c, e->front.oA);
-        free_batch(c, e->front.oB);
-        e->front.pending = false;
-    }
+    const bool use_front = take_front(e, d_ev, n);
     const bool chain = use_front ||
                        (!sharding_on(c) && e->d_wm && n <= 131072 &&
                         e->spec_fail < 3);
     DevBatch dPT, dAT, rawP, rawA;
     std::vector<DevBatch> wp_raw, wa_raw;
-    bool front_done = false;
+    WindowPlan wpP, wpA;
     if (chain) {
         if (use_front) {
-            e->front.pending = false;
             rawP = e->front.rawA;
             rawA = e->front.rawB;
             dPT = e->front.oA;
@@ -3370,63 +3357,39 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         } else {
             TRY(build_deltas_chain(e, d_ev, n, rawP, rawA, dPT, dAT));
         }
-        TRY(dbspk::wm_update(c->stream, dAT.k, c->d_len + 11, TUMBLE_MS,
-                             TUMBLE_MS, TUMBLE_MS, e->d_wm, e->d_bounds));
-        if ((int)e->pt_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->pt_int.consolidate_all(c));
-        if ((int)e->at_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->at_int.consolidate_all(c));
-        TraceArgs taP = trace_args_of(e->pt_int), taA = trace_args_of(e->at_int);
-        const int nregP = 3 * taP.nb + 1, nregA = 3 * taA.nb + 1;
-        int64_t *tableP = (int64_t *)arena_alloc(c, (size_t)nregP * 5 * 8 + 8);
-        int64_t *tableA = (int64_t *)arena_alloc(c, (size_t)nregA * 5 * 8 + 8);
-        bool launched = tableP && tableA;
+        TRY(dbspk::wm_update(c->stream, dAT.k, c->d_len + L_DELTA + 1,
+                             TUMBLE_MS, TUMBLE_MS, TUMBLE_MS, e->d_wm,
+                             e->d_bounds));
+        TRY(window_plan(c, e->pt_int, wpP));
+        TRY(window_plan(c, e->at_int, wpA));
+        const bool launched = wpP.table && wpA.table;
         if (launched) {
             ScopedTimer t(c, 4, 0.0);
-            TRY(dbspk::window_ranges_chain(c->stream, taP, dPT.k, 0,
-                                           c->d_len + 10, e->d_bounds, tableP,
-                                           c->d_len + 12));
-            TRY(dbspk::window_ranges_chain(c->stream, taA, dAT.k, 0,
-                                           c->d_len + 11, e->d_bounds, tableA,
-                                           c->d_len + 13));
+            TRY(dbspk::window_ranges_chain(c->stream, wpP.ta, dPT.k, 0,
+                                           c->d_len + L_DELTA, e->d_bounds,
+                                           wpP.table, c->d_len + L_WIN2));
+            TRY(dbspk::window_ranges_chain(c->stream, wpA.ta, dAT.k, 0,
+                                           c->d_len + L_DELTA + 1, e->d_bounds,
+                                           wpA.table, c->d_len + L_WIN2 + 1));
         }
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, 18 * sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds,
-                                    6 * sizeof(uint64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+        TRY(read_len(c, LEN_BASE0, LEN_TICK, /*sync=*/false));
+        TRY(read_bounds(e, /*sync=*/true));
         const bool lost = !launched || e->h_bounds[5] != 0 ||
-                          c->h_len[10] < 0 || c->h_len[11] < 0 ||
-                          c->h_len[12] < 0 || c->h_len[13] < 0;
+                          H[L_DELTA] < 0 || H[L_DELTA + 1] < 0 ||
+                          H[L_WIN2] < 0 || H[L_WIN2 + 1] < 0;
         if (!lost) {
-            dPT.n = c->h_len[10];
-            dAT.n = c->h_len[11];
-            if (c->h_len[12] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[12], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taP, dPT.k, dPT.v,
-                                             dPT.w, tableP, nregP,
-                                             c->h_len[12], o.k, o.v, o.w));
-                wp_raw.push_back(o);
-            }
-            if (c->h_len[13] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[13], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taA, dAT.k, dAT.v,
-                                             dAT.w, tableA, nregA,
-                                             c->h_len[13], o.k, o.v, o.w));
-                wa_raw.push_back(o);
-            }
-            front_done = true;
+            dPT.n = H[L_DELTA];
+            dAT.n = H[L_DELTA + 1];
+            TRY(window_emit(c, wpP, H[L_WIN2], dPT, wp_raw));
+            TRY(window_emit(c, wpA, H[L_WIN2 + 1], dAT, wa_raw));
             e->spec_fail = 0;
         } else {
             e->spec_fail++;
             // speculation lost (delta overflowed the fused sort, or no arena
             // for the tables): re-sort with real lengths, pull the watermark
             // state to the host, run the explicit window path, write back
-            rawP.n = c->h_len[8];
-            rawA.n = c->h_len[9];
+            rawP.n = H[L_RAW];
+            rawA.n = H[L_RAW + 1];
             free_batch(c, dPT);
             free_batch(c, dAT);
             TRY(sort_consolidate_batch(c, rawP, dPT));
@@ -3455,82 +3418,32 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
             hw[3] = 1;
             HIP_CHECK_ST(hipMemcpyAsync(e->d_wm, hw, sizeof(hw),
                                         hipMemcpyHostToDevice, c->stream));
-            front_done = true;
         }
-    }
-    if (!front_done) {
-        // explicit deltas (sharded exchange / chain fallback), but the
-        // watermark and windows stay device-side: the tick's local max
-        // event-time reduces across ranks ON THE STREAM (q8.rs:63-65 as an
-        // RCCL allreduce feeding k_wm_update_g) and the ranges chain behind
-        // it — the same state words the chained path uses, so flipping
-        // between the modes never desyncs the watermark.
+    } else {
+        // explicit deltas, but the watermark and windows stay device-side
+        // and the ranges chain behind the watermark
         TRY(build_deltas(e, d_ev, n, dPT, dAT, true));
-        unsigned long long *gslot = e->d_wm + 10;
-        if (dAT.n > 0) {
-            HIP_CHECK_ST(hipMemcpyAsync(gslot, dAT.k + dAT.n - 1,
-                                        sizeof(uint64_t),
-                                        hipMemcpyDeviceToDevice, c->stream));
-        } else {
-            HIP_CHECK_ST(hipMemsetAsync(gslot, 0, sizeof(uint64_t),
-                                        c->stream));
-        }
-        if (sharding_on(c) &&
-            ncclAllReduce(gslot, gslot, 1, ncclUint64, ncclMax, c->comm,
-                          c->stream) != ncclSuccess)
-            return DBSP_ERR_INTERNAL;
-        TRY(dbspk::wm_update_g(c->stream, gslot, TUMBLE_MS, TUMBLE_MS,
-                               TUMBLE_MS, e->d_wm, e->d_bounds));
-        if ((int)e->pt_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->pt_int.consolidate_all(c));
-        if ((int)e->at_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->at_int.consolidate_all(c));
-        TraceArgs taP = trace_args_of(e->pt_int), taA = trace_args_of(e->at_int);
-        const int nregP = 3 * taP.nb + 1, nregA = 3 * taA.nb + 1;
-        int64_t *tableP = (int64_t *)arena_alloc(c, (size_t)nregP * 5 * 8 + 8);
-        int64_t *tableA = (int64_t *)arena_alloc(c, (size_t)nregA * 5 * 8 + 8);
-        if (tableP && tableA) {
+        TRY(wm_update_global(e, dAT, TUMBLE_MS, TUMBLE_MS, TUMBLE_MS));
+        TRY(window_plan(c, e->pt_int, wpP));
+        TRY(window_plan(c, e->at_int, wpA));
+        if (wpP.table && wpA.table) {
             {
                 ScopedTimer t(c, 4, 0.0);
-                TRY(dbspk::window_ranges_chain(c->stream, taP, dPT.k, dPT.n,
-                                               nullptr, e->d_bounds, tableP,
-                                               c->d_len + 12));
-                TRY(dbspk::window_ranges_chain(c->stream, taA, dAT.k, dAT.n,
-                                               nullptr, e->d_bounds, tableA,
-                                               c->d_len + 13));
+                TRY(dbspk::window_ranges_chain(c->stream, wpP.ta, dPT.k, dPT.n,
+                                               nullptr, e->d_bounds, wpP.table,
+                                               c->d_len + L_WIN2));
+                TRY(dbspk::window_ranges_chain(c->stream, wpA.ta, dAT.k, dAT.n,
+                                               nullptr, e->d_bounds, wpA.table,
+                                               c->d_len + L_WIN2 + 1));
             }
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                        18 * sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            if (c->h_len[12] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[12], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taP, dPT.k, dPT.v,
-                                             dPT.w, tableP, nregP,
-                                             c->h_len[12], o.k, o.v, o.w));
-                wp_raw.push_back(o);
-            }
-            if (c->h_len[13] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[13], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taA, dAT.k, dAT.v,
-                                             dAT.w, tableA, nregA,
-                                             c->h_len[13], o.k, o.v, o.w));
-                wa_raw.push_back(o);
-            }
+            TRY(read_len(c, LEN_BASE0, LEN_TICK));
+            TRY(window_emit(c, wpP, H[L_WIN2], dPT, wp_raw));
+            TRY(window_emit(c, wpA, H[L_WIN2 + 1], dAT, wa_raw));
         } else {
             // no arena: read the published bounds and run the generic path
-            HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds,
-                                        6 * sizeof(uint64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            TRY(window_vs_spine(c, e->pt_int, dPT, e->h_bounds[4] != 0,
-                                e->h_bounds[0], e->h_bounds[1], e->h_bounds[2],
-                                e->h_bounds[3], wp_raw));
-            TRY(window_vs_spine(c, e->at_int, dAT, e->h_bounds[4] != 0,
-                                e->h_bounds[0], e->h_bounds[1], e->h_bounds[2],
-                                e->h_bounds[3], wa_raw));
+            TRY(read_bounds(e, /*sync=*/true));
+            TRY(window_vs_spine_bounds(c, e->pt_int, dPT, e->h_bounds, wp_raw));
+            TRY(window_vs_spine_bounds(c, e->at_int, dAT, e->h_bounds, wa_raw));
         }
     }
     if (sharding_on(c)) {
@@ -3557,88 +3470,22 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     std::vector<DevBatch> outs;
     TRY(join_vs_spine(c, dWP, e->wa_int, DBSP_PROJ_HI_K_LO_V1RND, TUMBLE_MS, outs));
     TRY(join_vs_spine(c, dWA, e->wp_int, DBSP_PROJ_HI_K_LO_V2RND, TUMBLE_MS, outs));
-    if (dWP.n > 0 && dWA.n > 0) {
-        TraceArgs t{};
-        t.nb = 1;
-        t.k[0] = dWA.k; t.v[0] = dWA.v; t.w[0] = dWA.w; t.n[0] = dWA.n;
-        DevBatch o;
-        ScopedTimer timer(c, 2, (double)dWP.n * 24.0);
-        TRY(dbspk::join_spine_rows(c->stream, dWP.k, dWP.v, dWP.w, dWP.n, t,
-                                   DBSP_PROJ_HI_K_LO_V1RND, TUMBLE_MS, &o.k,
-                                   &o.v, &o.w, &o.n));
-        if (o.n > 0) outs.push_back(o);
-        else free_batch(c, o);
-    }
+    TRY(join_vs_batch(c, dWP, dWA, DBSP_PROJ_HI_K_LO_V1RND, TUMBLE_MS, outs));
     engine_free_output(e);
     // consolidate the joined output asynchronously (as q3): sort launched to
     // the reused store before the inserts, length read at their sync
-    int64_t cat_n = 0;
-    for (auto &b : outs) cat_n += b.n;
-    const bool async_final = !sharding_on(c) && cat_n > 0 && cat_n <= 8192;
-    DevBatch res;
-    if (async_final) {
-        ScopedTimer t0(c, 0, (double)cat_n * 48.0);
-        DevBatch cat, scratch;
-        if (outs.size() == 1) {
-            cat = outs[0];
-            outs.clear();
-        } else {
-            TRY(alloc_batch(c, cat_n, cat, true));
-            int64_t off = 0;
-            for (auto &b : outs) {
-                if (b.n == 0) continue;
-                HIP_CHECK_ST(hipMemcpyAsync(cat.k + off, b.k, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.v + off, b.v, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.w + off, b.w, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                off += b.n;
-            }
-            for (auto &b : outs) free_batch(c, b);
-            outs.clear();
-        }
-        TRY(alloc_batch(c, cat_n, scratch, true));
-        if (e->out_cap < cat_n) {
-            if (e->out_store.k) free_batch(c, e->out_store);
-            e->out_cap = std::max<int64_t>(2 * cat_n, 8192);
-            TRY(alloc_batch(c, e->out_cap, e->out_store));
-        }
-        res = e->out_store;
-        SortArgs sa{};
-        sa.nb = 1;
-        sa.kin[0] = cat.k; sa.vin[0] = cat.v; sa.win[0] = cat.w;
-        sa.n[0] = cat_n;
-        sa.tk[0] = scratch.k; sa.tv[0] = scratch.v; sa.tw[0] = scratch.w;
-        sa.ok[0] = res.k; sa.ov[0] = res.v; sa.ow[0] = res.w;
-        sa.d_len = c->d_len + 6;
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 6, c->d_len + 6,
-                                    sizeof(int64_t), hipMemcpyDeviceToHost,
-                                    c->stream));
-    }
+    bool async_final = false;
+    TRY(final_begin(e, outs, !sharding_on(c), async_final));
     if (!sharding_on(c)) {
         std::function<dbsp_status()> hook = [&]() -> dbsp_status {
             if (!e->next_ev || e->next_n < 0 || e->next_n > 131072 ||
                 e->spec_fail >= 3 || !e->d_wm)
                 return DBSP_OK;
-            const size_t save_base = c->arena_base, save_off = c->arena_off;
-            c->arena_base =
-                c->arena_half ? (save_base ? 0 : c->arena_half) : save_base;
-            c->arena_off = 0;
-            dbsp_status st = build_deltas_chain(e, e->next_ev, e->next_n,
-                                                e->front.rawA, e->front.rawB,
-                                                e->front.oA, e->front.oB);
-            e->front.arena_base = c->arena_base;
-            e->front.arena_off = c->arena_off;
-            c->arena_base = save_base;
-            c->arena_off = save_off;
-            if (st == DBSP_OK) {
-                e->front.pending = true;
-                e->front.ev = e->next_ev;
-                e->front.n = e->next_n;
-            }
-            return st;
+            return enqueue_front(e, [&] {
+                return build_deltas_chain(e, e->next_ev, e->next_n,
+                                          e->front.rawA, e->front.rawB,
+                                          e->front.oA, e->front.oB);
+            });
         };
         Spine *sps[4] = {&e->wp_int, &e->wa_int, &e->pt_int, &e->at_int};
         DevBatch bs[4] = {dWP, dWA, dPT, dAT};
@@ -3646,65 +3493,51 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     } else {
         TRY(spines_insert_pair(c, e->wp_int, dWP, e->wa_int, dWA));
     }
-    if (async_final) {
-        res.n = c->h_len[6];
-        e->output = res;
-        e->output_is_store = true;
-    } else {
-        TRY(finalize_raw(c, outs, e->output));
-    }
-    return DBSP_OK;
+    return final_finish(e, outs, async_final);
+}
+
+// q5's front half: chained flatmap, then the min/max of the bid stream (the
+// dense-sort probe) chained behind its device row counter into L_MINMAX
+static dbsp_status q5_front(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
+                            DevBatch &raw0, DevBatch &raw1) {
+    dbsp_ctx *c = e->ctx;
+    TRY(flatmap_chain(e, d_ev, n, raw0, raw1));
+    return dbspk::minmax_rows_chain(
+        c->stream, raw0.k, raw0.v, n > 0 ? n : 1, c->d_len + L_RAW,
+        (unsigned long long *)(c->d_len + L_MINMAX));
 }
 
 // ---- q5 tick (queries/q5.rs:77-121) ----
 static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
     constexpr uint64_t WIDTH_MS = 10000, TUMBLE_MS = 2000, WM_LAG_MS = 4000;
+    const int64_t *H = c->h_len + LEN_BASE0;
     // Single-rank ticks: flatmap and the dense-range min/max probe chain into
     // ONE sync, the bid delta sorts through the dense path, and the
     // watermark/window-ranges run device-side as in q8.
     const bool chain = !sharding_on(c) && e->d_wm;
     DevBatch dBT;
     std::vector<DevBatch> wb_raw;
-    bool front_done = false;
-    bool use_front = e->front.pending && e->front.ev == d_ev &&
-                     e->front.n == n;
-    if (e->front.pending && !use_front) {  // stale pipelined front: discard
-        e->front.pending = false;  // q5 fronts hold only arena transients
-    }
+    WindowPlan wpB;
+    const bool use_front = take_front(e, d_ev, n);
     if (chain) {
-        const int64_t cap = n > 0 ? n : 1;
         DevBatch raw0, raw1;
         if (use_front) {
-            e->front.pending = false;
             raw0 = e->front.rawA;
             raw1 = e->front.rawB;
         } else {
-            TRY(alloc_batch(c, cap, raw0, true));
-            TRY(alloc_batch(c, cap, raw1, true));
-            dbspk::EventCols cols{};
-            const bool hc = staged_cols(e, d_ev, cols);
-            TRY(dbspk::flatmap_events_chain(c->stream, d_ev,
-                                            hc ? &cols : nullptr, n, e->query,
-                                            raw0.k, raw0.v, raw0.w, raw1.k,
-                                            raw1.v, raw1.w,
-                                            (uint64_t *)(c->d_len + 8)));
-            TRY(dbspk::minmax_rows_chain(c->stream, raw0.k, raw0.v, cap,
-                                         c->d_len + 8,
-                                         (unsigned long long *)(c->d_len + 12)));
+            TRY(q5_front(e, d_ev, n, raw0, raw1));
         }
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len, 18 * sizeof(int64_t),
-                                    hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+        TRY(read_len(c, LEN_BASE0, LEN_TICK));
         free_batch(c, raw1);
-        const int64_t n0 = c->h_len[8];
+        const int64_t n0 = H[L_RAW];
         raw0.n = n0;
-        bool n_pending = false;  // dBT.n still on the device (d_len[5])
+        bool n_pending = false;  // dBT.n still on the device (L_DENSE)
         if (n0 == 0) {
             dBT = DevBatch{};
             free_batch(c, raw0);
         } else {
-            const uint64_t *mm = (const uint64_t *)(c->h_len + 12);
+            const uint64_t *mm = (const uint64_t *)(H + L_MINMAX);
             const uint64_t kr = mm[2] - mm[0], vr = mm[3] - mm[1];
             const int64_t dense_cap =
                 std::min<int64_t>((int64_t)1 << 22, 8 * n0);
@@ -3718,7 +3551,7 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
                 TRY(dbspk::sort_cons_dense_chain(
                     c->stream, raw0.k, raw0.v, raw0.w, n0, mm[0], mm[1],
                     (int64_t)(kr + 1), (int64_t)(vr + 1), res.k, res.v, res.w,
-                    c->d_len + 5));
+                    c->d_len + L_DENSE));
                 free_batch(c, raw0);
                 dBT = res;
                 dBT.n = -1;
@@ -3729,117 +3562,53 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         }
         // device watermark + chained window ranges (q5.rs:85-90)
         if (n_pending) {
-            TRY(dbspk::wm_update(c->stream, dBT.k, c->d_len + 5, WIDTH_MS,
-                                 TUMBLE_MS, WM_LAG_MS, e->d_wm, e->d_bounds));
+            TRY(dbspk::wm_update(c->stream, dBT.k, c->d_len + L_DENSE,
+                                 WIDTH_MS, TUMBLE_MS, WM_LAG_MS, e->d_wm,
+                                 e->d_bounds));
         } else {
             TRY(dbspk::wm_update_n(c->stream, dBT.k, dBT.n, WIDTH_MS,
                                    TUMBLE_MS, WM_LAG_MS, e->d_wm,
                                    e->d_bounds));
         }
-        if ((int)e->bt_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->bt_int.consolidate_all(c));
-        TraceArgs taB = trace_args_of(e->bt_int);
-        const int nregB = 3 * taB.nb + 1;
-        int64_t *tableB = (int64_t *)arena_alloc(c, (size_t)nregB * 5 * 8 + 8);
-        if (tableB) {
+        TRY(window_plan(c, e->bt_int, wpB));
+        if (wpB.table) {
             {
                 ScopedTimer t(c, 4, 0.0);
                 TRY(dbspk::window_ranges_chain(
-                    c->stream, taB, dBT.k, dBT.n,
-                    n_pending ? c->d_len + 5 : nullptr, e->d_bounds, tableB,
-                    c->d_len + 7));
+                    c->stream, wpB.ta, dBT.k, dBT.n,
+                    n_pending ? c->d_len + L_DENSE : nullptr, e->d_bounds,
+                    wpB.table, c->d_len + L_WIN));
             }
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                        18 * sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            if (n_pending) {
-                dBT.n = c->h_len[5];
-                n_pending = false;
-            }
-            if (c->h_len[7] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[7], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taB, dBT.k, dBT.v,
-                                             dBT.w, tableB, nregB, c->h_len[7],
-                                             o.k, o.v, o.w));
-                wb_raw.push_back(o);
-            }
-            front_done = true;
+            TRY(read_len(c, LEN_BASE0, LEN_TICK));
+            if (n_pending) dBT.n = H[L_DENSE];
+            TRY(window_emit(c, wpB, H[L_WIN], dBT, wb_raw));
         } else {
             // no arena for the table: wm_update already advanced the device
             // state and published the bounds — read them (and the pending
             // dense length) and run the explicit window path
-            HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds,
-                                        6 * sizeof(uint64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len, c->d_len,
-                                        18 * sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            if (n_pending) {
-                dBT.n = c->h_len[5];
-                n_pending = false;
-            }
-            TRY(window_vs_spine(c, e->bt_int, dBT, e->h_bounds[4] != 0,
-                                e->h_bounds[0], e->h_bounds[1], e->h_bounds[2],
-                                e->h_bounds[3], wb_raw));
-            front_done = true;
+            TRY(read_bounds(e, /*sync=*/false));
+            TRY(read_len(c, LEN_BASE0, LEN_TICK));
+            if (n_pending) dBT.n = H[L_DENSE];
+            TRY(window_vs_spine_bounds(c, e->bt_int, dBT, e->h_bounds, wb_raw));
         }
-    }
-    if (!front_done) {
-        // explicit deltas (sharded exchange), device watermark: local max
-        // event-time reduced across ranks on the stream, bounds published
-        // device-side into the same state the chained path uses
+    } else {
+        // explicit deltas (sharded exchange), device watermark
         DevBatch dummy;
         TRY(build_deltas(e, d_ev, n, dBT, dummy, false));
-        unsigned long long *gslot = e->d_wm + 10;
-        if (dBT.n > 0) {
-            HIP_CHECK_ST(hipMemcpyAsync(gslot, dBT.k + dBT.n - 1,
-                                        sizeof(uint64_t),
-                                        hipMemcpyDeviceToDevice, c->stream));
-        } else {
-            HIP_CHECK_ST(hipMemsetAsync(gslot, 0, sizeof(uint64_t),
-                                        c->stream));
-        }
-        if (sharding_on(c) &&
-            ncclAllReduce(gslot, gslot, 1, ncclUint64, ncclMax, c->comm,
-                          c->stream) != ncclSuccess)
-            return DBSP_ERR_INTERNAL;
-        TRY(dbspk::wm_update_g(c->stream, gslot, WIDTH_MS, TUMBLE_MS,
-                               WM_LAG_MS, e->d_wm, e->d_bounds));
-        if ((int)e->bt_int.batches.size() > MAX_TRACE_BATCHES)
-            TRY(e->bt_int.consolidate_all(c));
-        TraceArgs taB = trace_args_of(e->bt_int);
-        const int nregB = 3 * taB.nb + 1;
-        int64_t *tableB = (int64_t *)arena_alloc(c, (size_t)nregB * 5 * 8 + 8);
-        if (tableB) {
+        TRY(wm_update_global(e, dBT, WIDTH_MS, TUMBLE_MS, WM_LAG_MS));
+        TRY(window_plan(c, e->bt_int, wpB));
+        if (wpB.table) {
             {
                 ScopedTimer t(c, 4, 0.0);
-                TRY(dbspk::window_ranges_chain(c->stream, taB, dBT.k, dBT.n,
-                                               nullptr, e->d_bounds, tableB,
-                                               c->d_len + 7));
+                TRY(dbspk::window_ranges_chain(c->stream, wpB.ta, dBT.k, dBT.n,
+                                               nullptr, e->d_bounds, wpB.table,
+                                               c->d_len + L_WIN));
             }
-            HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 7, c->d_len + 7,
-                                        sizeof(int64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            if (c->h_len[7] > 0) {
-                DevBatch o;
-                TRY(alloc_batch(c, c->h_len[7], o, true));
-                TRY(dbspk::window_emit_multi(c->stream, taB, dBT.k, dBT.v,
-                                             dBT.w, tableB, nregB,
-                                             c->h_len[7], o.k, o.v, o.w));
-                wb_raw.push_back(o);
-            }
+            TRY(read_len(c, L_WIN, 1));
+            TRY(window_emit(c, wpB, H[L_WIN], dBT, wb_raw));
         } else {
-            HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds,
-                                        6 * sizeof(uint64_t),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            TRY(window_vs_spine(c, e->bt_int, dBT, e->h_bounds[4] != 0,
-                                e->h_bounds[0], e->h_bounds[1], e->h_bounds[2],
-                                e->h_bounds[3], wb_raw));
+            TRY(read_bounds(e, /*sync=*/true));
+            TRY(window_vs_spine_bounds(c, e->bt_int, dBT, e->h_bounds, wb_raw));
         }
     }
     if (sharding_on(c)) TRY(e->bt_int.insert(c, dBT));
@@ -3924,85 +3693,16 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         else free_batch(c, o);
     }
     engine_free_output(e);
-    int64_t cat_n = 0;
-    for (auto &b : outs) cat_n += b.n;
-    const bool async_final = !sharding_on(c) && cat_n > 0 && cat_n <= 8192;
-    DevBatch res;
-    if (async_final) {
-        ScopedTimer t0(c, 0, (double)cat_n * 48.0);
-        DevBatch cat, scratch;
-        if (outs.size() == 1) {
-            cat = outs[0];
-            outs.clear();
-        } else {
-            TRY(alloc_batch(c, cat_n, cat, true));
-            int64_t off = 0;
-            for (auto &b : outs) {
-                if (b.n == 0) continue;
-                HIP_CHECK_ST(hipMemcpyAsync(cat.k + off, b.k, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.v + off, b.v, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                HIP_CHECK_ST(hipMemcpyAsync(cat.w + off, b.w, b.n * 8,
-                                            hipMemcpyDeviceToDevice, c->stream));
-                off += b.n;
-            }
-            for (auto &b : outs) free_batch(c, b);
-            outs.clear();
-        }
-        TRY(alloc_batch(c, cat_n, scratch, true));
-        if (e->out_cap < cat_n) {
-            if (e->out_store.k) free_batch(c, e->out_store);
-            e->out_cap = std::max<int64_t>(2 * cat_n, 8192);
-            TRY(alloc_batch(c, e->out_cap, e->out_store));
-        }
-        res = e->out_store;
-        SortArgs sa{};
-        sa.nb = 1;
-        sa.kin[0] = cat.k; sa.vin[0] = cat.v; sa.win[0] = cat.w;
-        sa.n[0] = cat_n;
-        sa.tk[0] = scratch.k; sa.tv[0] = scratch.v; sa.tw[0] = scratch.w;
-        sa.ok[0] = res.k; sa.ov[0] = res.v; sa.ow[0] = res.w;
-        sa.d_len = c->d_len + 6;
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-        HIP_CHECK_ST(hipMemcpyAsync(c->h_len + 6, c->d_len + 6,
-                                    sizeof(int64_t), hipMemcpyDeviceToHost,
-                                    c->stream));
-    }
+    bool async_final = false;
+    TRY(final_begin(e, outs, !sharding_on(c), async_final));
     if (!sharding_on(c)) {
         std::function<dbsp_status()> hook = [&]() -> dbsp_status {
             if (!e->next_ev || e->next_n < 0 || !e->d_wm) return DBSP_OK;
-            const size_t save_base = c->arena_base, save_off = c->arena_off;
-            c->arena_base =
-                c->arena_half ? (save_base ? 0 : c->arena_half) : save_base;
-            c->arena_off = 0;
-            const int64_t ncap = e->next_n > 0 ? e->next_n : 1;
-            dbsp_status st = alloc_batch(c, ncap, e->front.rawA, true);
-            if (st == DBSP_OK) st = alloc_batch(c, ncap, e->front.rawB, true);
-            dbspk::EventCols fcols{};
-            const bool fhc = staged_cols(e, e->next_ev, fcols);
-            if (st == DBSP_OK)
-                st = dbspk::flatmap_events_chain(
-                    c->stream, e->next_ev, fhc ? &fcols : nullptr, e->next_n,
-                    e->query, e->front.rawA.k, e->front.rawA.v,
-                    e->front.rawA.w, e->front.rawB.k, e->front.rawB.v,
-                    e->front.rawB.w, (uint64_t *)(c->d_len + 8));
-            if (st == DBSP_OK)
-                st = dbspk::minmax_rows_chain(
-                    c->stream, e->front.rawA.k, e->front.rawA.v, ncap,
-                    c->d_len + 8, (unsigned long long *)(c->d_len + 12));
-            e->front.arena_base = c->arena_base;
-            e->front.arena_off = c->arena_off;
-            c->arena_base = save_base;
-            c->arena_off = save_off;
-            if (st == DBSP_OK) {
-                e->front.pending = true;
-                e->front.ev = e->next_ev;
-                e->front.n = e->next_n;
-                e->front.oA = DevBatch{};
-                e->front.oB = DevBatch{};
-            }
-            return st;
+            return enqueue_front(e, [&] {
+                e->front.oA = e->front.oB = DevBatch{};
+                return q5_front(e, e->next_ev, e->next_n, e->front.rawA,
+                                e->front.rawB);
+            });
         };
         Spine *sps[3] = {&e->bc_int, &e->counts_int, &e->bt_int};
         DevBatch bs[3] = {dBC, dCounts, dBT};
@@ -4011,139 +3711,7 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         TRY(e->bc_int.insert(c, dBC));
         TRY(e->counts_int.insert(c, dCounts));
     }
-    if (async_final) {
-        res.n = c->h_len[6];
-        e->output = res;
-        e->output_is_store = true;
-    } else {
-        TRY(finalize_raw(c, outs, e->output));
-    }
-    return DBSP_OK;
-}
-
-// ---------------------------------------------------------------------------
-// q4 (queries/q4.rs): average winning-bid price per category.
-//   auctions ⋈ bids on auction id with the bid-validity window applied in
-//   the join_func (q4.rs:58-68; filtered pairs emit weight 0) →
-//   Max per (auction, category) over the consolidated integral
-//   (aggregate(Max), max.rs:36-55) with upsert retractions →
-//   Average per category as ONE linear aggregate over the packed value
-//   (sum<<20)+count (price < 2^20, per-category count < 2^20, so the packed
-//   i64 weight sum is exact), divided at the output map (average.rs).
-// Explicit per-op path (no chained speculation yet — q4 is not a headline
-// config; correctness and coverage first).
-// ---------------------------------------------------------------------------
-
-static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
-    dbsp_ctx *c = e->ctx;
-    engine_free_output(e);
-    DevBatch dA, dB;  // auction / bid deltas, keyed by auction id
-    TRY(build_deltas(e, d_ev, n, dA, dB, true));
-    // bilinear expansion against PREVIOUS traces:
-    //   dB ⋈ A_prev + dA ⋈ B_prev + dA ⋈ dB   (join.rs:217-292)
-    std::vector<DevBatch> outs;
-    TRY(join_vs_spine(c, dB, e->q4_a_int, DBSP_PROJ_Q4_BID_X_AUC, 0, outs));
-    TRY(join_vs_spine(c, dA, e->q4_b_int, DBSP_PROJ_Q4_AUC_X_BID, 0, outs));
-    if (dA.n > 0 && dB.n > 0) {
-        TraceArgs t{};
-        t.nb = 1;
-        t.k[0] = dB.k; t.v[0] = dB.v; t.w[0] = dB.w; t.n[0] = dB.n;
-        DevBatch o;
-        ScopedTimer timer(c, 2, (double)dA.n * 24.0);
-        TRY(dbspk::join_spine_rows(c->stream, dA.k, dA.v, dA.w, dA.n, t,
-                                   DBSP_PROJ_Q4_AUC_X_BID, 0, &o.k, &o.v,
-                                   &o.w, &o.n));
-        if (o.n > 0) outs.push_back(o);
-        else free_batch(c, o);
-    }
-    DevBatch dWinIn;
-    TRY(finalize_raw(c, outs, dWinIn));
-    DevBatch dWin{};
-    if (dWinIn.n > 0) {
-        // max input lives in a SPINE (amortized log maintenance); the Max
-        // aggregator re-reads only the AFFECTED keys' value runs each tick —
-        // the reference's eval_key discipline (aggregate/mod.rs:479-547) —
-        // by gathering them with a unit-weight key join over the spine
-        // (weights multiply by 1, so the gather carries the trace weights)
-        // and consolidating just that slice before the max scan
-        // (max.rs:36-55 needs per-val TOTAL weights)
-        {
-            DevBatch cpy;
-            TRY(copy_batch(c, dWinIn, cpy));
-            TRY(e->q4_maxin_sp.insert(c, cpy));
-        }
-        uint64_t *keys = nullptr;
-        int64_t nk = 0;
-        TRY(dbspk::unique_keys(c->stream, dWinIn.k, dWinIn.n, &keys, &nk));
-        DevBatch kb;
-        TRY(alloc_batch(c, nk, kb, true));
-        HIP_CHECK_ST(hipMemcpyAsync(kb.k, keys, nk * 8,
-                                    hipMemcpyDeviceToDevice, c->stream));
-        HIP_CHECK_ST(hipMemsetAsync(kb.v, 0, nk * 8, c->stream));
-        dbspk::fill_u64(c->stream, (uint64_t *)kb.w, 1, nk);
-        kb.n = nk;
-        std::vector<DevBatch> gouts;
-        TRY(join_vs_spine(c, kb, e->q4_maxin_sp, DBSP_PROJ_HI_K_LO_V2, 0,
-                          gouts));
-        DevBatch gathered;
-        TRY(finalize_raw(c, gouts, gathered));
-        DevBatch raw;
-        {
-            ScopedTimer timer(c, 3, 0.0);
-            TRY(dbspk::agg_max_upsert_rows(
-                c->stream, keys, nk, gathered.k, gathered.v, gathered.w,
-                gathered.n, e->q4_maxout.k, e->q4_maxout.v, e->q4_maxout.w,
-                e->q4_maxout.n, &raw.k, &raw.v, &raw.w, &raw.n));
-        }
-        free_batch(c, gathered);
-        HIP_CHECK_ST(dbspk::cache_free(keys, c->stream));
-        TRY(sort_consolidate_batch(c, raw, dWin));
-        if (dWin.n > 0) {
-            DevBatch cpy, m;
-            TRY(copy_batch(c, dWin, cpy));
-            TRY(merge_batches(c, e->q4_maxout, cpy, m));
-            free_batch(c, e->q4_maxout);
-            free_batch(c, cpy);
-            e->q4_maxout = m;
-        }
-    }
-    free_batch(c, dWinIn);
-    // average per category: weigh into the packed (sum<<20)+count weight,
-    // aggregate linearly over the integral spine, upsert, divide at output
-    if (dWin.n > 0) {
-        DevBatch wraw, dAvgIn;
-        TRY(alloc_batch(c, dWin.n, wraw, true));
-        TRY(dbspk::map_rows(c->stream, dWin.k, dWin.v, dWin.w, dWin.n, 5,
-                            wraw.k, wraw.v, wraw.w));
-        wraw.n = dWin.n;
-        TRY(sort_consolidate_batch(c, wraw, dAvgIn));
-        free_batch(c, dWin);
-        if (dAvgIn.n > 0) {
-            DevBatch cpy;
-            TRY(copy_batch(c, dAvgIn, cpy));
-            TRY(e->q4_avg_int.insert(c, cpy));
-            DevBatch upd;
-            TRY(agg_linear_spine(c, dAvgIn, e->q4_avg_int, e->q4_avgout,
-                                 upd));
-            free_batch(c, dAvgIn);
-            if (upd.n > 0) {
-                DevBatch cpy2;
-                TRY(copy_batch(c, upd, cpy2));
-                TRY(e->q4_avgout.insert(c, cpy2));
-                // output: divide the packed sums (two packed values can map
-                // to one average, so consolidate after the map)
-                TRY(map_sorted(c, upd, 6, e->output));
-            }
-            free_batch(c, upd);
-        }
-    } else {
-        free_batch(c, dWin);
-    }
-    // TraceAppend both input deltas
-    TRY(e->q4_a_int.insert(c, dA));
-    TRY(e->q4_b_int.insert(c, dB));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    return DBSP_OK;
+    return final_finish(e, outs, async_final);
 }
 
 // affected-key gather + keyed aggregate + upsert over a spine: the
@@ -4201,11 +3769,85 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
 }
 
 // ---------------------------------------------------------------------------
+// q4 (queries/q4.rs): average winning-bid price per category.
+//   auctions ⋈ bids on auction id with the bid-validity window applied in
+//   the join_func (q4.rs:58-68; filtered pairs emit weight 0) →
+//   Max per (auction, category) over the consolidated integral
+//   (aggregate(Max), max.rs:36-55) with upsert retractions →
+//   Average per category as ONE linear aggregate over the packed value
+//   (sum<<20)+count (price < 2^20, per-category count < 2^20, so the packed
+//   i64 weight sum is exact), divided at the output map (average.rs).
+// Explicit per-op path (no chained speculation yet — q4 is not a headline
+// config; correctness and coverage first).
+// ---------------------------------------------------------------------------
+
+static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
+    dbsp_ctx *c = e->ctx;
+    engine_free_output(e);
+    DevBatch dA, dB;  // auction / bid deltas, keyed by auction id
+    TRY(build_deltas(e, d_ev, n, dA, dB, true));
+    // bilinear expansion against PREVIOUS traces:
+    //   dB ⋈ A_prev + dA ⋈ B_prev + dA ⋈ dB   (join.rs:217-292)
+    std::vector<DevBatch> outs;
+    TRY(join_vs_spine(c, dB, e->q4_a_int, DBSP_PROJ_Q4_BID_X_AUC, 0, outs));
+    TRY(join_vs_spine(c, dA, e->q4_b_int, DBSP_PROJ_Q4_AUC_X_BID, 0, outs));
+    TRY(join_vs_batch(c, dA, dB, DBSP_PROJ_Q4_AUC_X_BID, 0, outs));
+    DevBatch dWinIn;
+    TRY(finalize_raw(c, outs, dWinIn));
+    DevBatch dWin{};
+    if (dWinIn.n > 0) {
+        // max input lives in a SPINE (amortized log maintenance); the Max
+        // aggregator re-reads only the AFFECTED keys' value runs each tick
+        DevBatch cpy;
+        TRY(copy_batch(c, dWinIn, cpy));
+        TRY(e->q4_maxin_sp.insert(c, cpy));
+        TRY(agg_keyed_spine(e, dWinIn, e->q4_maxin_sp, e->q4_maxout, 1, dWin));
+    }
+    free_batch(c, dWinIn);
+    // average per category: weigh into the packed (sum<<20)+count weight,
+    // aggregate linearly over the integral spine, upsert, divide at output
+    if (dWin.n > 0) {
+        DevBatch wraw, dAvgIn;
+        TRY(alloc_batch(c, dWin.n, wraw, true));
+        TRY(dbspk::map_rows(c->stream, dWin.k, dWin.v, dWin.w, dWin.n, 5,
+                            wraw.k, wraw.v, wraw.w));
+        wraw.n = dWin.n;
+        TRY(sort_consolidate_batch(c, wraw, dAvgIn));
+        free_batch(c, dWin);
+        if (dAvgIn.n > 0) {
+            DevBatch cpy;
+            TRY(copy_batch(c, dAvgIn, cpy));
+            TRY(e->q4_avg_int.insert(c, cpy));
+            DevBatch upd;
+            TRY(agg_linear_spine(c, dAvgIn, e->q4_avg_int, e->q4_avgout,
+                                 upd));
+            free_batch(c, dAvgIn);
+            if (upd.n > 0) {
+                DevBatch cpy2;
+                TRY(copy_batch(c, upd, cpy2));
+                TRY(e->q4_avgout.insert(c, cpy2));
+                // output: divide the packed sums (two packed values can map
+                // to one average, so consolidate after the map)
+                TRY(map_sorted(c, upd, 6, e->output));
+            }
+            free_batch(c, upd);
+        }
+    } else {
+        free_batch(c, dWin);
+    }
+    // TraceAppend both input deltas
+    TRY(e->q4_a_int.insert(c, dA));
+    TRY(e->q4_b_int.insert(c, dB));
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return DBSP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // q6 (queries/q6.rs): average winning-bid price of the last 10 closed
 // auctions per seller.  Same join shape as q4 on (auction, seller), Max per
 // (auction<<20|seller), then the VecDeque fold (q6.rs:96-110) as the MODE-2
 // last-10 average over the seller-keyed integral whose vals
-// (auction<<20)|price keep the reference's cursor order by auction id.
+// (auction<<27)|price keep the reference's cursor order by auction id.
 // ---------------------------------------------------------------------------
 
 static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
@@ -4216,18 +3858,7 @@ static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     std::vector<DevBatch> outs;
     TRY(join_vs_spine(c, dB, e->q6_a_int, DBSP_PROJ_Q6_BID_X_AUC, 0, outs));
     TRY(join_vs_spine(c, dA, e->q6_b_int, DBSP_PROJ_Q6_AUC_X_BID, 0, outs));
-    if (dA.n > 0 && dB.n > 0) {
-        TraceArgs t{};
-        t.nb = 1;
-        t.k[0] = dB.k; t.v[0] = dB.v; t.w[0] = dB.w; t.n[0] = dB.n;
-        DevBatch o;
-        ScopedTimer timer(c, 2, (double)dA.n * 24.0);
-        TRY(dbspk::join_spine_rows(c->stream, dA.k, dA.v, dA.w, dA.n, t,
-                                   DBSP_PROJ_Q6_AUC_X_BID, 0, &o.k, &o.v,
-                                   &o.w, &o.n));
-        if (o.n > 0) outs.push_back(o);
-        else free_batch(c, o);
-    }
+    TRY(join_vs_batch(c, dA, dB, DBSP_PROJ_Q6_AUC_X_BID, 0, outs));
     DevBatch dWinIn;
     TRY(finalize_raw(c, outs, dWinIn));
     DevBatch dWin{};
@@ -4239,7 +3870,7 @@ static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     }
     free_batch(c, dWinIn);
     if (dWin.n > 0) {
-        // map_index (q6.rs:92-94): key by seller, val (auction<<20)|price
+        // map_index (q6.rs:92-94): key by seller, val (auction<<27)|price
         DevBatch fraw, dFoldIn;
         TRY(alloc_batch(c, dWin.n, fraw, true));
         TRY(dbspk::map_rows(c->stream, dWin.k, dWin.v, dWin.w, dWin.n, 7,

@@ -2362,7 +2362,7 @@ __global__ void k_agg_emit(const uint64_t *keys, int64_t nd,
             } else if (MODE == 2) {
                 // q6.rs:96-110: the VecDeque fold keeps the last <= 10 vals
                 // of the seller's cursor-ordered run; avg of their prices
-                // (val low 20 bits), integer division
+                // (val = (auction<<27)|price: low 27 bits), integer division
                 const uint64_t ihi = newval[i], ilo = istart[i];
                 const uint64_t n10 =
                     ihi - ilo < 10 ? ihi - ilo : (uint64_t)10;

@@ -125,9 +125,6 @@ dbsp_status merge_rows(hipStream_t s, const uint64_t *ak, const uint64_t *av,
                        uint64_t **ok, uint64_t **ov, int64_t **ow,
                        int64_t *out_n);
 
-// fused single-workgroup sort+consolidate batch descriptors: up to 4
-// independent small (n <= 8192) raw batches sorted+consolidated concurrently,
-// one workgroup each, lengths left in d_len[i] (device)
 dbsp_status wm_update(hipStream_t s, const uint64_t *ak, const int64_t *n_dev,
                       uint64_t width, uint64_t tumble, uint64_t lag,
                       unsigned long long *state, unsigned long long *bounds);
@@ -202,6 +199,9 @@ dbsp_status frames_unpack_pair(hipStream_t s, const uint64_t *frame,
                                uint64_t *r0k, uint64_t *r0v, int64_t *r0w,
                                uint64_t *r1k, uint64_t *r1v, int64_t *r1w,
                                int64_t *d_tot0, int64_t *d_tot1);
+// fused single-workgroup sort+consolidate: up to SORT_BATCH_MAX (8)
+// independent small (n <= 8192) raw batches sorted+consolidated concurrently,
+// one workgroup each, lengths left in d_len[i] (device)
 dbsp_status sort_cons_small_batch(hipStream_t s, const SortArgs &args);
 // min/max of k and v (one sync): mm = {kmin, vmin, kmax, vmax}
 dbsp_status minmax_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
@@ -221,8 +221,10 @@ dbsp_status sort_cons_dense_chain(hipStream_t s, const uint64_t *k,
                                   uint64_t *ov, int64_t *ow,
                                   int64_t *out_n_dev);
 
-// single-workgroup merge of two consolidated batches (na+nb <= 8192):
-// one launch, no host sync; length left in *d_len (device)
+// single-workgroup merges of up to MERGE_BATCH_MAX pairs of consolidated
+// batches (each na+nb <= 32768; the spine merges keep it for pairs <= 4096
+// and send larger ones to merge_mid_batch): one launch, no host sync; lengths
+// left in d_len[p] (device)
 dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args);
 // fixed-grid multi-WG merge with optional device-side b lengths (in-train
 // accumulator fold); scratch holds np * (MERGE_MID_SCRATCH) int64 slots

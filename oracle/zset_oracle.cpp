@@ -126,7 +126,7 @@ inline void proj_emit(std::vector<Row> &out, dbsp_proj proj, uint64_t param,
         }
         case DBSP_PROJ_Q6_BID_X_AUC: {
             // q6.rs:60-80: delta = bid (v1 = bid_dt<<27|price), trace =
-            // auction (v2 = a_dt<<34 | (expires-a_dt)<<20 | seller)
+            // auction (v2 = a_dt<<36 | (expires-a_dt)<<20 | seller)
             const uint64_t bid_dt = v1 >> 27, price = v1 & 0x7FFFFFFull;
             const uint64_t a_dt = v2 >> 36, dur = (v2 >> 20) & 0xFFFFull;
             hi = (k << 20) | (v2 & 0xFFFFFull);
@@ -468,7 +468,7 @@ std::vector<Row> q4_step(Oracle &o, const std::vector<dbsp_event> &ev) {
 
 // queries/q6.rs: join -> Max per (auction<<20|seller) -> per-seller average
 // of the last <= 10 winning bids (the VecDeque fold in cursor order,
-// q6.rs:96-110; vals (auction<<20)|price keep that order)
+// q6.rs:96-110; vals (auction<<27)|price keep that order)
 std::vector<Row> q6_step(Oracle &o, const std::vector<dbsp_event> &ev) {
     std::vector<Row> dA, dB;
     for (auto &e : ev) {
