@@ -72,25 +72,29 @@ struct KernelStat {
 //                        aggregate's join count) borrow up to SORT_BATCH_MAX
 //                        slots from the start of tick base 0 (they alias
 //                        that base's first offsets)
-//   [sb, sb + 18)        one chained tick, sb = LEN_BASE0 or LEN_BASE1 (q3's
+//   [sb, sb + LEN_TICK)  one chained tick, sb = LEN_BASE0 or LEN_BASE1 (q3's
 //                        pipelined trains ping-pong; everything else uses
 //                        LEN_BASE0).  Offsets inside a base are the L_* below
+//   [sb + LEN_TICK, sb + LEN_BASE_N)
+//                        HOST only: the landing block of q3's tail readback
+//                        (the LH_* offsets below); no kernel writes the
+//                        device side of it
 //   [LEN_ROUND, +4)      spine-insert merge rounds: their readback can be
-//                        consumed after the next train's 18-slot readback
-//                        has landed, so it cannot live inside a base
-//   the rest up to LEN_SLOTS is unused padding
+//                        consumed after the next train's readbacks have
+//                        landed, so it cannot live inside a base
 enum : int {
-    LEN_SLOTS = 44,
+    LEN_SLOTS = 56,
     LEN_OP = 0,
+    LEN_TICK = 18,       // kernel-written slots of a tick base
+    LEN_BASE_N = 26,     // slots per tick base, host tail block included
     LEN_BASE0 = 0,
-    LEN_BASE1 = 18,
-    LEN_TICK = 18,       // slots per tick base (= the train's one readback)
-    LEN_ROUND = 36,
+    LEN_BASE1 = LEN_BASE_N,
+    LEN_ROUND = 2 * LEN_BASE_N,
     LEN_ROUND_N = MERGE_BATCH_MAX,
     // offsets inside a tick base
     L_PLAN = 0,          // 0..2: q3 join-plan count totals (-1: lost spec)
-    L_EMIT_TOTAL = 3,    // fused emit: combined row total (or -1)
-    L_EMIT_FLAG = 4,     // fused emit: nonzero = capacity overflow
+    L_EMIT_TOTAL = 3,    // join tail: combined row total (or -1)
+    L_EMIT_FLAG = 4,     // join tail: nonzero = capacity overflow
     L_DENSE = 5,         // q5: chained dense-sort length of the bid delta
     L_FINAL = 6,         // output (final) sort length
     L_WIN = 7,           // single-spine window total (q5, window_vs_spine)
@@ -101,25 +105,42 @@ enum : int {
     L_XCHG = 16,         // 16/17: framed-exchange receive totals (-1:
                          // frame overflow); q3's unsharded train reuses them
                          // for its two accumulator-merge lengths
-    // q3's second readback (q3_chain_emits) copies device offsets
-    // [L_EMIT_TOTAL, L_FINAL] to HOST offsets shifted by LH_TAIL_SHIFT, so
-    // the first readback's copies of plan totals and delta lengths stay
-    // intact for the verdict.  Host offsets 12..15 are free in a q3 tick
-    // (L_WIN2 / L_MINMAX belong to q8 / q5).
-    LH_TAIL_SHIFT = 9,
-    LH_TAIL_N = L_FINAL - L_EMIT_TOTAL + 1,
-    LH_EMIT_TOTAL = L_EMIT_TOTAL + LH_TAIL_SHIFT,  // 12
-    LH_EMIT_FLAG = L_EMIT_FLAG + LH_TAIL_SHIFT,    // 13
-    LH_FINAL = L_FINAL + LH_TAIL_SHIFT,            // 15
+    // A chained q3 tick reads back twice.
+    // HEAD: device [L_HEAD, L_HEAD + L_HEAD_N) to the same host offsets.  It
+    // carries what is final once the delta sorts and the accumulator merge
+    // are: L_RAW, L_DELTA and L_XCHG.  The host wakes on it for the
+    // speculation verdict.
+    L_HEAD = L_RAW,
+    L_HEAD_N = LEN_TICK - L_RAW,
+    // TAIL: device [L_PLAN, L_FINAL] — everything the join tail kernel
+    // writes — to HOST offsets shifted by LH_TAIL_SHIFT, into the base's
+    // host-only block.  That block is clear of the head readback's range
+    // and of LEN_OP: ops that sync at once (an overflow replay's sized
+    // sorts) may run between a tail readback landing and its consumption.
+    LH_TAIL_SHIFT = LEN_TICK,
+    LH_TAIL_N = L_FINAL - L_PLAN + 1,
+    LH_PLAN = L_PLAN + LH_TAIL_SHIFT,              // 18..20
+    LH_EMIT_TOTAL = L_EMIT_TOTAL + LH_TAIL_SHIFT,  // 21
+    LH_EMIT_FLAG = L_EMIT_FLAG + LH_TAIL_SHIFT,    // 22
+    LH_FINAL = L_FINAL + LH_TAIL_SHIFT,            // 24
 };
-static_assert(LEN_BASE1 + LEN_TICK <= LEN_ROUND &&
+static_assert(LEN_BASE1 + LEN_BASE_N <= LEN_ROUND &&
                   LEN_ROUND + LEN_ROUND_N <= LEN_SLOTS,
               "both tick bases and the round slots fit the allocation");
-static_assert(LEN_BASE0 + LEN_TICK <= LEN_BASE1, "tick bases overlap");
-static_assert(LH_EMIT_TOTAL > L_DELTA + 1 &&
-                  LH_EMIT_TOTAL + LH_TAIL_N <= L_XCHG,
-              "second-readback host range stays inside its base, clear of "
-              "the slots the verdict still reads");
+static_assert(LEN_BASE0 + LEN_BASE_N <= LEN_BASE1, "tick bases overlap");
+static_assert(L_PLAN + 3 <= L_EMIT_TOTAL && L_EMIT_TOTAL < L_EMIT_FLAG &&
+                  L_EMIT_FLAG < L_FINAL && L_FINAL < L_HEAD,
+              "the tail readback's device range holds the join tail's "
+              "outputs and nothing of the head");
+static_assert(L_HEAD <= L_RAW && L_HEAD <= L_DELTA &&
+                  L_DELTA + 2 <= L_HEAD + L_HEAD_N &&
+                  L_XCHG + 2 <= L_HEAD + L_HEAD_N &&
+                  L_HEAD + L_HEAD_N <= LEN_TICK,
+              "the head readback carries raw, delta and merge lengths");
+static_assert(LH_PLAN >= LEN_TICK && LH_PLAN >= LEN_OP + SORT_BATCH_MAX &&
+                  LH_PLAN + LH_TAIL_N <= LEN_BASE_N,
+              "tail-readback host range stays inside its base, clear of "
+              "the head readback and the op scratch");
 static_assert(LEN_OP + SORT_BATCH_MAX <= LEN_TICK, "op scratch inside base 0");
 
 struct dbsp_ctx {
@@ -152,6 +173,14 @@ struct dbsp_ctx {
     hipEvent_t ev_sync2 = nullptr;  // early-wake event (post-count readback)
     hipEvent_t ev_tick[2] = {nullptr, nullptr};  // pipelined-train events
     hipEvent_t ev_tail[2] = {nullptr, nullptr};  // train tail (post 2nd readback)
+    // q3 train fork: the accumulator merge and the head readback run on a
+    // side stream behind ev_fork (recorded on the main stream after the delta
+    // sorts); ev_tick, recorded on the side stream, is what the main stream
+    // joins on before the tail readback.  q3_fork is off under DBSP_PROFILE
+    // (ScopedTimer's events assume one stream) and with DBSP_Q3_FORK=0.
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork[2] = {nullptr, nullptr};
+    bool q3_fork = false;
     // deferred spine-insert round (train path): the last small-merge round's
     // length readback is resolved at the NEXT insert/step on a near-empty
     // stream instead of blocking behind the next tick's freshly enqueued
@@ -166,12 +195,15 @@ struct dbsp_ctx {
 
 // Length readback: copy `count` device slots from `first` to host slots from
 // `host_first`; with sync, wait for them.  Every read of h_len follows one.
+// `s`: the stream to copy on (null = the main stream).
 static dbsp_status read_len_to(dbsp_ctx *c, int host_first, int first,
-                               int count, bool sync) {
+                               int count, bool sync,
+                               hipStream_t s = nullptr) {
+    if (!s) s = c->stream;
     HIP_CHECK_ST(hipMemcpyAsync(c->h_len + host_first, c->d_len + first,
                                 count * sizeof(int64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    if (sync) HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+                                hipMemcpyDeviceToHost, s));
+    if (sync) HIP_CHECK_ST(hipStreamSynchronize(s));
     return DBSP_OK;
 }
 static inline dbsp_status read_len(dbsp_ctx *c, int first, int count,
@@ -242,10 +274,15 @@ extern "C" dbsp_status dbsp_ctx_create(dbsp_ctx **out, int device) {
     HIP_CHECK_ST(hipEventCreateWithFlags(&c->ev_insert, hipEventDisableTiming));
     HIP_CHECK_ST(hipEventCreateWithFlags(&c->ev_tail[0], hipEventDisableTiming));
     HIP_CHECK_ST(hipEventCreateWithFlags(&c->ev_tail[1], hipEventDisableTiming));
+    HIP_CHECK_ST(hipStreamCreate(&c->side));
+    HIP_CHECK_ST(hipEventCreateWithFlags(&c->ev_fork[0], hipEventDisableTiming));
+    HIP_CHECK_ST(hipEventCreateWithFlags(&c->ev_fork[1], hipEventDisableTiming));
     const char *p = getenv("DBSP_PROFILE");
     c->profile = p && p[0] == '1';
     const char *fs = getenv("DBSP_FORCE_SHARD");
     c->force_shard = fs && fs[0] == '1';
+    const char *fk = getenv("DBSP_Q3_FORK");
+    c->q3_fork = !c->profile && !(fk && fk[0] == '0');
     HIP_CHECK_ST(hipMalloc(&c->d_len, LEN_SLOTS * sizeof(int64_t)));
     HIP_CHECK_ST(hipMalloc(&c->d_mid, MERGE_BATCH_MAX * MERGE_MID_SCRATCH *
                                           sizeof(int64_t)));
@@ -274,6 +311,12 @@ extern "C" dbsp_status dbsp_ctx_destroy(dbsp_ctx *c) {
     if (c->ev_tick[1]) (void)hipEventDestroy(c->ev_tick[1]);
     if (c->comm) ncclCommDestroy(c->comm);
     (void)hipStreamSynchronize(c->stream);
+    if (c->side) {
+        (void)hipStreamSynchronize(c->side);
+        (void)hipStreamDestroy(c->side);
+    }
+    if (c->ev_fork[0]) (void)hipEventDestroy(c->ev_fork[0]);
+    if (c->ev_fork[1]) (void)hipEventDestroy(c->ev_fork[1]);
     if (c->d_len) (void)hipFree(c->d_len);
     if (c->d_mid) (void)hipFree(c->d_mid);
     dbspk::cache_trim(c->stream);
@@ -1210,6 +1253,7 @@ struct Q3Plan {
     TraceArgs t;
     int proj;
     uint32_t *cnts;
+    int64_t *starts;  // chained ticks only: the probe's run start positions
     uint64_t *offsets;
     bool small;
     bool dd;  // delta-vs-delta plan (trace length is tick-fresh)
@@ -2642,40 +2686,72 @@ extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
 // Single-rank ticks run almost entirely as ONE chained launch train with
 // device-side lengths:
 //   flatmap -> fused delta sorts (speculative, -1 sentinel over 8192 rows)
-//   -> 3-plan join count/scan -> per-plan emit bases -> chained emits into a
-//   capacity buffer -> fused output consolidate into the reused store.
-// The host wakes at an EVENT recorded right after the count totals + delta
-// lengths copy — while the GPU still runs the emits and the output sort —
-// checks the speculation, and immediately queues the spine inserts (whose
+//   -> 3-plan join probe (counts and run start positions per delta row and
+//   spine batch) -> join tail, one single-workgroup kernel: scan of the
+//   counts, capacity check, emit into a capacity buffer, output consolidate
+//   into the reused store.
+// A chained tick reads lengths back twice.  The HEAD readback (raw and delta
+// lengths, and on trains the accumulator-merge lengths) is final once the
+// delta sorts are; the host wakes at an EVENT recorded right after it —
+// while the GPU still runs the probe and the tail — checks the speculation
+// from the delta lengths, and immediately queues the spine inserts (whose
 // first wait doubles as the pipelining point launching the NEXT tick's
-// front).  Emit overflow (combined output beyond the capacity buffer) and
-// output overflow (beyond the fused sort) are detected after the inserts
-// from the second readback and replayed explicitly; a lost sort speculation
+// front).  The TAIL readback (plan totals, emit total / overflow flag,
+// output length) is consumed after the inserts.  Emit overflow (combined
+// output beyond the capacity buffer) and output overflow (beyond the fused
+// sort) are detected there and replayed explicitly from the tail kernel's
+// offsets and totals; a plan total that is negative although the delta
+// lengths passed is re-counted by that replay.  A lost sort speculation
 // re-sorts through the sized paths.  Sharded ranks keep the explicit path
 // (the exchange needs host lengths).
 //
-// Pipelined TRAINS (round 2): for run_staged loops the ENTIRE next tick's
-// launch train (flatmap -> speculative fused sorts -> 3-plan join count ->
-// emit bases -> chained emits -> output consolidate, plus both readbacks and
-// an event record) is enqueued at the END of the current step, right after
-// the spine inserts commit — at that point the post-insert spine state the
-// next tick's probes must read is final, so the train's TraceArgs are
-// correct by construction.  The next step then only WAITS on the train's
-// event and runs verdicts + inserts: the ~90 us of per-tick host enqueue
-// work (the round-1 trace showed 53 us gaps before the join probes and
-// 63 us before the insert merges — fat-kernarg hipLaunchKernel time, not
-// sync latency) overlaps the previous train's GPU execution.  Trains
-// ping-pong the length-slot bases (LEN_BASE0 / LEN_BASE1), the tick events
-// and the arena halves; the spine-insert rounds use the LEN_ROUND slots.
+// Pipelined TRAINS: for run_staged loops the ENTIRE next tick's launch train
+// is enqueued at the END of the current step, right after the spine inserts
+// commit — at that point the post-insert spine state the next tick's probes
+// must read is final, so the train's TraceArgs are correct by construction.
+// The next step then only WAITS on the train's events and runs verdicts +
+// the accumulator swap, so the per-tick host enqueue work overlaps the
+// previous train's GPU execution.  Trains ping-pong the length-slot bases
+// (LEN_BASE0 / LEN_BASE1), the events and the arena halves; the
+// spine-insert rounds use the LEN_ROUND slots.
+//
+// Inside a train the accumulator merge (this tick's deltas folded into the
+// per-spine memtable) is off the critical path: nothing in the tick reads
+// its result — the probes read the pre-insert spines — so it FORKS to a side
+// stream:
+//   main: flatmap -> delta sorts -> record ev_fork
+//   side: wait ev_fork -> accumulator merge -> head readback -> record ev_tick
+//   main: probe -> join tail -> wait ev_tick -> tail readback -> record ev_tail
+// Ordering argument (what buffer recycling and slot reuse rest on):
+//  1. The main stream joins the side stream (wait ev_tick, the side
+//     stream's last event of the train) before the train's last main-stream
+//     operation.  So everything train t launched, on either stream, is
+//     complete before anything enqueued on the main stream after train t:
+//     commit-side frees and allocations, spill rounds, replays, train t+1.
+//     A train that bails after forking joins before it unwinds.
+//  2. The side stream runs train work only, and train t+1's side work waits
+//     ev_fork(t+1), which the main stream records after train t's join.  So
+//     side work of t+1 follows all of train t and everything the commit of
+//     tick t enqueued on the main stream before the enqueue of train t+1.
+//  3. Hence any two users of a recycled buffer, of a length slot or of the
+//     merge scratch d_mid are ordered exactly as they were on one stream.
+//     d_mid in particular: the spill rounds of commit t are main-stream work
+//     enqueued before ev_fork(t+1) (rule 2) and after the join of train t
+//     (rule 1), so they never overlap a side merge.
+// Under DBSP_PROFILE (ScopedTimer's events assume one stream) and with
+// DBSP_Q3_FORK=0 the side work stays on the main stream, in the same order.
+//
 // Per-tick stepping (no next_ev), sharded ranks, oversized ticks and lost
-// speculations all run the unpipelined body below, which is the round-1
-// path unchanged.
+// speculations all run the unpipelined body below: the same probe and join
+// tail in order on the main stream when chained, the explicit path otherwise.
 
 static constexpr int64_t Q3_EMIT_CAP = 32768;
 
 // Build the three bilinear join plans against the CURRENT spines (callers
 // guarantee the spine state is the one tick t's probes must read) and
-// enqueue count(+scan).  spec: delta lengths still on device (L_DELTA of sb).
+// enqueue the probe (spec: delta lengths still on device, L_DELTA of sb; the
+// probe keeps the start positions for the join tail) or count+scan (host
+// lengths).
 static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
                                  bool spec, int sb, int64_t n_cap,
                                  Q3Plan plans[3], int &np, int &jca_np,
@@ -2686,15 +2762,15 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     const bool haveA = spec || dA.n > 0, haveP = spec || dP.n > 0;
     if (haveA && !e->p_int.batches.empty())
         plans[np++] = {0, trace_args_of(e->p_int), DBSP_PROJ_HI_V2_LO_V1,
-                       nullptr, nullptr, false, false, -1};
+                       nullptr, nullptr, nullptr, false, false, -1};
     if (haveP && !e->a_int.batches.empty())
         plans[np++] = {1, trace_args_of(e->a_int), DBSP_PROJ_HI_V1_LO_V2,
-                       nullptr, nullptr, false, false, -1};
+                       nullptr, nullptr, nullptr, false, false, -1};
     if (haveA && haveP) {
         TraceArgs t = trace_args_one(dP);
         if (spec) t.n[0] = 0;  // read from the device (tn_dev below)
-        plans[np++] = {0, t, DBSP_PROJ_HI_V2_LO_V1, nullptr, nullptr, false,
-                       true, -1};
+        plans[np++] = {0, t, DBSP_PROJ_HI_V2_LO_V1, nullptr, nullptr, nullptr,
+                       false, true, -1};
     }
     JoinCountArgs jca{};
     for (int i = 0; i < np; i++) {
@@ -2705,7 +2781,11 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
         const int64_t nd_cap = spec ? n_cap : d.n;
         pl.cnts = (uint32_t *)arena_alloc(c, (size_t)nd_cap * pl.t.nb * 4 + 8);
         pl.offsets = (uint64_t *)arena_alloc(c, (size_t)(nd_cap + 1) * 8);
-        const bool bufs = pl.cnts && pl.offsets;
+        pl.starts = nullptr;
+        if (spec)
+            pl.starts =
+                (int64_t *)arena_alloc(c, (size_t)nd_cap * pl.t.nb * 8 + 8);
+        const bool bufs = pl.cnts && pl.offsets && (!spec || pl.starts);
         if (spec && !bufs) {
             arena_ok = false;
             break;
@@ -2719,6 +2799,7 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
             if (spec && pl.dd) jca.tn_dev[jca.np] = c->d_len + sb + L_DELTA + 1;
             jca.t[jca.np] = pl.t;
             jca.cnts[jca.np] = pl.cnts;
+            jca.starts[jca.np] = pl.starts;
             jca.offsets[jca.np] = pl.offsets;
             jca.np++;
         }
@@ -2726,66 +2807,72 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     jca_np = jca.np;
     if (arena_ok) {
         jca.d_total = c->d_len + sb + L_PLAN;
-        if (jca.np > 0) TRY(dbspk::join_count_scan_batch(c->stream, jca));
+        // a chained tick only probes here: its join tail scans the counts
+        if (jca.np > 0 && spec) TRY(dbspk::join_probe_batch(c->stream, jca));
+        if (jca.np > 0 && !spec)
+            TRY(dbspk::join_count_scan_batch(c->stream, jca));
     }
     return DBSP_OK;
 }
 
-// chained emits + output consolidate behind the device-side totals; the
-// verdicts (emit total / overflow flag / output length) land in base sb's
-// host LH_* slots via the second readback
-static dbsp_status q3_chain_emits(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
-                                  Q3Plan plans[3], int np, int sb,
-                                  DevBatch &comb_chain, bool &ok) {
+// the join tail behind a chained probe: scan + emit into a capacity buffer +
+// output consolidate into the reused store, one launch.  Kernel only — the
+// caller queues the tail readback (q3_read_tail) once whatever else that
+// readback must follow is in the stream.  ok=false: arena exhausted, nothing
+// was launched.
+static dbsp_status q3_chain_tail(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
+                                 Q3Plan plans[3], int np, int sb,
+                                 DevBatch &comb_chain, bool &ok) {
     dbsp_ctx *c = e->ctx;
     ok = false;
-    int jca_np = 0;
-    for (int i = 0; i < np; i++)
-        if (plans[i].slot >= 0) jca_np = std::max(jca_np, plans[i].slot + 1);
     DevBatch scr;
     if (alloc_batch(c, Q3_EMIT_CAP, comb_chain, true) != DBSP_OK ||
-        alloc_batch(c, Q3_EMIT_CAP, scr, true) != DBSP_OK)
+        alloc_batch(c, 8192, scr, true) != DBSP_OK)
         return DBSP_OK;  // arena exhausted: caller keeps the explicit path
-    FusedEmitArgs fa{};
-    fa.np = jca_np;
+    if (!e->out_store.k) {
+        e->out_cap = 8192;
+        TRY(alloc_batch(c, e->out_cap, e->out_store));
+    }
+    JoinTailArgs ta{};
     for (int i = 0; i < np; i++) {
         Q3Plan &pl = plans[i];
         if (pl.slot < 0) continue;
         DevBatch &d = pl.which == 0 ? dA : dP;
         const int s2 = pl.slot;
-        fa.dk[s2] = d.k;
-        fa.dv[s2] = d.v;
-        fa.dw[s2] = d.w;
-        fa.nd_dev[s2] = c->d_len + sb + L_DELTA + pl.which;
-        fa.t[s2] = pl.t;
-        fa.tn_dev[s2] = pl.dd ? c->d_len + sb + L_DELTA + 1 : nullptr;
-        fa.cnts[s2] = pl.cnts;
-        fa.offsets[s2] = pl.offsets;
-        fa.proj[s2] = pl.proj;
+        ta.np = std::max(ta.np, s2 + 1);
+        ta.dk[s2] = d.k;
+        ta.dv[s2] = d.v;
+        ta.dw[s2] = d.w;
+        ta.nd_dev[s2] = c->d_len + sb + L_DELTA + pl.which;
+        ta.t[s2] = pl.t;
+        ta.tn_dev[s2] = pl.dd ? c->d_len + sb + L_DELTA + 1 : nullptr;
+        ta.cnts[s2] = pl.cnts;
+        ta.starts[s2] = pl.starts;
+        ta.offsets[s2] = pl.offsets;
+        ta.proj[s2] = pl.proj;
     }
-    fa.totals = c->d_len + sb + L_PLAN;
-    fa.cap = Q3_EMIT_CAP;
-    fa.d_total = c->d_len + sb + L_EMIT_TOTAL;
-    fa.d_flag = c->d_len + sb + L_EMIT_FLAG;
-    fa.ok = comb_chain.k;
-    fa.ov = comb_chain.v;
-    fa.ow = comb_chain.w;
-    TRY(dbspk::join_emit_fused(c->stream, fa));
-    if (!e->out_store.k) {
-        e->out_cap = 8192;
-        TRY(alloc_batch(c, e->out_cap, e->out_store));
-    }
-    SortArgs sa{};
-    sa.nb = 1;
-    sort_slot(sa, 0, comb_chain, scr, e->out_store,
-              c->d_len + sb + L_EMIT_TOTAL);
-    sa.d_len = c->d_len + sb + L_FINAL;
-    TRY(dbspk::sort_cons_small_batch(c->stream, sa));
-    // the second readback: device L_EMIT_TOTAL..L_FINAL -> host LH_*
-    TRY(read_len_to(c, sb + LH_EMIT_TOTAL, sb + L_EMIT_TOTAL, LH_TAIL_N,
-                    /*sync=*/false));
+    ta.totals = c->d_len + sb + L_PLAN;
+    ta.cap = Q3_EMIT_CAP;
+    ta.d_total = c->d_len + sb + L_EMIT_TOTAL;
+    ta.d_flag = c->d_len + sb + L_EMIT_FLAG;
+    ta.d_final = c->d_len + sb + L_FINAL;
+    ta.ek = comb_chain.k;
+    ta.ev = comb_chain.v;
+    ta.ew = comb_chain.w;
+    ta.tk = scr.k;
+    ta.tv = scr.v;
+    ta.tw = scr.w;
+    ta.ok = e->out_store.k;
+    ta.ov = e->out_store.v;
+    ta.ow = e->out_store.w;
+    TRY(dbspk::join_tail_small(c->stream, ta));
     ok = true;
     return DBSP_OK;
+}
+// the tail readback: device L_PLAN..L_FINAL of base sb -> host LH_*
+static inline dbsp_status q3_read_tail(dbsp_ctx *c, int sb) {
+    return read_len_to(c, sb + LH_PLAN, sb + L_PLAN, LH_TAIL_N,
+                       /*sync=*/false);
 }
 
 // explicit emits from prepared counts/offsets (the non-chained path and the
@@ -2879,27 +2966,33 @@ static dbsp_status final_finish(dbsp_engine *e, std::vector<DevBatch> &outs,
     return DBSP_OK;
 }
 
-// speculation verdict of a chained q3 tick from its first readback (H = the
-// host slots of its base): a delta overflowed the fused sort, or a plan's
-// count saw a negative length
-static bool q3_spec_lost(const int64_t *H, const Q3Plan *plans, int np) {
-    if (H[L_DELTA] < 0 || H[L_DELTA + 1] < 0) return true;
-    for (int i = 0; i < np; i++)
-        if (plans[i].slot >= 0 && H[L_PLAN + plans[i].slot] < 0) return true;
-    return false;
+// speculation verdict of a chained q3 tick from its head readback (H = the
+// host slots of its base): a delta overflowed the fused sort.  The plan
+// totals are not in yet, and are not needed: a plan's total is negative only
+// if a delta length it read was.
+static bool q3_spec_lost(const int64_t *H) {
+    return H[L_DELTA] < 0 || H[L_DELTA + 1] < 0;
 }
 
-// publish a chained q3 tick's output from its second readback (host LH_*
+// publish a chained q3 tick's output from its tail readback (host LH_*
 // slots of base sb; the caller has waited past it)
 static dbsp_status q3_publish_chained(dbsp_engine *e, int sb, DevBatch &dA,
                                       DevBatch &dP, Q3Plan plans[3], int np,
-                                      const int64_t slot_totals[3],
                                       DevBatch &comb_chain) {
     dbsp_ctx *c = e->ctx;
-    const int64_t *H = c->h_len + sb;
+    int64_t H[LEN_BASE_N];  // the replay's sized ops reuse h_len
+    memcpy(H, c->h_len + sb, sizeof(H));
     if (H[LH_EMIT_FLAG] != 0) {
         // combined emits exceeded the capacity buffer: replay explicitly
-        // from the still-valid counts/offsets
+        // from the tail kernel's counts/offsets/totals.  A plan whose total
+        // came back negative although the delta lengths had passed has no
+        // offsets: it is re-counted from scratch with the host lengths.
+        int64_t slot_totals[3] = {0, 0, 0};
+        for (int i = 0; i < np; i++) {
+            if (plans[i].slot < 0) continue;
+            slot_totals[plans[i].slot] = H[LH_PLAN + plans[i].slot];
+            if (slot_totals[plans[i].slot] < 0) plans[i].small = false;
+        }
         std::vector<DevBatch> outs;
         TRY(q3_emit_explicit(e, dA, dP, plans, np, slot_totals, outs));
         return finalize_raw(c, outs, e->output);
@@ -2937,25 +3030,33 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
             bool arena_ok = true;
             TRY(q3_plan_count(e, dA, dP, spec, LEN_BASE0, n, plans, np, jca_np,
                               arena_ok));
-            // one readback carries the plan totals and the delta lengths;
-            // with chained emits behind it the host wakes at an event
-            // recorded right after the copy instead of a full sync
+            // chained: the head readback carries the delta lengths; the
+            // host wakes at an event recorded right after the copy, with
+            // the join tail and its own readback queued behind it.
+            // Explicit: one synced readback carries the plan totals.
             const bool emits = spec && arena_ok && jca_np > 0;
-            TRY(read_len(c, LEN_BASE0, LEN_TICK, /*sync=*/!emits));
             if (emits) {
+                TRY(read_len(c, LEN_BASE0 + L_HEAD, L_HEAD_N, /*sync=*/false));
                 (void)hipEventRecord(c->ev_sync2, c->stream);
-                TRY(q3_chain_emits(e, dA, dP, plans, np, LEN_BASE0, comb_chain,
-                                   chain_emits));
+                TRY(q3_chain_tail(e, dA, dP, plans, np, LEN_BASE0, comb_chain,
+                                  chain_emits));
+                if (chain_emits) TRY(q3_read_tail(c, LEN_BASE0));
                 (void)hipEventSynchronize(c->ev_sync2);
+            } else {
+                TRY(read_len(c, LEN_BASE0, LEN_TICK));
             }
             for (int i = 0; i < np && i < 3; i++)
                 slot_totals[i] = H[L_PLAN + i];
             if (!spec) break;
-            if (arena_ok && !q3_spec_lost(H, plans, np)) {
+            if (emits && !q3_spec_lost(H)) {
                 dA.n = H[L_DELTA];
                 dP.n = H[L_DELTA + 1];
                 e->spec_fail = 0;
-                break;
+                if (chain_emits) break;
+                // no room for the tail's buffers: nothing scanned the
+                // probe's counts, so count again explicitly, host lengths
+                spec = false;
+                continue;
             }
             // lost: rebuild the deltas with host lengths from the furthest
             // stage that held (received frames, else the raw streams), then
@@ -2988,8 +3089,9 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
     engine_free_output(e);
     // The hook enqueues the NEXT tick's train mid-insert (after this tick's
     // merge launches, before their wait): probing the pre-cascade batch
-    // list is Z-set-identical to the merged state, and single-stream
-    // ordering keeps any recycled buffers safe.  The insert's event sync
+    // list is Z-set-identical to the merged state, and the train's
+    // fork/join ordering (comment above the q3 tick) keeps any recycled
+    // buffers safe.  The insert's event sync
     // (recorded pre-hook) covers this tick's readbacks, so the length reads
     // after it are complete.  Sharded ranks run no trains.
     std::function<dbsp_status()> hook = [&]() -> dbsp_status {
@@ -3001,8 +3103,7 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
     e->q3_acc[0] = e->q3_acc[1] = DevBatch{};
     if (chain_emits) {
         TRY(spines_insert_pair(c, e->a_int, dA, e->p_int, dP, &hook));
-        return q3_publish_chained(e, LEN_BASE0, dA, dP, plans, np, slot_totals,
-                                  comb_chain);
+        return q3_publish_chained(e, LEN_BASE0, dA, dP, plans, np, comb_chain);
     }
     // explicit path (sharded ranks and lost speculations)
     TRY(q3_emit_explicit(e, dA, dP, plans, np, slot_totals, outs));
@@ -3049,11 +3150,15 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         e->q3_acc[0] = DevBatch{};
     }
     // in-train accumulator merge: fold this tick's deltas into the per-spine
-    // memtable (one 2-pair single-WG launch; delta lengths read from the
-    // d_len slots the chain just wrote, so nothing here waits).  The commit
-    // swaps the spine top for the result — or, past the spill threshold,
-    // seals it as a ladder batch.  This removes the host-launched insert
-    // round that left the GPU idle ~45 us at every tick boundary.
+    // memtable (one 2-pair launch; delta lengths read from the d_len slots
+    // the chain just wrote, so nothing here waits).  The commit swaps the
+    // spine top for the result — or, past the spill threshold, seals it as a
+    // ladder batch.  Nothing in this tick reads the result (the probes read
+    // the pre-insert spines), so with the fork on it runs on the side stream
+    // beside the probe and the join tail, followed there by the head
+    // readback the host wakes on.
+    const bool fork = c->q3_fork;
+    hipStream_t ss = fork ? c->side : c->stream;
     {
         MergeArgs ma{};
         for (int s = 0; s < 2; s++) {
@@ -3067,13 +3172,24 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
             ma.np++;
         }
         // result lengths ride in the base's L_XCHG pair (unused on the
-        // unsharded train path) so the train's single LEN_TICK-slot readback
-        // carries them — no extra D2H
+        // unsharded train path), inside the head readback's range
         ma.d_len = c->d_len + sb + L_XCHG;
         ScopedTimer timer(c, 1, (double)(e->q3_acc[0].n + e->q3_acc[1].n +
                                          2 * n) * 48.0);
-        TRY(dbspk::merge_mid_batch(c->stream, ma, c->d_mid));
+        if (fork) {
+            HIP_CHECK_ST(hipEventRecord(c->ev_fork[evi], c->stream));
+            HIP_CHECK_ST(hipStreamWaitEvent(ss, c->ev_fork[evi], 0));
+        }
+        TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid));
     }
+    TRY(read_len_to(c, sb + L_HEAD, sb + L_HEAD, L_HEAD_N, /*sync=*/false, ss));
+    HIP_CHECK_ST(hipEventRecord(c->ev_tick[evi], ss));
+    // from here on a bail must rejoin the side stream first: whatever the
+    // main stream runs next may recycle the buffers the merge is writing
+    auto bail_joined = [&](void) {
+        if (fork) (void)hipStreamWaitEvent(c->stream, c->ev_tick[evi], 0);
+        bail();
+    };
     int jca_np = 0;
     bool arena_ok = true;
     {
@@ -3082,21 +3198,23 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
                           arena_ok));
     }
     if (!arena_ok || jca_np == 0) {
-        bail();
+        bail_joined();
         return DBSP_OK;  // fall back: next step runs the unpipelined body
     }
-    TRY(read_len(c, sb, LEN_TICK, /*sync=*/false));
-    (void)hipEventRecord(c->ev_tick[evi], c->stream);
-    bool emits_ok = false;
-    TRY(q3_chain_emits(e, T.oA, T.oP, T.plans, T.np, sb, T.comb_chain,
-                       emits_ok));
-    if (!emits_ok) {
-        bail();
+    bool tail_ok = false;
+    TRY(q3_chain_tail(e, T.oA, T.oP, T.plans, T.np, sb, T.comb_chain,
+                      tail_ok));
+    if (!tail_ok) {
+        bail_joined();
         return DBSP_OK;
     }
-    // tail barrier: the commit's output-length reads (host LH_* slots) are
-    // written by the emit chain's SECOND readback, which ev_tick does not
-    // cover — the commit waits this event just before consuming them
+    // join: the tail readback and ev_tail follow BOTH streams' work, so
+    // ev_tail — and anything enqueued on the main stream after this train —
+    // is behind everything the train launched on either stream
+    if (fork) HIP_CHECK_ST(hipStreamWaitEvent(c->stream, c->ev_tick[evi], 0));
+    TRY(q3_read_tail(c, sb));
+    // tail barrier: the commit's output-length and plan-total reads (host
+    // LH_* slots) wait this event just before consuming them
     (void)hipEventRecord(c->ev_tail[evi], c->stream);
     T.arena_base = c->arena_base;
     T.arena_off = c->arena_off;
@@ -3147,9 +3265,9 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     arena_other_half(c, T.arena_base);
     (void)hipEventSynchronize(c->ev_tick[T.evi]);
     double t1 = prof ? host_us() : 0;
-    int64_t H[LEN_TICK];  // the train's first readback (later ones reuse h_len)
+    int64_t H[LEN_TICK];  // the train's head readback (later ones reuse h_len)
     memcpy(H, c->h_len + T.sb, sizeof(H));
-    if (q3_spec_lost(H, T.plans, T.np)) {
+    if (q3_spec_lost(H)) {
         e->spec_fail++;
         q3_train_drop(c, T);
         // re-materialize the deltas from the raw flatmap outputs (arena of
@@ -3181,6 +3299,7 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     constexpr int64_t Q3_ACC_SPILL = 32768;
     Spine *spill[2];
     int nspill = 0;
+    DevBatch consumed[2];
     for (int s = 0; s < 2; s++) {
         Spine &sp = s == 0 ? e->a_int : e->p_int;
         DevBatch res = T.res[s];
@@ -3188,7 +3307,9 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
         DevBatch acc = e->q3_acc[s];
         if (acc.n > 0) {  // the top batch is the consumed accumulator
             sp.batches.pop_back();
-            free_batch(c, acc);
+            // this tick's plans probed it: an overflow replay at the publish
+            // below still reads it, so it is freed after that
+            consumed[s] = acc;
         }
         e->q3_acc[s] = DevBatch{};
         if (res.n > 0) {
@@ -3221,13 +3342,12 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
         fprintf(stderr,
                 "[commit] wait %.1f verdict %.1f swap+hook(total %.1f, hook %.1f) us\n",
                 t1 - t0, t2 - t1, t3 - t2, th1 - th0);
-    // this tick's output lengths land with the emit chain's second
+    // this tick's plan totals and output lengths land with the tail
     // readback, past ev_tick — wait the tail before consuming them
     (void)hipEventSynchronize(c->ev_tail[T.evi]);
-    int64_t slot_totals[3] = {0, 0, 0};
-    for (int i = 0; i < T.np && i < 3; i++) slot_totals[i] = H[L_PLAN + i];
-    TRY(q3_publish_chained(e, T.sb, dA, dP, T.plans, T.np, slot_totals,
-                           T.comb_chain));
+    TRY(q3_publish_chained(e, T.sb, dA, dP, T.plans, T.np, T.comb_chain));
+    free_batch(c, consumed[0]);
+    free_batch(c, consumed[1]);
     // the deltas were folded into res by the in-train merge (they are NOT
     // in the spine); free once the output paths above are done with them
     free_batch(c, dA);

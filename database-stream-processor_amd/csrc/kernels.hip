@@ -577,9 +577,24 @@ __device__ inline uint32_t fuse_scan(uint32_t thread_sum, uint32_t *wave_tot,
     return r;
 }
 
+// LDS of the fused sort (~96 KiB): declared by the kernels and handed to
+// sort_cons_body, so a kernel that runs other phases before the sort can use
+// the buffers for them first
+#define SORT_CONS_LDS                                                      \
+    __shared__ alignas(16) uint32_t bufA[FUSE_MAX];                        \
+    __shared__ alignas(16) uint32_t bufB[FUSE_MAX];                        \
+    __shared__ uint32_t cnt[FUSE_MAX]; /* ballot cells / f64 head pos */   \
+    __shared__ uint32_t wave_tot[FUSE_THREADS / WAVE + 1];                 \
+    __shared__ uint64_t smax[2];                                           \
+    __shared__ uint64_t smin[2];
+
 template <typename W>
-__global__ __launch_bounds__(FUSE_THREADS, 4) void k_sort_cons_small(SortArgs args) {
-    // Fused sort+consolidate of one raw batch per workgroup (n <= 8192).
+__device__ __forceinline__ void sort_cons_body(
+    const uint64_t *kin, const uint64_t *vin, const W *win, int64_t n,
+    uint64_t *tk, uint64_t *tv, W *tw, uint64_t *ok, uint64_t *ov, W *ow,
+    int64_t *out_len, uint32_t *bufA, uint32_t *bufB, uint32_t *cnt,
+    uint32_t *wave_tot, uint64_t *smax, uint64_t *smin) {
+    // Fused sort+consolidate of one raw batch by one workgroup (n <= 8192).
     //
     // LSD radix over 4-bit digits of the concatenated (k - kmin, v - vmin)
     // key, restructured around the 64-wide wavefront:
@@ -596,37 +611,11 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_sort_cons_small(SortArgs ar
     //    memory: one gather per 4-pass group rebuilds the entries.
     // The consolidation reuses the same ballot machinery for head flags and
     // the nonzero compaction.
-    const int batch = blockIdx.x;
-    const uint64_t *kin = args.kin[batch];
-    const uint64_t *vin = args.vin[batch];
-    const W *win = (const W *)args.win[batch];
-    int64_t n = args.n[batch];
-    uint64_t *tk = args.tk[batch];   // scratch (>= n rows)
-    uint64_t *tv = args.tv[batch];
-    W *tw = (W *)args.tw[batch];
-    uint64_t *ok = args.ok[batch];   // output (cap >= n rows)
-    uint64_t *ov = args.ov[batch];
-    W *ow = (W *)args.ow[batch];
-    int64_t *out_len = args.d_len + batch;
-    const int64_t n_chain = args.n_dev[batch] ? *args.n_dev[batch] : -1;
-    __shared__ alignas(16) uint32_t bufA[FUSE_MAX];
-    __shared__ alignas(16) uint32_t bufB[FUSE_MAX];
-    __shared__ uint32_t cnt[FUSE_MAX];  // ballot cells / f64 head positions
-    __shared__ uint32_t wave_tot[FUSE_THREADS / WAVE + 1];
-    __shared__ uint64_t smax[2];
-    __shared__ uint64_t smin[2];
     const int tid = threadIdx.x;
     const int wid = tid / WAVE;
     const int lane = tid % WAVE;
     const uint64_t lt = ((uint64_t)1 << lane) - 1;
 
-    if (args.n_dev[batch]) {
-        if (n_chain > FUSE_MAX || n_chain < 0) {  // speculation lost
-            if (tid == 0) *out_len = -1;
-            return;
-        }
-        n = n_chain;
-    }
     if (n == 0) {
         if (tid == 0) *out_len = 0;
         return;
@@ -973,8 +962,27 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_sort_cons_small(SortArgs ar
     }
 }
 
-
-
+template <typename W>
+__global__ __launch_bounds__(FUSE_THREADS, 4) void k_sort_cons_small(SortArgs args) {
+    // one raw batch per workgroup through sort_cons_body
+    const int batch = blockIdx.x;
+    int64_t n = args.n[batch];
+    int64_t *out_len = args.d_len + batch;
+    SORT_CONS_LDS
+    if (args.n_dev[batch]) {
+        const int64_t n_chain = *args.n_dev[batch];
+        if (n_chain > FUSE_MAX || n_chain < 0) {  // speculation lost
+            if (threadIdx.x == 0) *out_len = -1;
+            return;
+        }
+        n = n_chain;
+    }
+    sort_cons_body<W>(args.kin[batch], args.vin[batch],
+                      (const W *)args.win[batch], n, args.tk[batch],
+                      args.tv[batch], (W *)args.tw[batch], args.ok[batch],
+                      args.ov[batch], (W *)args.ow[batch], out_len, bufA, bufB,
+                      cnt, wave_tot, smax, smin);
+}
 
 // ---------------------------------------------------------------------------
 // dense-range sort+consolidate.  A Nexmark tick's delta usually has a TINY
@@ -2045,65 +2053,6 @@ __global__ void k_join_count_multi(const uint64_t *dk, int64_t nd, TraceArgs t,
 // (a lost speculation upstream, or the combined output exceeding the
 // capacity buffer) makes every consumer bail; the host re-emits explicitly.
 // ---------------------------------------------------------------------------
-// fused variant: bases + all (<=3) plans' emits in ONE launch — each of the
-// three separate chained emit launches cost ~5 us of dependent dispatch on
-// the q3 tick's critical path; every thread recomputes the 3-entry base
-// prefix from the (L2-hot) count totals instead
-__global__ void k_join_emit_fused(FusedEmitArgs a) {
-    int64_t bases[3];
-    int64_t acc = 0;
-    int okf = 1;
-    for (int i = 0; i < a.np; i++) {
-        const int64_t t = a.totals[i];
-        if (t < 0) {
-            okf = 0;
-            break;
-        }
-        bases[i] = acc;
-        acc += t;
-    }
-    if (acc > a.cap) okf = 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *a.d_total = okf ? acc : -1;
-        *a.d_flag = okf ? 0 : 1;
-    }
-    if (!okf) return;
-    for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < acc;
-         o += (int64_t)gridDim.x * blockDim.x) {
-        int p = 0;
-        while (p + 1 < a.np && o >= bases[p + 1]) p++;
-        const int64_t nd = *a.nd_dev[p];
-        if (nd <= 0) continue;
-        const TraceArgs &t = a.t[p];
-        const uint32_t *cnts = a.cnts[p];
-        const uint64_t *offsets = a.offsets[p];
-        const int64_t tn0 = a.tn_dev[p] ? *a.tn_dev[p] : t.n[0];
-        const int64_t oo = o - bases[p];
-        int64_t lo = 0, hi = nd;
-        while (lo < hi) {
-            int64_t mid = (lo + hi) / 2;
-            if (offsets[mid] <= (uint64_t)oo) lo = mid + 1; else hi = mid;
-        }
-        int64_t i = lo - 1;
-        int64_t j = oo - (int64_t)offsets[i];
-        int b = 0;
-        while (j >= (int64_t)cnts[i * t.nb + b]) {
-            j -= cnts[i * t.nb + b];
-            b++;
-        }
-        const uint64_t key = a.dk[p][i];
-        const int64_t tb_n = b == 0 ? tn0 : t.n[b];
-        const int64_t start = lower_bound_k(t.k[b], tb_n, key);
-        const int64_t ti = start + j;
-        uint64_t hi_o, lo_o;
-        const bool valid = proj_out(a.proj[p], 0, key, a.dv[p][i],
-                                    t.v[b][ti], hi_o, lo_o);
-        a.ok[o] = hi_o;
-        a.ov[o] = lo_o;
-        a.ow[o] = valid ? a.dw[p][i] * t.w[b][ti] : 0;
-    }
-}
-
 __global__ void k_emit_bases(const int64_t *totals, int np, int64_t cap,
                              int64_t *bases, int64_t *out_total,
                              int64_t *out_flag) {
@@ -2211,14 +2160,16 @@ __global__ __launch_bounds__(BLK, 8) void k_join_probe_multi(
     const int64_t tn0 = args.tn_dev[plan] ? *args.tn_dev[plan] : t.n[0];
     if (nd < 0 || nd > FUSE_MAX || tn0 < 0) return;  // scan flags the total
     uint32_t *cnts = args.cnts[plan];
+    int64_t *starts = args.starts[plan];  // null: the caller re-searches
     for (int64_t i = (int64_t)slice * BLK + threadIdx.x; i < nd;
          i += (int64_t)JPROBE_BLOCKS * BLK) {
         const uint64_t key = dk[i];
         for (int b = 0; b < t.nb; b++) {
             const int64_t tb_n = b == 0 ? tn0 : t.n[b];
             int64_t lo = lower_bound_k(t.k[b], tb_n, key);
-            cnts[(int64_t)i * t.nb + b] =
-                (uint32_t)gallop_run(t.k[b], tb_n, key, lo);
+            const uint32_t c = (uint32_t)gallop_run(t.k[b], tb_n, key, lo);
+            cnts[(int64_t)i * t.nb + b] = c;
+            if (starts && c) starts[(int64_t)i * t.nb + b] = lo;
         }
     }
 }
@@ -2258,6 +2209,171 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_scan_small(
         off += row_tot[j];
     }
     if (tid == 0) *d_total = (int64_t)total;
+}
+
+// ---------------------------------------------------------------------------
+// join tail: everything of a chained join tick behind the probe, in ONE
+// single-workgroup launch — scan of the probe's counts, capacity check, emit
+// into the capacity buffer, sort+consolidate into the output store.  At tick
+// scale (a few hundred delta and output rows) these were three dependent
+// launches of one workgroup each plus a length copy between them; here the
+// phases are separated by block barriers only.
+//
+// The delta rows of all (<= 3) plans form ONE row sequence, plan after plan
+// (R <= 3 * 8192 rows), scanned once: row r's exclusive offset is at once its
+// first position in the capacity buffer, plan-major as the per-plan emits
+// wrote it.  The offsets stay in LDS — the sort's three buffers, free until
+// the sort phase — and the emit binary-searches them there.  The probe left,
+// per delta row i and trace batch b, the match count cnts[i*nb+b] and, where
+// that is nonzero, the run's first position starts[i*nb+b]: the emit
+// searches neither the trace nor global memory.  Loops over a row's batches
+// are unrolled to MAX_TRACE_BATCHES predicated loads, so they are issued
+// together instead of one load latency per batch.
+//
+// Verdicts (the host reads them after the tail readback):
+//   totals[p]  plan p's row total, -1 if one of its lengths is a lost
+//              speculation; offsets[p][] (plan-local) is written for every
+//              plan whose total is >= 0, whatever the other plans did, so
+//              the host's explicit replay can emit from them
+//   d_flag     1: nothing usable in the capacity buffer (negative plan, or
+//              combined total > cap); rows are only ever written below cap
+//   d_total    combined total, -1 if flagged
+//   d_final    consolidated length in the output store, -1 if flagged or if
+//              the combined total exceeds the fused sort (then the emitted
+//              rows wait in the capacity buffer for a sized sort)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_tail_small(
+    JoinTailArgs a) {
+    SORT_CONS_LDS
+    // row r's offset cell: three 8192-cell buffers back to back
+    auto cell = [&](int r) -> uint32_t * {
+        return r < FUSE_MAX ? cnt + r
+                            : (r < 2 * FUSE_MAX ? bufA + (r - FUSE_MAX)
+                                                : bufB + (r - 2 * FUSE_MAX));
+    };
+    const int tid = threadIdx.x;
+    // per-plan constants in registers (np <= 3; absent plans have no rows)
+    int rb[4] = {0, 0, 0, 0};  // first row of plan p; rb[3] = R
+    int nbp[3] = {0, 0, 0};
+    const uint32_t *cp[3] = {nullptr, nullptr, nullptr};
+    int neg = 0;  // bit p: plan p read a lost speculation's length
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        int n = 0;
+        if (p < a.np) {
+            const int64_t nd = *a.nd_dev[p];
+            const int64_t tn0 = a.tn_dev[p] ? *a.tn_dev[p] : a.t[p].n[0];
+            if (nd < 0 || nd > FUSE_MAX || tn0 < 0) {
+                neg |= 1 << p;
+            } else {
+                n = (int)nd;
+            }
+            nbp[p] = a.t[p].nb;
+            cp[p] = a.cnts[p];
+        }
+        rb[p + 1] = rb[p] + n;
+    }
+    const int R = rb[3];
+    auto plan_of = [&](int r) -> int { return (r >= rb[1]) + (r >= rb[2]); };
+
+    // ---- scan: row totals into their cells, then exclusive offsets ----
+    const int ipt = (R + FUSE_THREADS - 1) / FUSE_THREADS;  // rows per thread
+    uint32_t tsum = 0;
+    for (int j = 0; j < ipt; j++) {
+        const int r = tid * ipt + j;
+        if (r >= R) break;
+        const int p = plan_of(r);
+        const int nb = p == 0 ? nbp[0] : (p == 1 ? nbp[1] : nbp[2]);
+        const uint32_t *c =
+            (p == 0 ? cp[0] : (p == 1 ? cp[1] : cp[2])) +
+            (int64_t)(r - (p == 0 ? rb[0] : (p == 1 ? rb[1] : rb[2]))) * nb;
+        uint32_t rt = 0;
+#pragma unroll
+        for (int b = 0; b < MAX_TRACE_BATCHES; b++)
+            rt += b < nb ? c[b] : 0;
+        *cell(r) = rt;
+        tsum += rt;
+    }
+    uint32_t total;
+    uint32_t off = fuse_scan(tsum, wave_tot, &total);
+    for (int j = 0; j < ipt; j++) {
+        const int r = tid * ipt + j;
+        if (r >= R) break;
+        uint32_t *q = cell(r);
+        const uint32_t rt = *q;
+        *q = off;
+        off += rt;
+    }
+    __syncthreads();
+
+    // ---- per-plan totals and plan-local offsets for the explicit replay ----
+    uint32_t pb[4];  // plan p's first output position; pb[3] = total
+#pragma unroll
+    for (int p = 0; p < 4; p++) pb[p] = rb[p] < R ? *cell(rb[p]) : total;
+    if (tid == 0) {
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+            if (p < a.np)
+                a.totals[p] =
+                    (neg >> p) & 1 ? -1 : (int64_t)(pb[p + 1] - pb[p]);
+    }
+    for (int r = tid; r < R; r += FUSE_THREADS) {
+        const int p = plan_of(r);
+        const int r0 = p == 0 ? rb[0] : (p == 1 ? rb[1] : rb[2]);
+        const uint32_t b0 = p == 0 ? pb[0] : (p == 1 ? pb[1] : pb[2]);
+        a.offsets[p][r - r0] = *cell(r) - b0;
+    }
+
+    // ---- emit: only if the combined rows fit the capacity buffer ----
+    const int64_t acc = total;
+    const bool okf = !neg && acc <= a.cap;
+    if (okf) {
+        for (uint32_t o = tid; o < total; o += FUSE_THREADS) {
+            int lo = 0, hi = R;
+            while (lo < hi) {
+                const int mid = (lo + hi) / 2;
+                if (*cell(mid) <= o) lo = mid + 1; else hi = mid;
+            }
+            const int r = lo - 1;
+            const int p = plan_of(r);
+            const TraceArgs &t = a.t[p];
+            const int nb = t.nb;
+            const int64_t i = r - (p == 0 ? rb[0] : (p == 1 ? rb[1] : rb[2]));
+            const uint32_t *c = a.cnts[p] + i * nb;
+            uint32_t j = o - *cell(r);
+            int b = 0;
+#pragma unroll
+            for (int bb = 0; bb < MAX_TRACE_BATCHES; bb++) {
+                // past nb nothing is taken: j is below the row's total
+                const uint32_t cb = bb < nb ? c[bb] : 0xFFFFFFFFu;
+                const bool take = b == bb && j >= cb;
+                j -= take ? cb : 0;
+                b += take ? 1 : 0;
+            }
+            const int64_t ti = a.starts[p][i * nb + b] + j;
+            const uint64_t key = a.dk[p][i];
+            uint64_t hi_o, lo_o;
+            const bool valid = proj_out(a.proj[p], 0, key, a.dv[p][i],
+                                        t.v[b][ti], hi_o, lo_o);
+            a.ek[o] = hi_o;
+            a.ev[o] = lo_o;
+            a.ew[o] = valid ? a.dw[p][i] * t.w[b][ti] : 0;
+        }
+    }
+    __syncthreads();  // the cells are the sort's buffers from here on
+    if (tid == 0) {
+        *a.d_total = okf ? acc : -1;
+        *a.d_flag = okf ? 0 : 1;
+    }
+    if (!okf || acc > FUSE_MAX) {
+        if (tid == 0) *a.d_final = -1;
+        return;
+    }
+    // the emitted rows were stored by this workgroup; the barrier above
+    // orders them before the sort's loads
+    sort_cons_body<int64_t>(a.ek, a.ev, a.ew, acc, a.tk, a.tv, a.tw, a.ok,
+                            a.ov, a.ow, a.d_final, bufA, bufB, cnt, wave_tot,
+                            smax, smin);
 }
 
 // ---------------------------------------------------------------------------
@@ -3377,8 +3493,18 @@ dbsp_status join_emit_chain(hipStream_t s, const uint64_t *dk,
     return DBSP_OK;
 }
 
-dbsp_status join_emit_fused(hipStream_t s, const FusedEmitArgs &a) {
-    k_join_emit_fused<<<grid_for(a.cap), BLK, 0, s>>>(a);
+dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args) {
+    if (args.np == 0) return DBSP_OK;
+    for (int i = 0; i < args.np; i++)
+        if (args.nd[i] > FUSE_MAX) return DBSP_ERR_INVALID;
+    k_join_probe_multi<<<dim3((uint32_t)(args.np * JPROBE_BLOCKS)), BLK, 0,
+                         s>>>(args);
+    return DBSP_OK;
+}
+
+dbsp_status join_tail_small(hipStream_t s, const JoinTailArgs &a) {
+    if (a.np < 0 || a.np > 3 || a.cap < FUSE_MAX) return DBSP_ERR_INVALID;
+    k_join_tail_small<<<1, FUSE_THREADS, 0, s>>>(a);
     return DBSP_OK;
 }
 

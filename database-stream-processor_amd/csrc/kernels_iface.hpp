@@ -58,8 +58,11 @@ struct MergeArgs {
     int64_t *d_len;
 };
 
-// fused chained-emit descriptor (bases + all plans' emits in one launch)
-struct FusedEmitArgs {
+// join-tail descriptor: per-plan scan + capacity check + emit into the
+// capacity buffer (e*) + sort/consolidate through the scratch (t*) into the
+// output store (o*, >= 8192 rows), all in one single-workgroup launch behind
+// a probe that kept the start positions.  See k_join_tail_small.
+struct JoinTailArgs {
     int np;
     const uint64_t *dk[3], *dv[3];
     const int64_t *dw[3];
@@ -67,12 +70,18 @@ struct FusedEmitArgs {
     TraceArgs t[3];
     const int64_t *tn_dev[3];
     const uint32_t *cnts[3];
-    const uint64_t *offsets[3];
+    const int64_t *starts[3];
+    uint64_t *offsets[3];  // out: per-row exclusive offsets (explicit replay)
     int proj[3];
-    const int64_t *totals;  // per-plan count totals (device)
-    int64_t cap;
-    int64_t *d_total;  // combined total out (or -1)
-    int64_t *d_flag;   // overflow flag out
+    int64_t *totals;   // out: per-plan row totals (-1: negative length)
+    int64_t cap;       // rows of the capacity buffer
+    int64_t *d_total;  // out: combined total (or -1)
+    int64_t *d_flag;   // out: nonzero = capacity buffer unusable
+    int64_t *d_final;  // out: consolidated length (or -1)
+    uint64_t *ek, *ev;
+    int64_t *ew;
+    uint64_t *tk, *tv;
+    int64_t *tw;
     uint64_t *ok, *ov;
     int64_t *ow;
 };
@@ -90,6 +99,9 @@ struct JoinCountArgs {
     // make the plan write d_total = -1 for the host to detect at its sync.
     const int64_t *nd_dev[3];
     const int64_t *tn_dev[3];
+    // optional: the probe also keeps each (row, batch) run's first position,
+    // starts[i*nb+b] next to cnts[i*nb+b] (int64: exact for any batch length)
+    int64_t *starts[3];
 };
 
 
@@ -279,7 +291,10 @@ dbsp_status distinct_inc_rows(hipStream_t s, const uint64_t *dk,
                               int64_t nd, const TraceArgs &t, uint64_t **ok,
                               uint64_t **ov, int64_t **ow, int64_t *out_n);
 
-dbsp_status join_emit_fused(hipStream_t s, const FusedEmitArgs &a);
+// the probe phase of join_count_scan_batch alone (counts and, if asked,
+// start positions; no scan), and the single-workgroup tail that consumes it
+dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args);
+dbsp_status join_tail_small(hipStream_t s, const JoinTailArgs &a);
 
 dbsp_status agg_linear_upsert_rows(hipStream_t s, const uint64_t *keys,
                                    int64_t nd, const uint64_t *ik,
