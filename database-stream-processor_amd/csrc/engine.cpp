@@ -386,11 +386,7 @@ struct ScopedTimer {
 // device batches + spine
 // ---------------------------------------------------------------------------
 
-struct DevBatch {
-    uint64_t *k = nullptr, *v = nullptr;
-    int64_t *w = nullptr;
-    int64_t n = 0;
-};
+using DevBatch = dbspk::Rows;
 
 static void free_batch(dbsp_ctx *c, DevBatch &b) {
     if (b.k && !in_arena(c, b.k)) (void)dbspk::cache_free(b.k, c->stream);
@@ -487,37 +483,12 @@ static inline TraceArgs trace_args_one(const DevBatch &b) {
     return t;
 }
 
-// the weight type's three merge kernels (tiny single-WG, fixed-grid mid,
-// multi-block two-pass); f64 weights travel as their bit patterns
-struct MergeOps {
-    dbsp_status (*small)(hipStream_t, const MergeArgs &);
-    dbsp_status (*mid)(hipStream_t, const MergeArgs &, int64_t *);
-    dbsp_status (*rows)(hipStream_t, const uint64_t *, const uint64_t *,
-                        const int64_t *, int64_t, const uint64_t *,
-                        const uint64_t *, const int64_t *, int64_t,
-                        uint64_t **, uint64_t **, int64_t **, int64_t *);
-};
-static dbsp_status merge_rows_f64_bits(hipStream_t s, const uint64_t *ak,
-                                       const uint64_t *av, const int64_t *aw,
-                                       int64_t na, const uint64_t *bk,
-                                       const uint64_t *bv, const int64_t *bw,
-                                       int64_t nb, uint64_t **ok, uint64_t **ov,
-                                       int64_t **ow, int64_t *out_n) {
-    return dbspk::merge_rows_f64(s, ak, av, (const double *)aw, na, bk, bv,
-                                 (const double *)bw, nb, ok, ov, (double **)ow,
-                                 out_n);
-}
-static const MergeOps MERGE_I64 = {dbspk::merge_small_batch,
-                                   dbspk::merge_mid_batch, dbspk::merge_rows};
-// (config C5's weighted integral spine; position-fixed reduction orders,
-// algebra/floats.rs:24 zero elimination)
-static const MergeOps MERGE_F64 = {dbspk::merge_small_batch_f64,
-                                   dbspk::merge_mid_batch_f64,
-                                   merge_rows_f64_bits};
-
+// wf64: f64 weights, carried as their bit patterns (config C5's weighted
+// integral spine; position-fixed reduction orders, algebra/floats.rs:24 zero
+// elimination)
 static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
                                  const DevBatch &b, DevBatch &out,
-                                 const MergeOps &ops = MERGE_I64);
+                                 bool wf64 = false);
 
 // medium raw batches (8192 < n <= 64k): chunk into <=8 fused single-WG sorts
 // in ONE launch, then a batched single-WG merge tree (3 launches, 1 sync per
@@ -536,7 +507,7 @@ static dbsp_status sort_medium(dbsp_ctx *c, DevBatch raw, DevBatch &out) {
                   scratch[i], chunks[i]);
     }
     sa.d_len = c->d_len + LEN_OP;
-    TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+    TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
     TRY(read_len(c, LEN_OP, nch));
     for (int i = 0; i < nch; i++) chunks[i].n = c->h_len[LEN_OP + i];
     free_batch(c, raw);
@@ -570,9 +541,9 @@ static dbsp_status sort_medium(dbsp_ctx *c, DevBatch raw, DevBatch &out) {
             }
             ma.d_len = c->d_len + LEN_OP;
             mm.d_len = c->d_len + LEN_OP + ma.np;
-            if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma));
+            if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma, false));
             if (mm.np > 0)
-                TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid));
+                TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid, false));
             TRY(read_len(c, LEN_OP, ma.np + mm.np));
             for (size_t p = 0; p < results.size(); p++)
                 TRY(checked_len(c, LEN_OP + slots[p], results[p].n));
@@ -609,7 +580,7 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
         // where a weight histogram over (krange+1)*(vrange+1) cells replaces
         // the whole sort.  Worth one extra sync only above the fused size.
         uint64_t mm[4];
-        TRY(dbspk::minmax_rows(c->stream, raw.k, raw.v, raw.n, mm));
+        TRY(dbspk::minmax_rows(c->stream, raw, mm));
         const uint64_t kr = mm[2] - mm[0], vr = mm[3] - mm[1];
         const int64_t dense_cap =
             std::min<int64_t>((int64_t)1 << 22, 8 * raw.n);
@@ -617,10 +588,9 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
             (int64_t)((kr + 1) * (vr + 1)) <= dense_cap) {
             DevBatch res;
             TRY(alloc_batch(c, raw.n, res));
-            TRY(dbspk::sort_cons_dense(c->stream, raw.k, raw.v, raw.w, raw.n,
-                                       mm[0], mm[1], (int64_t)(kr + 1),
-                                       (int64_t)(vr + 1), res.k, res.v, res.w,
-                                       &res.n));
+            TRY(dbspk::sort_cons_dense(c->stream, raw, mm[0], mm[1],
+                                       (int64_t)(kr + 1), (int64_t)(vr + 1),
+                                       &res));
             free_batch(c, raw);
             out = res;
             return DBSP_OK;
@@ -637,7 +607,7 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
         sa.nb = 1;
         sort_slot(sa, 0, raw, scratch, res);
         sa.d_len = c->d_len + LEN_OP;
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+        TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
         TRY(read_len(c, LEN_OP, 1));
         res.n = c->h_len[LEN_OP];
         free_batch(c, raw);
@@ -646,19 +616,16 @@ static dbsp_status sort_consolidate_batch(dbsp_ctx *c, DevBatch raw, DevBatch &o
         return DBSP_OK;
     }
     bool in_scratch = false;
-    TRY(dbspk::sort_rows(c->stream, raw.k, raw.v, raw.w, raw.n, scratch.k,
-                         scratch.v, scratch.w, &in_scratch));
-    DevBatch &sorted = in_scratch ? scratch : raw;
-    TRY(dbspk::consolidate_sorted(c->stream, sorted.k, sorted.v, sorted.w, raw.n,
-                                  &out.k, &out.v, &out.w, &out.n));
+    TRY(dbspk::sort_rows(c->stream, raw, scratch, &in_scratch));
+    TRY(dbspk::consolidate_sorted(c->stream, in_scratch ? scratch : raw, false,
+                                  &out));
     free_batch(c, raw);
     free_batch(c, scratch);
     return DBSP_OK;
 }
 
 static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
-                                 const DevBatch &b, DevBatch &out,
-                                 const MergeOps &ops) {
+                                 const DevBatch &b, DevBatch &out, bool wf64) {
     ScopedTimer t(c, 1, (double)(a.n + b.n) * 48.0);
     // three bands: tiny pairs (<= 4k) in one single-WG launch; mid pairs
     // (<= 32k) in the fixed-grid multi-WG merge (a 16k single-WG merge
@@ -672,16 +639,15 @@ static dbsp_status merge_batches(dbsp_ctx *c, const DevBatch &a,
         merge_pair(ma, 0, a, b, res);
         ma.d_len = c->d_len + LEN_OP;
         if (a.n + b.n <= 4096)
-            TRY(ops.small(c->stream, ma));
+            TRY(dbspk::merge_small_batch(c->stream, ma, wf64));
         else
-            TRY(ops.mid(c->stream, ma, c->d_mid));
+            TRY(dbspk::merge_mid_batch(c->stream, ma, c->d_mid, wf64));
         TRY(read_len(c, LEN_OP, 1));
         TRY(checked_len(c, LEN_OP, res.n));  // fused-barrier poison
         out = res;
         return DBSP_OK;
     }
-    return ops.rows(c->stream, a.k, a.v, a.w, a.n, b.k, b.v, b.w, b.n, &out.k,
-                    &out.v, &out.w, &out.n);
+    return dbspk::merge_rows(c->stream, a, b, wf64, &out);
 }
 
 // Spine: stack of consolidated batches; invariant size[i] >= 2*size[i+1]
@@ -698,7 +664,7 @@ struct Spine {
 
     dbsp_status merge2(dbsp_ctx *c, const DevBatch &a, const DevBatch &b,
                        DevBatch &out) const {
-        return merge_batches(c, a, b, out, wf64 ? MERGE_F64 : MERGE_I64);
+        return merge_batches(c, a, b, out, wf64);
     }
 
     // more batches than a TraceArgs holds: merge down to one
@@ -845,9 +811,8 @@ extern "C" dbsp_status dbsp_join(dbsp_ctx *c, const dbsp_batch *delta,
     DevBatch res;
     {
         ScopedTimer t(c, 2, (double)delta->len * 24.0);
-        TRY(dbspk::join_rows(c->stream, delta->k, delta->v, delta->w, delta->len,
-                             trace->k, trace->v, trace->w, trace->len, proj,
-                             param, &res.k, &res.v, &res.w, &res.n));
+        TRY(dbspk::join_rows(c->stream, as_batch(delta), as_batch(trace), proj,
+                             param, &res));
     }
     put_batch(out, res);
     return DBSP_OK;
@@ -866,13 +831,10 @@ extern "C" dbsp_status dbsp_rolling_agg(dbsp_ctx *c, const dbsp_batch *in,
     TRY(alloc_batch(c, in->len > 0 ? in->len : 1, res));
     {
         ScopedTimer t(c, 3, 0.0);
-        TRY(dbspk::rolling_agg_rows(c->stream, in->k, in->v, in->w, in->len,
-                                    width, res.k, res.v, res.w));
+        TRY(dbspk::rolling_agg_rows(c->stream, as_batch(in), width, res));
     }
-    out->k = res.k;
-    out->v = res.v;
-    out->w = res.w;
-    out->len = in->len;
+    res.n = in->len;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -883,11 +845,8 @@ extern "C" dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *c,
                                               const dbsp_batch *out_trace,
                                               dbsp_batch *out) {
     DevBatch res;
-    TRY(dbspk::agg_linear_upsert_rows(c->stream, delta_keys, nd, in_trace->k,
-                                      in_trace->v, in_trace->w, in_trace->len,
-                                      out_trace->k, out_trace->v, out_trace->w,
-                                      out_trace->len, &res.k, &res.v, &res.w,
-                                      &res.n));
+    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LINEAR, delta_keys, nd,
+                               as_batch(in_trace), as_batch(out_trace), &res));
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -899,11 +858,8 @@ extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
                                            const dbsp_batch *out_trace,
                                            dbsp_batch *out) {
     DevBatch res;
-    TRY(dbspk::agg_max_upsert_rows(c->stream, delta_keys, nd, in_trace->k,
-                                   in_trace->v, in_trace->w, in_trace->len,
-                                   out_trace->k, out_trace->v, out_trace->w,
-                                   out_trace->len, &res.k, &res.v, &res.w,
-                                   &res.n));
+    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_MAX, delta_keys, nd,
+                               as_batch(in_trace), as_batch(out_trace), &res));
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -915,10 +871,8 @@ extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
     DevBatch res;
     {
         ScopedTimer t(c, 4, 0.0);
-        TRY(dbspk::window_rows(c->stream, trace->k, trace->v, trace->w,
-                               trace->len, batch->k, batch->v, batch->w,
-                               batch->len, have_prev, s0, e0, s1, e1, &res.k,
-                               &res.v, &res.w, &res.n));
+        TRY(dbspk::window_rows(c->stream, as_batch(trace), as_batch(batch),
+                               have_prev, s0, e0, s1, e1, &res));
     }
     put_batch(out, res);
     return DBSP_OK;
@@ -929,9 +883,8 @@ extern "C" dbsp_status dbsp_shard_partition(dbsp_ctx *c, const dbsp_batch *in,
                                             int64_t *offsets_host) {
     DevBatch res;
     TRY(alloc_batch(c, in->len, res));
-    TRY(dbspk::shard_rows(c->stream, in->k, in->v, in->w, in->len, nshards,
-                          res.k, res.v, res.w, offsets_host));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = in->len;
+    TRY(dbspk::shard_rows(c->stream, as_batch(in), nshards, res, offsets_host));
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -958,7 +911,7 @@ extern "C" dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *c,
         sa.nb = 1;
         sort_slot(sa, 0, raw, scratch, res);
         sa.d_len = c->d_len + LEN_OP;
-        TRY(dbspk::sort_cons_small_batch_f64(c->stream, sa));
+        TRY(dbspk::sort_cons_small_batch(c->stream, sa, true));
         TRY(read_len(c, LEN_OP, 1));
         res.n = c->h_len[LEN_OP];
         put_batch(out, res);
@@ -969,16 +922,11 @@ extern "C" dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *c,
     DevBatch scratch;
     TRY(alloc_batch(c, n, scratch, true));
     bool in_scratch = false;
-    TRY(dbspk::sort_rows(c->stream, raw.k, raw.v, raw.w, n, scratch.k,
-                         scratch.v, scratch.w, &in_scratch));
-    DevBatch &sorted = in_scratch ? scratch : raw;
-    uint64_t *rk, *rv;
-    double *rw;
-    int64_t nout = 0;
-    TRY(dbspk::consolidate_sorted_f64(c->stream, sorted.k, sorted.v,
-                                      (double *)sorted.w, n, &rk, &rv, &rw,
-                                      &nout));
-    out->k = rk; out->v = rv; out->w = (int64_t *)rw; out->len = nout;
+    TRY(dbspk::sort_rows(c->stream, raw, scratch, &in_scratch));
+    DevBatch res;
+    TRY(dbspk::consolidate_sorted(c->stream, in_scratch ? scratch : raw, true,
+                                  &res));
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -991,19 +939,15 @@ extern "C" dbsp_status dbsp_merge_f64(dbsp_ctx *c, const dbsp_batch *a,
         ma.np = 1;
         merge_pair(ma, 0, as_batch(a), as_batch(b), res);
         ma.d_len = c->d_len + LEN_OP;
-        TRY(dbspk::merge_small_batch_f64(c->stream, ma));
+        TRY(dbspk::merge_small_batch(c->stream, ma, true));
         TRY(read_len(c, LEN_OP, 1));
         res.n = c->h_len[LEN_OP];
         put_batch(out, res);
         return DBSP_OK;
     }
-    uint64_t *rk, *rv;
-    double *rw;
-    int64_t nout = 0;
-    TRY(dbspk::merge_rows_f64(c->stream, a->k, a->v, (const double *)a->w,
-                              a->len, b->k, b->v, (const double *)b->w, b->len,
-                              &rk, &rv, &rw, &nout));
-    out->k = rk; out->v = rv; out->w = (int64_t *)rw; out->len = nout;
+    DevBatch res;
+    TRY(dbspk::merge_rows(c->stream, as_batch(a), as_batch(b), true, &res));
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -1011,9 +955,9 @@ extern "C" dbsp_status dbsp_weigh_f64(dbsp_ctx *c, const dbsp_batch *in,
                                       dbsp_batch *out) {
     DevBatch res;
     TRY(alloc_batch(c, in->len > 0 ? in->len : 1, res));
-    TRY(dbspk::map_rows(c->stream, in->k, in->v, in->w, in->len, 4, res.k,
-                        res.v, res.w));
-    out->k = res.k; out->v = res.v; out->w = res.w; out->len = in->len;
+    TRY(dbspk::map_rows(c->stream, as_batch(in), 4, res));
+    res.n = in->len;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -1027,26 +971,19 @@ extern "C" dbsp_status dbsp_agg_linear_upsert_f64(dbsp_ctx *c,
         put_batch(out, DevBatch{});
         return DBSP_OK;
     }
-    double *acc;
+    int64_t *acc;  // f64 sums as bit patterns
     HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nd * 8 + 8, c->stream));
     HIP_CHECK_ST(hipMemsetAsync(acc, 0, nd * 8, c->stream));
-    TRY(dbspk::agg_sum_batch_f64(c->stream, delta_keys, nd, in_trace->k,
-                                 (const double *)in_trace->w, in_trace->len,
-                                 acc));
+    TRY(dbspk::agg_sum_batch(c->stream, delta_keys, nd, as_batch(in_trace), acc,
+                             true));
     DevBatch ins;
     TRY(alloc_batch(c, nd, ins, true));
-    int64_t n_ins = 0;
-    TRY(dbspk::emit_nonzero_f64(c->stream, delta_keys, acc, nd, ins.k, ins.v,
-                                ins.w, &n_ins));
-    ins.n = n_ins;
+    TRY(dbspk::emit_nonzero(c->stream, delta_keys, acc, nd, true, &ins));
     HIP_CHECK_ST(dbspk::cache_free(acc, c->stream));
     // retractions against the (i64-weighted) output trace
     DevBatch retr;
-    TRY(dbspk::agg_linear_upsert_rows(c->stream, delta_keys, nd, nullptr,
-                                      nullptr, nullptr, 0, out_trace->k,
-                                      out_trace->v, out_trace->w,
-                                      out_trace->len, &retr.k, &retr.v,
-                                      &retr.w, &retr.n));
+    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LINEAR, delta_keys, nd,
+                               DevBatch{}, as_batch(out_trace), &retr));
     DevBatch res;
     TRY(alloc_batch(c, ins.n + retr.n, res));
     TRY(copy_cols(c, res, 0, ins.k, ins.v, ins.w, ins.n));
@@ -1066,8 +1003,7 @@ extern "C" dbsp_status dbsp_distinct_inc(dbsp_ctx *c, const dbsp_batch *delta,
     for (int i = 0; i < n_batches; i++)
         if (trace_batches[i].len != 0) trace_push(t, as_batch(&trace_batches[i]));
     DevBatch res;
-    TRY(dbspk::distinct_inc_rows(c->stream, delta->k, delta->v, delta->w,
-                                 delta->len, t, &res.k, &res.v, &res.w, &res.n));
+    TRY(dbspk::distinct_inc_rows(c->stream, as_batch(delta), t, &res));
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -1190,8 +1126,7 @@ static dbsp_status shard_exchange(dbsp_ctx *c, DevBatch local, DevBatch &out,
     DevBatch parts;
     TRY(alloc_batch(c, local.n, parts));
     int64_t offsets[65];
-    TRY(dbspk::shard_rows(c->stream, local.k, local.v, local.w, local.n,
-                          c->world, parts.k, parts.v, parts.w, offsets));
+    TRY(dbspk::shard_rows(c->stream, local, c->world, parts, offsets));
     free_batch(c, local);
     if (hint > 0 && c->world <= 8 && c->comm) {
         const int64_t P = 2 * hint / c->world + 512;
@@ -1219,8 +1154,7 @@ static dbsp_status shard_exchange(dbsp_ctx *c, DevBatch local, DevBatch &out,
         DevBatch r0, r1;
         TRY(alloc_batch(c, c->world * P, r0, true));
         TRY(alloc_batch(c, c->world, r1, true));
-        TRY(dbspk::frames_unpack_pair(c->stream, frecv, c->world, P, 1, r0.k,
-                                      r0.v, r0.w, r1.k, r1.v, r1.w,
+        TRY(dbspk::frames_unpack_pair(c->stream, frecv, c->world, P, 1, r0, r1,
                                       c->d_len + L_XCHG,
                                       c->d_len + L_XCHG + 1));
         TRY(read_len(c, L_XCHG, 2));
@@ -1520,7 +1454,7 @@ static dbsp_status sort_two_small(dbsp_ctx *c, DevBatch rawA, DevBatch rawB,
     sort_slot(sa, 0, rawA, sA, oA);
     sort_slot(sa, 1, rawB, sB, oB);
     sa.d_len = c->d_len + LEN_OP;
-    TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+    TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
     TRY(read_len(c, LEN_OP, 2));
     oA.n = c->h_len[LEN_OP];
     oB.n = c->h_len[LEN_OP + 1];
@@ -1557,9 +1491,7 @@ static dbsp_status shard_exchange_pair(dbsp_ctx *c, DevBatch l0, DevBatch l1,
     TRY(alloc_batch(c, l0.n > 0 ? l0.n : 1, p0, true));
     TRY(alloc_batch(c, l1.n > 0 ? l1.n : 1, p1, true));
     int64_t off0[65], off1[65];
-    TRY(dbspk::shard_rows_pair(c->stream, l0.k, l0.v, l0.w, l0.n, l1.k, l1.v,
-                               l1.w, l1.n, world, p0.k, p0.v, p0.w, p1.k,
-                               p1.v, p1.w, off0, off1));
+    TRY(dbspk::shard_rows_pair(c->stream, l0, l1, world, p0, p1, off0, off1));
     p0.n = l0.n;
     p1.n = l1.n;
     free_batch(c, l0);
@@ -1599,8 +1531,7 @@ static dbsp_status shard_exchange_pair(dbsp_ctx *c, DevBatch l0, DevBatch l1,
         DevBatch r0, r1;
         TRY(alloc_batch(c, world * P0, r0, true));
         TRY(alloc_batch(c, world * P1, r1, true));
-        TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, r0.k,
-                                      r0.v, r0.w, r1.k, r1.v, r1.w,
+        TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, r0, r1,
                                       c->d_len + L_XCHG,
                                       c->d_len + L_XCHG + 1));
         TRY(read_len(c, L_XCHG, 2));
@@ -1714,8 +1645,7 @@ static dbsp_status flatmap_chain(dbsp_engine *e, const dbsp_event *d_ev,
     dbspk::EventCols cols{};
     const bool hc = staged_cols(e, d_ev, cols);
     return dbspk::flatmap_events_chain(c->stream, d_ev, hc ? &cols : nullptr,
-                                       n, e->query, rawA.k, rawA.v, rawA.w,
-                                       rawB.k, rawB.v, rawB.w,
+                                       n, e->query, rawA, rawB,
                                        (uint64_t *)(c->d_len + sb + L_RAW));
 }
 
@@ -1739,7 +1669,7 @@ static dbsp_status sort_pair_chain(dbsp_ctx *c, const DevBatch &inA,
     sa.d_len = c->d_len + sb + L_DELTA;
     {
         ScopedTimer t(c, 0, (double)n_events * 48.0);
-        TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+        TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
     }
     oA.n = -1;
     oB.n = -1;
@@ -1762,15 +1692,11 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
         DevBatch raw0, raw1;
         TRY(alloc_batch(c, n > 0 ? n : 1, raw0, true));
         TRY(alloc_batch(c, n > 0 ? n : 1, raw1, true));
-        int64_t n0 = 0, n1 = 0;
         dbspk::EventCols cols{};
         const bool hc = staged_cols(e, d_ev, cols);
         TRY(dbspk::flatmap_events(c->stream, d_ev, hc ? &cols : nullptr, n,
-                                  e->query, raw0.k, raw0.v, raw0.w, &n0,
-                                  raw1.k, raw1.v, raw1.w, &n1));
-        raw0.n = n0;
-        raw1.n = n1;
-        if (want_two && n0 <= 8192 && n1 <= 8192) {
+                                  e->query, &raw0, &raw1));
+        if (want_two && raw0.n <= 8192 && raw1.n <= 8192) {
             TRY(sort_two_small(c, raw0, raw1, d0, d1));
         } else {
             TRY(sort_consolidate_batch(c, raw0, d0));
@@ -1867,18 +1793,16 @@ static dbsp_status build_deltas_chain_sharded(
                                      c->stream));
     HIP_CHECK_ST(dbspk::cache_malloc((void **)&frecv, (size_t)world * S * 8,
                                      c->stream));
-    TRY(dbspk::shard_frames_chain(c->stream, rawA.k, rawA.v, rawA.w, raw_len,
-                                  rawB.k, rawB.v, rawB.w, raw_len + 1, world,
-                                  P0, P1, cap, fsend));
+    TRY(dbspk::shard_frames_chain(c->stream, rawA, raw_len, rawB, raw_len + 1,
+                                  world, P0, P1, cap, fsend));
     if (ncclAllToAll(fsend, frecv, (size_t)S, ncclUint64, c->comm,
                      c->stream) != ncclSuccess)
         return DBSP_ERR_INTERNAL;
     const int64_t capA = world * P0, capB = world * P1;
     TRY(alloc_batch(c, capA, recvA, true));
     TRY(alloc_batch(c, capB, recvB, true));
-    TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, recvA.k,
-                                  recvA.v, recvA.w, recvB.k, recvB.v, recvB.w,
-                                  tot, tot + 1));
+    TRY(dbspk::frames_unpack_pair(c->stream, frecv, world, P0, P1, recvA,
+                                  recvB, tot, tot + 1));
     HIP_CHECK_ST(dbspk::cache_free(fsend, c->stream));
     HIP_CHECK_ST(dbspk::cache_free(frecv, c->stream));
     return sort_pair_chain(c, recvA, recvB, capA, capB, tot, tot + 1,
@@ -1892,8 +1816,7 @@ static dbsp_status join_vs_trace(dbsp_ctx *c, const DevBatch &delta,
                                  std::vector<DevBatch> &outs) {
     DevBatch o;
     ScopedTimer timer(c, 2, (double)delta.n * 24.0);
-    TRY(dbspk::join_spine_rows(c->stream, delta.k, delta.v, delta.w, delta.n, t,
-                               proj, param, &o.k, &o.v, &o.w, &o.n));
+    TRY(dbspk::join_spine_rows(c->stream, delta, t, proj, param, &o));
     if (o.n > 0) outs.push_back(o);
     else free_batch(c, o);
     return DBSP_OK;
@@ -1974,8 +1897,8 @@ static dbsp_status window_emit(dbsp_ctx *c, const WindowPlan &wp,
     if (total <= 0) return DBSP_OK;
     DevBatch o;
     TRY(alloc_batch(c, total, o, true));
-    TRY(dbspk::window_emit_multi(c->stream, wp.ta, batch.k, batch.v, batch.w,
-                                 wp.table, wp.nreg, total, o.k, o.v, o.w));
+    TRY(dbspk::window_emit_multi(c->stream, wp.ta, batch, wp.table, wp.nreg,
+                                 total, o));
     raw.push_back(o);
     return DBSP_OK;
 }
@@ -2023,8 +1946,7 @@ static dbsp_status map_sorted(dbsp_ctx *c, const DevBatch &in, int mode,
     }
     DevBatch raw;
     TRY(alloc_batch(c, in.n, raw));
-    TRY(dbspk::map_rows(c->stream, in.k, in.v, in.w, in.n, mode, raw.k, raw.v, raw.w));
-    raw.n = in.n;
+    TRY(dbspk::map_rows(c->stream, in, mode, raw));
     TRY(sort_consolidate_batch(c, raw, out));
     return DBSP_OK;
 }
@@ -2054,14 +1976,12 @@ static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
     HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
     HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
     for (auto &b : in_trace.batches)
-        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, b.k, b.w, b.n, acc));
+        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, b, acc, false));
     std::vector<DevBatch> outs;
     // inserts
     DevBatch ins;
     TRY(alloc_batch(c, nk, ins, true));
-    int64_t n_ins = 0;
-    TRY(dbspk::emit_nonzero(c->stream, keys, acc, nk, ins.k, ins.v, ins.w, &n_ins));
-    ins.n = n_ins;
+    TRY(dbspk::emit_nonzero(c->stream, keys, acc, nk, false, &ins));
     if (ins.n > 0) outs.push_back(ins);
     // retractions ARE a join: probing the output trace with (key, _, -1) rows
     // under proj (k, v2) emits exactly (key, old_val, -old_w) — the upsert
@@ -2105,19 +2025,17 @@ static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
                 if (total > 0) {
                     DevBatch o;
                     TRY(alloc_batch(c, total, o, true));
-                    TRY(dbspk::join_emit_prepared(c->stream, keys, dv, dw, nk,
-                                                  t, cnts, offsets, total,
-                                                  DBSP_PROJ_HI_K_LO_V2, 0, o.k,
-                                                  o.v, o.w));
-                    o.n = total;
+                    TRY(dbspk::join_emit_prepared(
+                        c->stream, DevBatch{keys, dv, dw, nk}, t, cnts,
+                        offsets, total, DBSP_PROJ_HI_K_LO_V2, 0, o));
                     outs.push_back(o);
                 }
                 free_batch(c, tmp2);
             } else {
                 DevBatch o;
-                TRY(dbspk::join_spine_rows(c->stream, keys, dv, dw, nk, t,
-                                           DBSP_PROJ_HI_K_LO_V2, 0, &o.k, &o.v,
-                                           &o.w, &o.n));
+                TRY(dbspk::join_spine_rows(c->stream,
+                                           DevBatch{keys, dv, dw, nk}, t,
+                                           DBSP_PROJ_HI_K_LO_V2, 0, &o));
                 if (o.n > 0) outs.push_back(o);
                 else free_batch(c, o);
             }
@@ -2145,19 +2063,15 @@ static dbsp_status agg_linear_spine_f64(dbsp_ctx *c, const DevBatch &delta,
     uint64_t *keys = nullptr;
     int64_t nk = 0;
     TRY(dbspk::unique_keys(c->stream, delta.k, delta.n, &keys, &nk));
-    double *acc;
+    int64_t *acc;  // f64 sums as bit patterns
     HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
     HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
     for (auto &b : in_trace.batches)
-        TRY(dbspk::agg_sum_batch_f64(c->stream, keys, nk, b.k,
-                                     (const double *)b.w, b.n, acc));
+        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, b, acc, true));
     std::vector<DevBatch> outs;
     DevBatch ins;
     TRY(alloc_batch(c, nk, ins, true));
-    int64_t n_ins = 0;
-    TRY(dbspk::emit_nonzero_f64(c->stream, keys, acc, nk, ins.k, ins.v, ins.w,
-                                &n_ins));
-    ins.n = n_ins;
+    TRY(dbspk::emit_nonzero(c->stream, keys, acc, nk, true, &ins));
     if (ins.n > 0) outs.push_back(ins);
     // retractions: probe the (i64-weighted) output trace with (key, _, -1)
     // rows under proj (k, v2) — the upsert contract (upsert.rs:180-195)
@@ -2176,9 +2090,8 @@ static dbsp_status agg_linear_spine_f64(dbsp_ctx *c, const DevBatch &delta,
             HIP_CHECK_ST(hipMemsetAsync(dv, 0, nk * 8, c->stream));
             HIP_CHECK_ST(hipMemsetAsync(dw, 0xFF, nk * 8, c->stream));  // -1
             DevBatch o;
-            TRY(dbspk::join_spine_rows(c->stream, keys, dv, dw, nk, t,
-                                       DBSP_PROJ_HI_K_LO_V2, 0, &o.k, &o.v,
-                                       &o.w, &o.n));
+            TRY(dbspk::join_spine_rows(c->stream, DevBatch{keys, dv, dw, nk}, t,
+                                       DBSP_PROJ_HI_K_LO_V2, 0, &o));
             if (o.n > 0) outs.push_back(o);
             else free_batch(c, o);
             free_batch(c, tmp);
@@ -2267,8 +2180,9 @@ static dbsp_status spine_rounds(dbsp_ctx *c, Spine *const *sps, int ns,
             }
             ma.d_len = c->d_len + LEN_ROUND;
             mm.d_len = c->d_len + LEN_ROUND + ma.np;
-            if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma));
-            if (mm.np > 0) TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid));
+            if (ma.np > 0) TRY(dbspk::merge_small_batch(c->stream, ma, false));
+            if (mm.np > 0)
+                TRY(dbspk::merge_mid_batch(c->stream, mm, c->d_mid, false));
             TRY(read_len(c, LEN_ROUND, ma.np + mm.np, /*sync=*/false));
             if (defer && hook && !*hook_fired) {
                 (void)hipEventRecord(c->ev_insert, c->stream);
@@ -2400,8 +2314,8 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     uint64_t *rb = nullptr;
     int64_t n_gather = 0, n_affected = 0;
     int err = 0;
-    TRY(dbspk::roll_ranges(c->stream, delta.k, delta.v, n, before, after, &rb,
-                           &n_gather, &n_affected, &err));
+    TRY(dbspk::roll_ranges(c->stream, delta, before, after, &rb, &n_gather,
+                           &n_affected, &err));
     if (err) return DBSP_ERR_INVALID;
     {
         DevBatch cpy;
@@ -2413,17 +2327,15 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     // gather + consolidate the slice of the input integral
     DevBatch raw, slice;
     TRY(dbspk::range_gather(c->stream, rb, rb + n, rb + 2 * n, n_gather,
-                            trace_args_of(in_sp), 0, 1, &raw.k, &raw.v, &raw.w,
-                            &raw.n));
+                            trace_args_of(in_sp), 0, 1, &raw));
     int64_t moved = raw.n;
     TRY(sort_consolidate_batch(c, raw, slice));
     // insertions
     std::vector<DevBatch> parts;
     if (slice.n > 0) {
         DevBatch ins;
-        TRY(dbspk::roll_eval_rows(c->stream, slice.k, slice.v, slice.w,
-                                  slice.n, delta.k, delta.v, n, before, after,
-                                  &ins.k, &ins.v, &ins.w, &ins.n));
+        TRY(dbspk::roll_eval_rows(c->stream, slice, delta, before, after,
+                                  &ins));
         moved += ins.n;
         if (ins.n > 0) parts.push_back(ins);
     }
@@ -2432,8 +2344,7 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     {
         DevBatch ret;
         TRY(dbspk::range_gather(c->stream, rb + 3 * n, rb + 4 * n, rb + 5 * n,
-                                n_affected, trace_args_of(out_sp), 1, -1,
-                                &ret.k, &ret.v, &ret.w, &ret.n));
+                                n_affected, trace_args_of(out_sp), 1, -1, &ret));
         moved += 2 * ret.n;
         if (ret.n > 0) parts.push_back(ret);
     }
@@ -2454,7 +2365,7 @@ static dbsp_status truncate_batch(dbsp_ctx *c, const DevBatch &in, int mode,
     out = DevBatch{};
     if (in.n == 0) return DBSP_OK;
     return dbspk::truncate_spine(c->stream, trace_args_one(in), mode, bound,
-                                 &out.k, &out.v, &out.w, &out.n);
+                                 &out);
 }
 
 dbsp_status RollingOp::step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
@@ -2485,10 +2396,8 @@ dbsp_status RollingOp::sweep(dbsp_ctx *c, int mode) {
     if (nb > 0) {
         TraceArgs t{};  // every batch, empty ones too: outputs are per batch
         for (auto &b : sp.batches) trace_push(t, b);
-        uint64_t *ok[MAX_TRACE_BATCHES], *ov[MAX_TRACE_BATCHES];
-        int64_t *ow[MAX_TRACE_BATCHES], on[MAX_TRACE_BATCHES];
-        TRY(dbspk::truncate_spine(c->stream, t, mode, lower_bound(), ok, ov,
-                                  ow, on));
+        DevBatch kept[MAX_TRACE_BATCHES];
+        TRY(dbspk::truncate_spine(c->stream, t, mode, lower_bound(), kept));
         std::vector<DevBatch> old;
         old.swap(sp.batches);
         for (auto &b : old) free_batch(c, b);
@@ -2498,8 +2407,7 @@ dbsp_status RollingOp::sweep(dbsp_ctx *c, int mode) {
         // retraction/insertion pairs still waiting for a merge.  One batch
         // satisfies size[i] >= 2 * size[i+1] trivially.
         for (int b = 0; b < nb; b++)
-            if (on[b] > 0)
-                sp.batches.push_back(DevBatch{ok[b], ov[b], ow[b], on[b]});
+            if (kept[b].n > 0) sp.batches.push_back(kept[b]);
         TRY(sp.consolidate_all(c));
     }
     (mode == 0 ? in_live : out_live) = sp.total();
@@ -2639,7 +2547,7 @@ static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
         uint64_t x = 0;
         if (d.n > 0) {
             uint64_t mm[4];
-            TRY(dbspk::minmax_rows(c->stream, d.k, d.v, d.n, mm));
+            TRY(dbspk::minmax_rows(c->stream, d, mm));
             x = mm[3] > e->roll_lateness ? mm[3] - e->roll_lateness : 0;
         }
         st = e->roll.step_wm(c, d, x, e->output);
@@ -2897,15 +2805,13 @@ static dbsp_status q3_emit_explicit(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
         if (pl.small) {
             int64_t total = slot_totals[pl.slot];
             if (total <= 0) continue;
-            TRY(dbspk::join_emit_prepared(c->stream, d.k, d.v, d.w, d.n, pl.t,
-                                          pl.cnts, pl.offsets, total, pl.proj,
-                                          0, comb.k + base, comb.v + base,
-                                          comb.w + base));
+            TRY(dbspk::join_emit_prepared(
+                c->stream, d, pl.t, pl.cnts, pl.offsets, total, pl.proj, 0,
+                DevBatch{comb.k + base, comb.v + base, comb.w + base, total}));
             base += total;
         } else {
             DevBatch o;
-            TRY(dbspk::join_spine_rows(c->stream, d.k, d.v, d.w, d.n, pl.t,
-                                       pl.proj, 0, &o.k, &o.v, &o.w, &o.n));
+            TRY(dbspk::join_spine_rows(c->stream, d, pl.t, pl.proj, 0, &o));
             if (o.n > 0) outs.push_back(o);
             else free_batch(c, o);
         }
@@ -2954,7 +2860,7 @@ static dbsp_status final_begin(dbsp_engine *e, std::vector<DevBatch> &outs,
     sa.nb = 1;
     sort_slot(sa, 0, cat, scratch, e->out_store);
     sa.d_len = c->d_len + L_FINAL;
-    TRY(dbspk::sort_cons_small_batch(c->stream, sa));
+    TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
     return read_len(c, L_FINAL, 1, /*sync=*/false);
 }
 // second half, after the inserts: publish the store with the length that
@@ -3180,7 +3086,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
             HIP_CHECK_ST(hipEventRecord(c->ev_fork[evi], c->stream));
             HIP_CHECK_ST(hipStreamWaitEvent(ss, c->ev_fork[evi], 0));
         }
-        TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid));
+        TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid, false));
     }
     TRY(read_len_to(c, sb + L_HEAD, sb + L_HEAD, L_HEAD_N, /*sync=*/false, ss));
     HIP_CHECK_ST(hipEventRecord(c->ev_tick[evi], ss));
@@ -3622,8 +3528,9 @@ static dbsp_status q5_front(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
                             DevBatch &raw0, DevBatch &raw1) {
     dbsp_ctx *c = e->ctx;
     TRY(flatmap_chain(e, d_ev, n, raw0, raw1));
+    // raw0.n is the capacity here; the length is still at d_len[L_RAW]
     return dbspk::minmax_rows_chain(
-        c->stream, raw0.k, raw0.v, n > 0 ? n : 1, c->d_len + L_RAW,
+        c->stream, raw0, c->d_len + L_RAW,
         (unsigned long long *)(c->d_len + L_MINMAX));
 }
 
@@ -3669,9 +3576,8 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
                 DevBatch res;
                 TRY(alloc_batch(c, n0, res));
                 TRY(dbspk::sort_cons_dense_chain(
-                    c->stream, raw0.k, raw0.v, raw0.w, n0, mm[0], mm[1],
-                    (int64_t)(kr + 1), (int64_t)(vr + 1), res.k, res.v, res.w,
-                    c->d_len + L_DENSE));
+                    c->stream, raw0, mm[0], mm[1], (int64_t)(kr + 1),
+                    (int64_t)(vr + 1), res, c->d_len + L_DENSE));
                 free_batch(c, raw0);
                 dBT = res;
                 dBT.n = -1;
@@ -3770,10 +3676,8 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         HIP_CHECK_ST(dbspk::cache_malloc((void **)&d_unit, 8, c->stream));
         HIP_CHECK_ST(hipMemsetAsync(d_unit, 0, 8, c->stream));
         DevBatch raw;
-        TRY(dbspk::agg_max_upsert_rows(
-            c->stream, d_unit, 1, e->maxin_int.k, e->maxin_int.v, e->maxin_int.w,
-            e->maxin_int.n, e->maxout_int.k, e->maxout_int.v, e->maxout_int.w,
-            e->maxout_int.n, &raw.k, &raw.v, &raw.w, &raw.n));
+        TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_MAX, d_unit, 1,
+                                   e->maxin_int, e->maxout_int, &raw));
         HIP_CHECK_ST(dbspk::cache_free(d_unit, c->stream));
         TRY(sort_consolidate_batch(c, raw, dMaxOut));
         DevBatch m2;
@@ -3805,10 +3709,8 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     }
     if (dBC.n > 0 && e->maxz_int.n > 0) {
         DevBatch o;
-        TRY(dbspk::join_rows(c->stream, dBC.k, dBC.v, dBC.w, dBC.n,
-                             e->maxz_int.k, e->maxz_int.v, e->maxz_int.w,
-                             e->maxz_int.n, DBSP_PROJ_HI_V1_LO_K, 0, &o.k, &o.v,
-                             &o.w, &o.n));
+        TRY(dbspk::join_rows(c->stream, dBC, e->maxz_int, DBSP_PROJ_HI_V1_LO_K,
+                             0, &o));
         if (o.n > 0) outs.push_back(o);
         else free_batch(c, o);
     }
@@ -3863,16 +3765,9 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
     DevBatch raw;
     {
         ScopedTimer timer(c, 3, 0.0);
-        if (mode == 1)
-            TRY(dbspk::agg_max_upsert_rows(
-                c->stream, keys, nk, gathered.k, gathered.v, gathered.w,
-                gathered.n, out_int.k, out_int.v, out_int.w, out_int.n,
-                &raw.k, &raw.v, &raw.w, &raw.n));
-        else
-            TRY(dbspk::agg_last10_upsert_rows(
-                c->stream, keys, nk, gathered.k, gathered.v, gathered.w,
-                gathered.n, out_int.k, out_int.v, out_int.w, out_int.n,
-                &raw.k, &raw.v, &raw.w, &raw.n));
+        TRY(dbspk::agg_upsert_rows(
+            c->stream, mode == 1 ? dbspk::AGG_MAX : dbspk::AGG_LAST10, keys,
+            nk, gathered, out_int, &raw));
     }
     free_batch(c, gathered);
     HIP_CHECK_ST(dbspk::cache_free(keys, c->stream));
@@ -3929,9 +3824,7 @@ static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     if (dWin.n > 0) {
         DevBatch wraw, dAvgIn;
         TRY(alloc_batch(c, dWin.n, wraw, true));
-        TRY(dbspk::map_rows(c->stream, dWin.k, dWin.v, dWin.w, dWin.n, 5,
-                            wraw.k, wraw.v, wraw.w));
-        wraw.n = dWin.n;
+        TRY(dbspk::map_rows(c->stream, dWin, 5, wraw));
         TRY(sort_consolidate_batch(c, wraw, dAvgIn));
         free_batch(c, dWin);
         if (dAvgIn.n > 0) {
@@ -3993,9 +3886,7 @@ static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         // map_index (q6.rs:92-94): key by seller, val (auction<<27)|price
         DevBatch fraw, dFoldIn;
         TRY(alloc_batch(c, dWin.n, fraw, true));
-        TRY(dbspk::map_rows(c->stream, dWin.k, dWin.v, dWin.w, dWin.n, 7,
-                            fraw.k, fraw.v, fraw.w));
-        fraw.n = dWin.n;
+        TRY(dbspk::map_rows(c->stream, dWin, 7, fraw));
         TRY(sort_consolidate_batch(c, fraw, dFoldIn));
         free_batch(c, dWin);
         if (dFoldIn.n > 0) {
@@ -4044,8 +3935,7 @@ extern "C" dbsp_status dbsp_engine_c5_init(dbsp_engine *e, int64_t n_trace,
     DevBatch tr;
     TRY(alloc_batch(c, n_trace, tr));
     // trace keys 5i + h%4 (sorted unique, ~0.8 keys/int density), f64 vals
-    TRY(dbspk::c5_gen_rows(c->stream, n_trace, 5, 4, seed, 0, tr.k, tr.v,
-                           tr.w));
+    TRY(dbspk::c5_gen_rows(c->stream, tr, 5, 4, seed, 0));
     TRY(e->c5_trace.insert(c, tr));
     e->c5_n_delta = n_delta;
     e->c5_seed = seed;
@@ -4068,10 +3958,9 @@ static dbsp_status c5_step(dbsp_engine *e, int64_t lo, int64_t hi) {
     // tick's delta: device-generated sorted-unique rows, v = 0, w = +1
     DevBatch delta;
     TRY(alloc_batch(c, nd, delta));
-    TRY(dbspk::c5_gen_rows(c->stream, nd, e->c5_delta_stride,
+    TRY(dbspk::c5_gen_rows(c->stream, delta, e->c5_delta_stride,
                            e->c5_delta_stride - 1,
-                           e->c5_seed + 0x9E3779B97F4A7C15ull * (tick + 1), 1,
-                           delta.k, delta.v, delta.w));
+                           e->c5_seed + 0x9E3779B97F4A7C15ull * (tick + 1), 1));
     // 1. join vs the trace spine, carrying the trace-side f64 val
     std::vector<DevBatch> outs;
     TRY(join_vs_spine(c, delta, e->c5_trace, DBSP_PROJ_HI_K_LO_V2, 0, outs));
@@ -4086,10 +3975,8 @@ static dbsp_status c5_step(dbsp_engine *e, int64_t lo, int64_t hi) {
         TRY(alloc_batch(c, cat.n, weighed, true));
         {
             ScopedTimer t(c, 3, 0.0);
-            TRY(dbspk::map_rows(c->stream, cat.k, cat.v, cat.w, cat.n, 4,
-                                weighed.k, weighed.v, weighed.w));
+            TRY(dbspk::map_rows(c->stream, cat, 4, weighed));
         }
-        weighed.n = cat.n;
         free_batch(c, cat);
         dbsp_batch ob{};
         TRY(dbsp_sort_consolidate_f64(c, weighed.k, weighed.v,

@@ -223,6 +223,12 @@ void cache_small_set(bool on, hipStream_t s) {
         }                                                                 \
     } while (0)
 
+#define TRY_K(x)                                                          \
+    do {                                                                  \
+        dbsp_status st_ = (x);                                            \
+        if (st_ != DBSP_OK) return st_;                                   \
+    } while (0)
+
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------------------
@@ -1130,17 +1136,11 @@ __global__ void k_seg_collect_f64(const uint64_t *k, const uint64_t *v,
     }
 }
 
-__global__ void k_nonzero_flags_f64(const double *w, int64_t n,
-                                    uint64_t *flags) {
+template <typename W>
+__global__ void k_nonzero_flags(const W *w, int64_t n, uint64_t *flags) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x)
-        flags[i] = w[i] != 0.0;  // -0.0 compares equal to 0.0: dropped
-}
-
-__global__ void k_nonzero_flags(const int64_t *w, int64_t n, uint64_t *flags) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        flags[i] = w[i] != 0;
+        flags[i] = w[i] != W(0);  // f64: -0.0 compares equal to 0.0: dropped
 }
 
 __global__ void k_compact(const uint64_t *k, const uint64_t *v, const int64_t *w,
@@ -1155,6 +1155,20 @@ __global__ void k_compact(const uint64_t *k, const uint64_t *v, const int64_t *w
             ow[pos] = w[i];
         }
     }
+}
+
+// distinct keys of a sorted batch: the key-only head flags and compact
+__global__ void k_key_head_flags(const uint64_t *k, int64_t n, uint64_t *flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        flags[i] = (i == 0) || k[i] != k[i - 1];
+}
+
+__global__ void k_compact_keys(const uint64_t *k, const uint64_t *flags,
+                               const uint64_t *fscan, int64_t n, uint64_t *ok) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        if (flags[i]) ok[fscan[i]] = k[i];
 }
 
 // ---------------------------------------------------------------------------
@@ -1469,7 +1483,7 @@ typedef __attribute__((address_space(1))) unsigned long long gu64_t;
 // emit); mode 0 reads each input byte once but its lookback protocol costs
 // more than the count re-read at 1B-row scale (measured: granule-load
 // throughput-bound — wider windows and preloading both made it slower).
-template <typename W, int TILE, int MODE, bool SKIP_LB = false>
+template <typename W, int TILE, int MODE>
 __global__ __launch_bounds__(MP_THREADS, 4) void k_mp_merge_onepass(
     const uint64_t *ak, const uint64_t *av, const W *aw, int64_t na,
     const uint64_t *bk, const uint64_t *bv, const W *bw, int64_t nb,
@@ -1595,17 +1609,6 @@ __global__ __launch_bounds__(MP_THREADS, 4) void k_mp_merge_onepass(
     if (MODE == 2) {
         // emit phase: the device scan already turned counts into offsets
         if (tid == 0) sh_prefix = state[vb];
-    } else if (SKIP_LB) {
-        // timing diagnostic ONLY (DBSP_MERGE_NOLB=1): measures the kernel
-        // without the lookback protocol; outputs land at uncompacted per-tile
-        // offsets (store pattern representative, results wrong by design)
-        if (tid == 0) {
-            gu64_t *g = (gu64_t *)(state + 2);
-            __hip_atomic_store(&g[vb],
-                               ((unsigned long long)block_cnt << 2) | 2ull,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            sh_prefix = (unsigned long long)(vb * TILE);
-        }
     } else if (tid < WAVE) {
         gu64_t *g = (gu64_t *)(state + 2);
         if (tid == 0)
@@ -1769,7 +1772,7 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_small(MergeArgs args)
 // fixed-grid multi-workgroup merge with DEVICE-side b length (the in-train
 // accumulator fold: the tick's delta length is only known on device).  Two
 // phases over MERGE_MID_WGS workgroups per pair: count writes per-WG output
-// counts to scratch; emit recomputes each WG's prefix from the tiny counts
+// counts to scratch; emit computes each WG's prefix from the tiny counts
 // array (no separate scan launch) and writes its segment.  Equal (k, v)
 // pairs never split across WGs (adjust_split), so per-segment consolidation
 // is exact.
@@ -1777,135 +1780,15 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_small(MergeArgs args)
 static_assert(MERGE_MID_SCRATCH == MERGE_MID_WGS + 1,
               "scratch layout mismatch with kernels_iface.hpp");
 
-template <typename W>
-__global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_mid_count(
-        MergeArgs args, int64_t *scratch /* np * (MERGE_MID_WGS+1) */) {
-    const int p = blockIdx.y;
-    const int wg = blockIdx.x;
-    int64_t *cnt_row = scratch + (int64_t)p * (MERGE_MID_WGS + 1);
-    const int64_t na = args.na[p];
-    const int64_t nb = args.dnb[p] ? *args.dnb[p] : args.nb[p];
-    if (na < 0 || nb < 0) {
-        if (threadIdx.x == 0) cnt_row[MERGE_MID_WGS] = -1;
-        return;
-    }
-    if (threadIdx.x == 0 && wg == 0) cnt_row[MERGE_MID_WGS] = 0;
-    const uint64_t *ak = args.ak[p], *av = args.av[p];
-    const W *aw = (const W *)args.aw[p];
-    const uint64_t *bk = args.bk[p], *bv = args.bv[p];
-    const W *bw = (const W *)args.bw[p];
-    const int64_t total = na + nb;
-    const int64_t per_wg = (total + MERGE_MID_WGS - 1) / MERGE_MID_WGS;
-    const int64_t w0 = min((int64_t)wg * per_wg, total);
-    const int64_t w1 = min(w0 + per_wg, total);
-    const int64_t items = (w1 - w0 + FUSE_THREADS - 1) / FUSE_THREADS;
-    int64_t d0 = min(w0 + (int64_t)threadIdx.x * items, w1);
-    int64_t d1 = min(d0 + items, w1);
-    int64_t ai, bi, ae, be;
-    merge_path(ak, av, na, bk, bv, nb, d0, ai, bi);
-    adjust_split(ak, av, bk, bv, na, nb, ai, bi);
-    merge_path(ak, av, na, bk, bv, nb, d1, ae, be);
-    adjust_split(ak, av, bk, bv, na, nb, ae, be);
-    uint32_t cnt = 0;
-    {
-        int64_t i = ai, j = bi;
-        while (i < ae || j < be) {
-            if (i < ae && j < be && row_eq(ak[i], av[i], bk[j], bv[j])) {
-                if (aw[i] + bw[j] != (W)0) cnt++;
-                i++; j++;
-            } else if (j >= be || (i < ae && row_lt(ak[i], av[i], bk[j], bv[j]))) {
-                cnt++; i++;
-            } else {
-                cnt++; j++;
-            }
-        }
-    }
-    __shared__ uint32_t wave_tot[FUSE_THREADS / WAVE + 1];
-    uint32_t wg_tot;
-    (void)fuse_scan(cnt, wave_tot, &wg_tot);
-    if (threadIdx.x == 0) cnt_row[wg] = (int64_t)wg_tot;
-}
-
-template <typename W>
-__global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_mid_emit(
-        MergeArgs args, const int64_t *scratch) {
-    const int p = blockIdx.y;
-    const int wg = blockIdx.x;
-    const int64_t *cnt_row = scratch + (int64_t)p * (MERGE_MID_WGS + 1);
-    int64_t *out_len = args.d_len + p;
-    if (cnt_row[MERGE_MID_WGS] < 0) {
-        if (threadIdx.x == 0 && wg == 0) *out_len = -1;
-        return;
-    }
-    const int64_t na = args.na[p];
-    const int64_t nb = args.dnb[p] ? *args.dnb[p] : args.nb[p];
-    const uint64_t *ak = args.ak[p], *av = args.av[p];
-    const W *aw = (const W *)args.aw[p];
-    const uint64_t *bk = args.bk[p], *bv = args.bv[p];
-    const W *bw = (const W *)args.bw[p];
-    uint64_t *ok = args.ok[p], *ov = args.ov[p];
-    W *ow = (W *)args.ow[p];
-    int64_t base = 0, all = 0;
-    for (int g = 0; g < MERGE_MID_WGS; g++) {
-        if (g < wg) base += cnt_row[g];
-        all += cnt_row[g];
-    }
-    if (threadIdx.x == 0 && wg == 0) *out_len = all;
-    const int64_t total = na + nb;
-    const int64_t per_wg = (total + MERGE_MID_WGS - 1) / MERGE_MID_WGS;
-    const int64_t w0 = min((int64_t)wg * per_wg, total);
-    const int64_t w1 = min(w0 + per_wg, total);
-    const int64_t items = (w1 - w0 + FUSE_THREADS - 1) / FUSE_THREADS;
-    int64_t d0 = min(w0 + (int64_t)threadIdx.x * items, w1);
-    int64_t d1 = min(d0 + items, w1);
-    int64_t ai, bi, ae, be;
-    merge_path(ak, av, na, bk, bv, nb, d0, ai, bi);
-    adjust_split(ak, av, bk, bv, na, nb, ai, bi);
-    merge_path(ak, av, na, bk, bv, nb, d1, ae, be);
-    adjust_split(ak, av, bk, bv, na, nb, ae, be);
-    uint32_t cnt = 0;
-    {
-        int64_t i = ai, j = bi;
-        while (i < ae || j < be) {
-            if (i < ae && j < be && row_eq(ak[i], av[i], bk[j], bv[j])) {
-                if (aw[i] + bw[j] != (W)0) cnt++;
-                i++; j++;
-            } else if (j >= be || (i < ae && row_lt(ak[i], av[i], bk[j], bv[j]))) {
-                cnt++; i++;
-            } else {
-                cnt++; j++;
-            }
-        }
-    }
-    __shared__ uint32_t wave_tot[FUSE_THREADS / WAVE + 1];
-    uint32_t seg_tot;
-    uint32_t off32 = fuse_scan(cnt, wave_tot, &seg_tot);
-    int64_t off = base + (int64_t)off32;
-    {
-        int64_t i = ai, j = bi;
-        while (i < ae || j < be) {
-            if (i < ae && j < be && row_eq(ak[i], av[i], bk[j], bv[j])) {
-                W s = aw[i] + bw[j];
-                if (s != (W)0) { ok[off] = ak[i]; ov[off] = av[i]; ow[off] = s; off++; }
-                i++; j++;
-            } else if (j >= be || (i < ae && row_lt(ak[i], av[i], bk[j], bv[j]))) {
-                ok[off] = ak[i]; ov[off] = av[i]; ow[off] = aw[i]; off++; i++;
-            } else {
-                ok[off] = bk[j]; ov[off] = bv[j]; ow[off] = bw[j]; off++; j++;
-            }
-        }
-    }
-}
-
-// single-launch variant: count, one-shot cross-WG barrier, emit.  The grid
-// is tiny (MERGE_MID_WGS x np <= 128 workgroups, all co-resident), so every
-// WG publishes its count tagged with the launch generation and spins for
-// its pair's 32 peers — a single barrier between uniform-work peers, NOT a
+// One launch: count, one-shot cross-WG barrier, emit.  The grid is tiny
+// (MERGE_MID_WGS x np <= 128 workgroups, all co-resident), so every WG
+// publishes its count tagged with the launch generation and spins for its
+// pair's 32 peers — a single barrier between uniform-work peers, NOT a
 // serial lookback chain.  Each thread keeps its merge-path bounds in
-// registers across the barrier, so the emit phase skips the splits the
-// two-launch version recomputes.  Generation tags make the persistent
-// scratch self-cleaning (no memset launch); a stale match would need a
-// pair row untouched for exactly 2^32 launches.
+// registers across the barrier, so the emit phase recomputes no split.
+// Generation tags make the persistent scratch self-cleaning (no memset
+// launch); a stale match would need a pair row untouched for exactly 2^32
+// launches.
 template <typename W>
 __global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_mid_fused(
         MergeArgs args, int64_t *scratch, uint32_t gen) {
@@ -2045,72 +1928,6 @@ __global__ void k_join_count_multi(const uint64_t *dk, int64_t nd, TraceArgs t,
     }
 }
 
-
-// ---------------------------------------------------------------------------
-// chained join emit: per-plan output bases from the device-side count totals
-// (so the emits and the output consolidate launch before the tick sync), and
-// the emit kernel itself reads every size from device memory.  flag != 0
-// (a lost speculation upstream, or the combined output exceeding the
-// capacity buffer) makes every consumer bail; the host re-emits explicitly.
-// ---------------------------------------------------------------------------
-__global__ void k_emit_bases(const int64_t *totals, int np, int64_t cap,
-                             int64_t *bases, int64_t *out_total,
-                             int64_t *out_flag) {
-    int64_t acc = 0;
-    int ok = 1;
-    for (int i = 0; i < np; i++) {
-        const int64_t t = totals[i];
-        if (t < 0) { ok = 0; break; }
-        bases[i] = acc;
-        acc += t;
-    }
-    if (acc > cap) ok = 0;
-    *out_total = ok ? acc : -1;
-    *out_flag = ok ? 0 : 1;
-}
-
-__global__ void k_join_emit_chain(const uint64_t *dk, const uint64_t *dv,
-                                  const int64_t *dw, const int64_t *nd_dev,
-                                  TraceArgs t, const int64_t *tn_dev,
-                                  const uint32_t *cnts,
-                                  const uint64_t *offsets,
-                                  const int64_t *total_dev,
-                                  const int64_t *base_dev,
-                                  const int64_t *flag_dev, int proj,
-                                  uint64_t param, uint64_t *ok, uint64_t *ov,
-                                  int64_t *ow) {
-    if (*flag_dev != 0) return;
-    const int64_t nd = *nd_dev;
-    const int64_t n_out = *total_dev;
-    if (nd <= 0 || n_out <= 0) return;
-    const int64_t base = *base_dev;
-    const int64_t tn0 = tn_dev ? *tn_dev : t.n[0];
-    for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < n_out;
-         o += (int64_t)gridDim.x * blockDim.x) {
-        int64_t lo = 0, hi = nd;
-        while (lo < hi) {
-            int64_t mid = (lo + hi) / 2;
-            if (offsets[mid] <= (uint64_t)o) lo = mid + 1; else hi = mid;
-        }
-        int64_t i = lo - 1;
-        int64_t j = o - (int64_t)offsets[i];
-        int b = 0;
-        while (j >= (int64_t)cnts[i * t.nb + b]) {
-            j -= cnts[i * t.nb + b];
-            b++;
-        }
-        uint64_t key = dk[i];
-        const int64_t tb_n = b == 0 ? tn0 : t.n[b];
-        int64_t start = lower_bound_k(t.k[b], tb_n, key);
-        int64_t ti = start + j;
-        uint64_t hi_o, lo_o;
-        const bool valid =
-            proj_out(proj, param, key, dv[i], t.v[b][ti], hi_o, lo_o);
-        ok[base + o] = hi_o;
-        ov[base + o] = lo_o;
-        ow[base + o] = valid ? dw[i] * t.w[b][ti] : 0;
-    }
-}
 
 __global__ void k_join_emit_multi(const uint64_t *dk, const uint64_t *dv,
                                   const int64_t *dw, int64_t nd, TraceArgs t,
@@ -2495,6 +2312,41 @@ __global__ void k_agg_emit(const uint64_t *keys, int64_t nd,
         // retractions from the output trace (upsert.rs:180-195)
         for (uint64_t t = ostart[i]; emitted < cnt; t++, emitted++, pos++) {
             rk[pos] = key; rv[pos] = ov_[t]; rw[pos] = -ow_[t];
+        }
+    }
+}
+
+// multi-batch linear aggregate (spine batches summed; linear op): per-key
+// weight sums of one batch added into acc.  f64 sums run in batch-position
+// order (deterministic).
+template <typename W>
+__global__ void k_agg_sum(const uint64_t *keys, int64_t nd, const uint64_t *ik,
+                          const W *iw, int64_t ni, W *acc) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t key = keys[i];
+        int64_t lo = lower_bound_k(ik, ni, key);
+        int64_t hi = upper_bound_k(ik, ni, key);
+        W sum = 0;
+        for (int64_t t = lo; t < hi; t++) sum += iw[t];
+        acc[i] += sum;
+    }
+}
+
+// emit (key, bits(sum), +1) for sum != 0 (f64: WeightedCount returns None for
+// a zero aggregate — aggregate/mod.rs:129-156 with R = F64)
+template <typename W>
+__global__ void k_emit_nonzero(const uint64_t *keys, const W *acc, int64_t nd,
+                               uint64_t *ctr, uint64_t *ok, uint64_t *ov,
+                               int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (acc[i] != W(0)) {
+            uint64_t p = atomicAdd((unsigned long long *)ctr, 1ull);
+            ok[p] = keys[i];
+            W a = acc[i];
+            ov[p] = *(const uint64_t *)&a;
+            ow[p] = 1;
         }
     }
 }
@@ -3004,6 +2856,70 @@ __global__ void k_map(const uint64_t *k, const uint64_t *v, const int64_t *w,
 
 namespace dbspk {
 
+// ---------------------------------------------------------------------------
+// Scoped scratch: device buffers from the big-buffer cache, bound to a stream
+// and returned to it in allocation order when the scope ends — on every
+// return path, so an error return leaks nothing into the free-list
+// accounting.  Result columns are carved through the scope too and stay its
+// property until the wrapper hands them over (keep / give_rows).
+// ---------------------------------------------------------------------------
+class Scratch {
+  public:
+    explicit Scratch(hipStream_t s) : s_(s) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() {
+        for (int i = 0; i < n_; i++) (void)cache_free(p_[i], s_);
+    }
+    template <typename T>
+    hipError_t get(T **out, size_t bytes) {
+        if (n_ == CAP) return hipErrorOutOfMemory;
+        hipError_t e = cache_malloc((void **)out, bytes, s_);
+        if (e == hipSuccess) p_[n_++] = *out;
+        return e;
+    }
+    // free p now: an early release that later allocations count on
+    hipError_t release(void *p) { return cache_free(take(p), s_); }
+    // the caller owns p from here on
+    void keep(void *p) { (void)take(p); }
+    hipStream_t stream() const { return s_; }
+
+  private:
+    void *take(void *p) {
+        for (int i = 0; i < n_; i++)
+            if (p_[i] == p) p_[i] = nullptr;
+        return p;
+    }
+    // the most: truncate_spine's counts plus three columns per spine batch
+    static constexpr int CAP = 3 * MAX_TRACE_BATCHES + 8;
+    hipStream_t s_;
+    void *p_[CAP];
+    int n_ = 0;
+};
+
+// the result carve: three columns of n rows (8 B pad each), the scope's until
+// give_rows
+static dbsp_status alloc_rows(Scratch &sc, int64_t n, Rows *r) {
+    HIP_CHECK(sc.get(&r->k, n * sizeof(uint64_t) + 8));
+    HIP_CHECK(sc.get(&r->v, n * sizeof(uint64_t) + 8));
+    HIP_CHECK(sc.get(&r->w, n * sizeof(int64_t) + 8));
+    r->n = n;
+    return DBSP_OK;
+}
+// success: the caller takes r's columns
+static dbsp_status give_rows(Scratch &sc, const Rows &r, Rows *out) {
+    sc.keep(r.k);
+    sc.keep(r.v);
+    sc.keep(r.w);
+    *out = r;
+    return DBSP_OK;
+}
+// the empty result
+static dbsp_status no_rows(Rows *out) {
+    *out = Rows{};
+    return DBSP_OK;
+}
+
 dbsp_status scan_excl(hipStream_t s, const uint64_t *in, uint64_t *out,
                       int64_t n, uint64_t *h_total) {
     return scan_exclusive(s, in, out, n, h_total);
@@ -3046,33 +2962,35 @@ __global__ void k_c5_gen(int64_t n, uint64_t stride, uint64_t jitter,
     }
 }
 
-dbsp_status c5_gen_rows(hipStream_t s, int64_t n, uint64_t stride,
-                        uint64_t jitter, uint64_t seed, int val_mode,
-                        uint64_t *k, uint64_t *v, int64_t *w) {
-    if (n <= 0) return DBSP_OK;
-    k_c5_gen<<<grid_for(n), BLK, 0, s>>>(n, stride, jitter, seed, val_mode, k,
-                                         v, w);
+dbsp_status c5_gen_rows(hipStream_t s, const Rows &out, uint64_t stride,
+                        uint64_t jitter, uint64_t seed, int val_mode) {
+    if (out.n <= 0) return DBSP_OK;
+    k_c5_gen<<<grid_for(out.n), BLK, 0, s>>>(out.n, stride, jitter, seed,
+                                             val_mode, out.k, out.v, out.w);
     return DBSP_OK;
 }
 
-// sort rows by (k major, v minor); ping-pong scratch must hold n rows
-// (kk2/vv2/ww2).  Skips byte passes above the significant bytes of max(k)/max(v).
-dbsp_status sort_rows(hipStream_t s, uint64_t *kk, uint64_t *vv, int64_t *ww,
-                      int64_t n, uint64_t *kk2, uint64_t *vv2, int64_t *ww2,
+// sort rows by (k major, v minor); ping-pong scratch must hold rows.n rows.
+// Skips byte passes above the significant bytes of max(k)/max(v).
+dbsp_status sort_rows(hipStream_t s, const Rows &rows, const Rows &scratch,
                       bool *result_in_scratch) {
     *result_in_scratch = false;
+    const int64_t n = rows.n;
     if (n <= 1) return DBSP_OK;
     // significant bytes from max values
-    uint64_t *d_max;
-    HIP_CHECK(dbspk::cache_malloc((void **)&d_max, 4 * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(d_max, 0, 2 * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(d_max + 2, 0xFF, 2 * sizeof(uint64_t), s));
-    k_minmax_u64<<<grid_for(n), BLK, 0, s>>>(kk, vv, n, d_max);
     uint64_t h_max[4];
-    HIP_CHECK(hipMemcpyAsync(h_max, d_max, 4 * sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(dbspk::cache_free(d_max, s));
+    {
+        // its own scope: d_max is back in the list before counts is carved
+        Scratch sc(s);
+        uint64_t *d_max;
+        HIP_CHECK(sc.get(&d_max, 4 * sizeof(uint64_t)));
+        HIP_CHECK(hipMemsetAsync(d_max, 0, 2 * sizeof(uint64_t), s));
+        HIP_CHECK(hipMemsetAsync(d_max + 2, 0xFF, 2 * sizeof(uint64_t), s));
+        k_minmax_u64<<<grid_for(n), BLK, 0, s>>>(rows.k, rows.v, n, d_max);
+        HIP_CHECK(hipMemcpyAsync(h_max, d_max, 4 * sizeof(uint64_t),
+                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
     const uint64_t kbase = h_max[2], vbase = h_max[3];
     const uint64_t krange = h_max[0] - kbase, vrange = h_max[1] - vbase;
     int kbytes = 0, vbytes = 0;
@@ -3080,91 +2998,87 @@ dbsp_status sort_rows(hipStream_t s, uint64_t *kk, uint64_t *vv, int64_t *ww,
     while (vbytes < 8 && (vrange >> (8 * vbytes)) != 0) vbytes++;
 
     int64_t nblocks = ceil_div(n, SORT_TILE);
+    Scratch sc(s);
     uint64_t *counts;
-    HIP_CHECK(dbspk::cache_malloc((void **)&counts, (int64_t)256 * nblocks * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&counts, (int64_t)256 * nblocks * sizeof(uint64_t)));
 
-    uint64_t *src_k = kk, *src_v = vv; int64_t *src_w = ww;
-    uint64_t *dst_k = kk2, *dst_v = vv2; int64_t *dst_w = ww2;
+    Rows src = rows, dst = scratch;
     for (int byte = 0; byte < 16; byte++) {
         bool is_v = byte < 8;
         if (is_v && (byte & 7) >= vbytes) continue;
         if (!is_v && (byte & 7) >= kbytes) continue;
         k_radix_hist<<<dim3((uint32_t)nblocks), BLK, 0, s>>>(
-            src_k, src_v, n, byte, kbase, vbase, nblocks, counts);
-        dbsp_status st = scan_exclusive(s, counts, counts, 256 * nblocks, nullptr);
-        if (st != DBSP_OK) return st;
+            src.k, src.v, n, byte, kbase, vbase, nblocks, counts);
+        TRY_K(scan_exclusive(s, counts, counts, 256 * nblocks, nullptr));
         k_radix_scatter<<<dim3((uint32_t)nblocks), BLK, 0, s>>>(
-            src_k, src_v, src_w, n, byte, kbase, vbase, nblocks, counts, dst_k,
-            dst_v, dst_w);
-        uint64_t *t;
-        int64_t *tw;
-        t = src_k; src_k = dst_k; dst_k = t;
-        t = src_v; src_v = dst_v; dst_v = t;
-        tw = src_w; src_w = dst_w; dst_w = tw;
+            src.k, src.v, src.w, n, byte, kbase, vbase, nblocks, counts, dst.k,
+            dst.v, dst.w);
+        std::swap(src, dst);
     }
-    HIP_CHECK(dbspk::cache_free(counts, s));
-    *result_in_scratch = (src_k != kk);
+    *result_in_scratch = (src.k != rows.k);
     return DBSP_OK;
 }
 
-// consolidate SORTED rows into freshly allocated output; returns exact length
-dbsp_status consolidate_sorted(hipStream_t s, const uint64_t *kk,
-                               const uint64_t *vv, const int64_t *ww, int64_t n,
-                               uint64_t **ok, uint64_t **ov, int64_t **ow,
-                               int64_t *out_n) {
-    if (n == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
+// consolidate SORTED rows into freshly allocated output; returns exact length.
+// The segment reduction is the weight type's: i64 sums with atomics; f64 runs
+// the deterministic segmented tree IN PLACE over in.w (position-fixed order;
+// tolerance 2 ulp * ceil(log2 run) vs sequential).
+dbsp_status consolidate_sorted(hipStream_t s, const Rows &in, bool wf64,
+                               Rows *out) {
+    const int64_t n = in.n;
+    if (n == 0) return no_rows(out);
+    Scratch sc(s);
     uint64_t *flags, *fscan;
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, n * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
-    k_head_flags<<<grid_for(n), BLK, 0, s>>>(kk, vv, n, flags);
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_head_flags<<<grid_for(n), BLK, 0, s>>>(in.k, in.v, n, flags);
     uint64_t nseg = 0;
-    dbsp_status st = scan_exclusive(s, flags, fscan, n, &nseg);
-    if (st != DBSP_OK) return st;
-    uint64_t *sk, *sv; int64_t *sw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&sk, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&sv, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&sw, nseg * sizeof(int64_t) + 8, s));
-    HIP_CHECK(hipMemsetAsync(sw, 0, nseg * sizeof(int64_t), s));
-    k_seg_accum<<<grid_for(n), BLK, 0, s>>>(kk, vv, ww, fscan, flags, n, sk, sv, sw);
+    TRY_K(scan_exclusive(s, flags, fscan, n, &nseg));
+    Rows seg;
+    TRY_K(alloc_rows(sc, (int64_t)nseg, &seg));
+    if (wf64) {
+        uint64_t *hp;
+        double *ww = (double *)in.w;
+        HIP_CHECK(sc.get(&hp, nseg * sizeof(uint64_t) + 8));
+        k_seg_headpos<<<grid_for(n), BLK, 0, s>>>(flags, fscan, n, hp);
+        for (int64_t d = 1; d < n; d <<= 1)
+            k_seg_tree_round<<<grid_for(n), BLK, 0, s>>>(ww, flags, fscan, hp,
+                                                         n, d);
+        k_seg_collect_f64<<<grid_for(n), BLK, 0, s>>>(
+            in.k, in.v, ww, flags, fscan, n, seg.k, seg.v, (double *)seg.w);
+    } else {
+        HIP_CHECK(hipMemsetAsync(seg.w, 0, nseg * sizeof(int64_t), s));
+        k_seg_accum<<<grid_for(n), BLK, 0, s>>>(in.k, in.v, in.w, fscan, flags,
+                                                n, seg.k, seg.v, seg.w);
+    }
     // drop zero-weight segments
     uint64_t *nzflags, *nzscan;
-    HIP_CHECK(dbspk::cache_malloc((void **)&nzflags, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&nzscan, nseg * sizeof(uint64_t) + 8, s));
-    k_nonzero_flags<<<grid_for(nseg), BLK, 0, s>>>(sw, nseg, nzflags);
+    HIP_CHECK(sc.get(&nzflags, nseg * sizeof(uint64_t) + 8));
+    HIP_CHECK(sc.get(&nzscan, nseg * sizeof(uint64_t) + 8));
+    if (wf64)
+        k_nonzero_flags<double><<<grid_for(nseg), BLK, 0, s>>>(
+            (const double *)seg.w, nseg, nzflags);
+    else
+        k_nonzero_flags<int64_t><<<grid_for(nseg), BLK, 0, s>>>(seg.w, nseg,
+                                                                nzflags);
     uint64_t nout = 0;
-    st = scan_exclusive(s, nzflags, nzscan, nseg, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv; int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(int64_t) + 8, s));
-    k_compact<<<grid_for(nseg), BLK, 0, s>>>(sk, sv, sw, nzflags, nzscan, nseg,
-                                             rk, rv, rw);
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
-    HIP_CHECK(dbspk::cache_free(sk, s));
-    HIP_CHECK(dbspk::cache_free(sv, s));
-    HIP_CHECK(dbspk::cache_free(sw, s));
-    HIP_CHECK(dbspk::cache_free(nzflags, s));
-    HIP_CHECK(dbspk::cache_free(nzscan, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
+    TRY_K(scan_exclusive(s, nzflags, nzscan, nseg, &nout));
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
+    // k_compact copies the weight column bitwise (8 B) — valid for f64
+    k_compact<<<grid_for(nseg), BLK, 0, s>>>(seg.k, seg.v, seg.w, nzflags,
+                                             nzscan, nseg, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
 template <typename W>
-static dbsp_status merge_rows_t(hipStream_t s, const uint64_t *ak,
-                                const uint64_t *av, const W *aw, int64_t na,
-                                const uint64_t *bk, const uint64_t *bv,
-                                const W *bw, int64_t nb, uint64_t **ok,
-                                uint64_t **ov, W **ow, int64_t *out_n) {
+static dbsp_status merge_rows_t(hipStream_t s, const Rows &a, const Rows &b,
+                                Rows *out) {
+    const uint64_t *ak = a.k, *av = a.v, *bk = b.k, *bv = b.v;
+    const W *aw = (const W *)a.w, *bw = (const W *)b.w;
+    const int64_t na = a.n, nb = b.n;
     int64_t total = na + nb;
-    if (total == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
+    if (total == 0) return no_rows(out);
     // Default: two-pass count -> device scan -> emit (k_mp_merge_onepass
     // modes 1+2 — branchless capture walk in both phases).  The single-pass
     // decoupled-lookback variant (mode 0) reads each input byte once but its
@@ -3181,59 +3095,48 @@ static dbsp_status merge_rows_t(hipStream_t s, const uint64_t *ak,
     }();
     const int64_t tile = op_tile;
     int64_t nblocks = ceil_div(total, tile);
+    Scratch sc(s);
     int64_t *pa, *pb;
-    HIP_CHECK(dbspk::cache_malloc((void **)&pa, (nblocks + 1) * sizeof(int64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&pb, (nblocks + 1) * sizeof(int64_t), s));
+    HIP_CHECK(sc.get(&pa, (nblocks + 1) * sizeof(int64_t)));
+    HIP_CHECK(sc.get(&pb, (nblocks + 1) * sizeof(int64_t)));
     k_mp_partition<<<grid_for(nblocks + 1), BLK, 0, s>>>(ak, av, na, bk, bv, nb,
                                                          nblocks, tile, pa, pb);
-    uint64_t *rk, *rv;
-    W *rw;
+    Rows r;
     const dim3 g((uint32_t)nblocks);
     if (!twopass) {
         unsigned long long *state;
-        HIP_CHECK(dbspk::cache_malloc((void **)&state, (nblocks + 2) * sizeof(uint64_t), s));
+        HIP_CHECK(sc.get(&state, (nblocks + 2) * sizeof(uint64_t)));
         HIP_CHECK(hipMemsetAsync(state, 0, (nblocks + 2) * sizeof(uint64_t), s));
-        HIP_CHECK(dbspk::cache_malloc((void **)&rk, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)&rv, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)&rw, total * sizeof(W) + 8, s));
-        static const bool nolb = []() {  // timing diagnostic (wrong results)
-            const char *e = getenv("DBSP_MERGE_NOLB");
-            return e && e[0] == '1';
-        }();
+        TRY_K(alloc_rows(sc, total, &r));
         const size_t smem = 3 * (tile + 2) * sizeof(uint64_t);
-        if (nolb && tile == 2048)
-            k_mp_merge_onepass<W, 2048, 0, true><<<g, MP_THREADS, smem, s>>>(
-                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, rk, rv, rw);
-        else if (nolb)
-            k_mp_merge_onepass<W, MP_TILE, 0, true><<<g, MP_THREADS, smem, s>>>(
-                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, rk, rv, rw);
-        else if (tile == 2048)
+        if (tile == 2048)
             k_mp_merge_onepass<W, 2048, 0><<<g, MP_THREADS, smem, s>>>(
-                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, rk, rv, rw);
+                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, r.k,
+                r.v, (W *)r.w);
         else
             k_mp_merge_onepass<W, MP_TILE, 0><<<g, MP_THREADS, smem, s>>>(
-                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, rk, rv, rw);
+                ak, av, aw, na, bk, bv, bw, nb, pa, pb, state, nblocks, r.k,
+                r.v, (W *)r.w);
         unsigned long long h_state[2];
         HIP_CHECK(hipMemcpyAsync(&h_state[0], state + 1, sizeof(uint64_t),
                                  hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(&h_state[1], state + 2 + (nblocks - 1),
                                  sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(dbspk::cache_free(state, s));
+        // early: state is back in the list before the fall-back path carves
+        HIP_CHECK(sc.release(state));
         if (h_state[0] == 0 && (h_state[1] & 3ull) == 2ull) {
-            HIP_CHECK(dbspk::cache_free(pa, s));
-            HIP_CHECK(dbspk::cache_free(pb, s));
-            *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)(h_state[1] >> 2);
-            return DBSP_OK;
+            r.n = (int64_t)(h_state[1] >> 2);
+            return give_rows(sc, r, out);
         }
         // poisoned lookback: free the optimistic buffers and fall through to
         // the two-pass pipeline on the partitions already computed
-        (void)dbspk::cache_free(rk, s);
-        (void)dbspk::cache_free(rv, s);
-        (void)dbspk::cache_free(rw, s);
+        (void)sc.release(r.k);
+        (void)sc.release(r.v);
+        (void)sc.release(r.w);
     }
     uint64_t *counts;
-    HIP_CHECK(dbspk::cache_malloc((void **)&counts, (nblocks + 1) * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&counts, (nblocks + 1) * sizeof(uint64_t)));
     const size_t smem_count = 2 * (tile + 2) * sizeof(uint64_t);
     if (tile == 2048)
         k_mp_merge_onepass<W, 2048, 1><<<g, MP_THREADS, smem_count, s>>>(
@@ -3244,164 +3147,132 @@ static dbsp_status merge_rows_t(hipStream_t s, const uint64_t *ak,
             ak, av, aw, na, bk, bv, bw, nb, pa, pb,
             (unsigned long long *)counts, nblocks, nullptr, nullptr, nullptr);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, counts, counts, nblocks, &nout);
-    if (st != DBSP_OK) return st;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(W) + 8, s));
+    TRY_K(scan_exclusive(s, counts, counts, nblocks, &nout));
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
     const size_t smem_emit = 3 * (tile + 2) * sizeof(uint64_t);
     if (nout > 0) {
         if (tile == 2048)
             k_mp_merge_onepass<W, 2048, 2><<<g, MP_THREADS, smem_emit, s>>>(
                 ak, av, aw, na, bk, bv, bw, nb, pa, pb,
-                (unsigned long long *)counts, nblocks, rk, rv, rw);
+                (unsigned long long *)counts, nblocks, r.k, r.v, (W *)r.w);
         else
             k_mp_merge_onepass<W, MP_TILE, 2><<<g, MP_THREADS, smem_emit, s>>>(
                 ak, av, aw, na, bk, bv, bw, nb, pa, pb,
-                (unsigned long long *)counts, nblocks, rk, rv, rw);
+                (unsigned long long *)counts, nblocks, r.k, r.v, (W *)r.w);
     }
-    HIP_CHECK(dbspk::cache_free(pa, s));
-    HIP_CHECK(dbspk::cache_free(pb, s));
-    HIP_CHECK(dbspk::cache_free(counts, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
+    return give_rows(sc, r, out);
 }
 
-dbsp_status merge_rows(hipStream_t s, const uint64_t *ak, const uint64_t *av,
-                       const int64_t *aw, int64_t na, const uint64_t *bk,
-                       const uint64_t *bv, const int64_t *bw, int64_t nb,
-                       uint64_t **ok, uint64_t **ov, int64_t **ow,
-                       int64_t *out_n) {
-    return merge_rows_t<int64_t>(s, ak, av, aw, na, bk, bv, bw, nb, ok, ov, ow,
-                                 out_n);
+dbsp_status merge_rows(hipStream_t s, const Rows &a, const Rows &b, bool wf64,
+                       Rows *out) {
+    return wf64 ? merge_rows_t<double>(s, a, b, out)
+                : merge_rows_t<int64_t>(s, a, b, out);
 }
 
-dbsp_status merge_rows_f64(hipStream_t s, const uint64_t *ak, const uint64_t *av,
-                           const double *aw, int64_t na, const uint64_t *bk,
-                           const uint64_t *bv, const double *bw, int64_t nb,
-                           uint64_t **ok, uint64_t **ov, double **ow,
-                           int64_t *out_n) {
-    return merge_rows_t<double>(s, ak, av, aw, na, bk, bv, bw, nb, ok, ov, ow,
-                                out_n);
-}
-
-
-dbsp_status minmax_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                        int64_t n, uint64_t mm[4]) {
+dbsp_status minmax_rows(hipStream_t s, const Rows &rows, uint64_t mm[4]) {
+    Scratch sc(s);
     unsigned long long *d;
-    HIP_CHECK(dbspk::cache_malloc((void **)&d, 4 * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&d, 4 * sizeof(uint64_t)));
     const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
     HIP_CHECK(hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, s));
     // cap the grid: each block ends with 8 global atomics on 4 hot words,
     // and a full grid_for() grid serializes ~15 us on them alone
-    k_minmax_rows<<<dim3(std::min(grid_for(n).x, 64u)), BLK, 0, s>>>(k, v, n,
-                                                                     d);
+    k_minmax_rows<<<dim3(std::min(grid_for(rows.n).x, 64u)), BLK, 0, s>>>(
+        rows.k, rows.v, rows.n, d);
     HIP_CHECK(hipMemcpyAsync(mm, d, 4 * sizeof(uint64_t),
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(dbspk::cache_free(d, s));
     return DBSP_OK;
 }
 
 // chained variant: n read from the device, results left in mm_dev[0..3]
 // (caller reads them at its own sync); grid sized by the capacity bound
-dbsp_status minmax_rows_chain(hipStream_t s, const uint64_t *k,
-                              const uint64_t *v, int64_t cap,
+dbsp_status minmax_rows_chain(hipStream_t s, const Rows &rows,
                               const int64_t *n_dev,
                               unsigned long long *mm_dev) {
     const unsigned long long init[4] = {~0ull, ~0ull, 0ull, 0ull};
     HIP_CHECK(hipMemcpyAsync(mm_dev, init, sizeof(init), hipMemcpyHostToDevice,
                              s));
-    k_minmax_rows<<<dim3(std::min(grid_for(cap).x, 64u)), BLK, 0, s>>>(
-        k, v, 0, mm_dev, n_dev);
+    k_minmax_rows<<<dim3(std::min(grid_for(rows.n).x, 64u)), BLK, 0, s>>>(
+        rows.k, rows.v, 0, mm_dev, n_dev);
     return DBSP_OK;
+}
+
+// the dense consolidates' shared front: weights into the kspan*vspan
+// histogram, cell flags scanned in place (total to *h_total if asked: a sync)
+static dbsp_status dense_hist(Scratch &sc, const Rows &in, uint64_t kbase,
+                              uint64_t vbase, int64_t vspan, int64_t r,
+                              unsigned long long **wbuf, uint64_t **flags,
+                              uint64_t *h_total) {
+    hipStream_t s = sc.stream();
+    HIP_CHECK(sc.get(wbuf, r * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(flags, (r + 1) * sizeof(uint64_t)));
+    HIP_CHECK(hipMemsetAsync(*wbuf, 0, r * sizeof(uint64_t), s));
+    k_hist_add<<<grid_for(in.n), BLK, 0, s>>>(in.k, in.v, in.w, in.n, kbase,
+                                              vbase, (uint64_t)vspan, *wbuf);
+    k_hist_flags<<<grid_for(r), BLK, 0, s>>>(*wbuf, r, *flags);
+    return scan_exclusive(s, *flags, *flags, r, h_total);
 }
 
 // chained variant: no host sync — the consolidated length lands in
 // *out_n_dev for the caller's one tick sync (the emit grid covers the whole
 // histogram range, so nothing here needs the total on the host)
-dbsp_status sort_cons_dense_chain(hipStream_t s, const uint64_t *k,
-                                  const uint64_t *v, const int64_t *w,
-                                  int64_t n, uint64_t kbase, uint64_t vbase,
-                                  int64_t kspan, int64_t vspan, uint64_t *ok,
-                                  uint64_t *ov, int64_t *ow,
-                                  int64_t *out_n_dev) {
+dbsp_status sort_cons_dense_chain(hipStream_t s, const Rows &in,
+                                  uint64_t kbase, uint64_t vbase,
+                                  int64_t kspan, int64_t vspan,
+                                  const Rows &out, int64_t *out_n_dev) {
     const int64_t r = kspan * vspan;
+    Scratch sc(s);
     unsigned long long *wbuf;
     uint64_t *flags;
-    HIP_CHECK(dbspk::cache_malloc((void **)&wbuf, r * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, (r + 1) * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(wbuf, 0, r * sizeof(uint64_t), s));
-    k_hist_add<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, kbase, vbase,
-                                           (uint64_t)vspan, wbuf);
-    k_hist_flags<<<grid_for(r), BLK, 0, s>>>(wbuf, r, flags);
-    dbsp_status st = scan_exclusive(s, flags, flags, r, nullptr);
-    if (st != DBSP_OK) return st;
+    TRY_K(dense_hist(sc, in, kbase, vbase, vspan, r, &wbuf, &flags, nullptr));
     k_hist_total<<<1, 1, 0, s>>>(wbuf, flags, r, out_n_dev);
     k_hist_emit<<<grid_for(r), BLK, 0, s>>>(wbuf, flags, r, kbase, vbase,
-                                            (uint64_t)vspan, ok, ov, ow);
-    HIP_CHECK(dbspk::cache_free(wbuf, s));
-    HIP_CHECK(dbspk::cache_free(flags, s));
+                                            (uint64_t)vspan, out.k, out.v,
+                                            out.w);
     return DBSP_OK;
 }
 
-dbsp_status sort_cons_dense(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                            const int64_t *w, int64_t n, uint64_t kbase,
+dbsp_status sort_cons_dense(hipStream_t s, const Rows &in, uint64_t kbase,
                             uint64_t vbase, int64_t kspan, int64_t vspan,
-                            uint64_t *ok, uint64_t *ov, int64_t *ow,
-                            int64_t *out_n) {
+                            Rows *out) {
     const int64_t r = kspan * vspan;
+    Scratch sc(s);
     unsigned long long *wbuf;
     uint64_t *flags;
-    HIP_CHECK(dbspk::cache_malloc((void **)&wbuf, r * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, (r + 1) * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(wbuf, 0, r * sizeof(uint64_t), s));
-    k_hist_add<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, kbase, vbase,
-                                           (uint64_t)vspan, wbuf);
-    k_hist_flags<<<grid_for(r), BLK, 0, s>>>(wbuf, r, flags);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, flags, flags, r, &nout);
-    if (st != DBSP_OK) return st;
+    TRY_K(dense_hist(sc, in, kbase, vbase, vspan, r, &wbuf, &flags, &nout));
     if (nout > 0)
         k_hist_emit<<<grid_for(r), BLK, 0, s>>>(wbuf, flags, r, kbase, vbase,
-                                                (uint64_t)vspan, ok, ov, ow);
-    HIP_CHECK(dbspk::cache_free(wbuf, s));
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    *out_n = (int64_t)nout;
+                                                (uint64_t)vspan, out->k,
+                                                out->v, out->w);
+    out->n = (int64_t)nout;
     return DBSP_OK;
 }
 
-dbsp_status sort_cons_small_batch(hipStream_t s, const SortArgs &args) {
+dbsp_status sort_cons_small_batch(hipStream_t s, const SortArgs &args,
+                                  bool wf64) {
     for (int b = 0; b < args.nb; b++)
         if (args.n[b] > FUSE_MAX) return DBSP_ERR_INVALID;
     if (args.nb == 0) return DBSP_OK;
-    k_sort_cons_small<int64_t>
-        <<<dim3((uint32_t)args.nb), FUSE_THREADS, 0, s>>>(args);
+    const dim3 grid((uint32_t)args.nb);
+    if (wf64)
+        k_sort_cons_small<double><<<grid, FUSE_THREADS, 0, s>>>(args);
+    else
+        k_sort_cons_small<int64_t><<<grid, FUSE_THREADS, 0, s>>>(args);
     return DBSP_OK;
 }
 
-dbsp_status sort_cons_small_batch_f64(hipStream_t s, const SortArgs &args) {
-    for (int b = 0; b < args.nb; b++)
-        if (args.n[b] > FUSE_MAX) return DBSP_ERR_INVALID;
-    if (args.nb == 0) return DBSP_OK;
-    k_sort_cons_small<double>
-        <<<dim3((uint32_t)args.nb), FUSE_THREADS, 0, s>>>(args);
-    return DBSP_OK;
-}
-
-dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args) {
+dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args,
+                              bool wf64) {
     if (args.np == 0) return DBSP_OK;
     for (int i = 0; i < args.np; i++)
         if (args.na[i] + args.nb[i] > 4 * FUSE_MAX) return DBSP_ERR_INVALID;
-    k_merge_small<int64_t><<<dim3((uint32_t)args.np), FUSE_THREADS, 0, s>>>(args);
-    return DBSP_OK;
-}
-
-dbsp_status merge_small_batch_f64(hipStream_t s, const MergeArgs &args) {
-    if (args.np == 0) return DBSP_OK;
-    for (int i = 0; i < args.np; i++)
-        if (args.na[i] + args.nb[i] > 4 * FUSE_MAX) return DBSP_ERR_INVALID;
-    k_merge_small<double><<<dim3((uint32_t)args.np), FUSE_THREADS, 0, s>>>(args);
+    const dim3 grid((uint32_t)args.np);
+    if (wf64)
+        k_merge_small<double><<<grid, FUSE_THREADS, 0, s>>>(args);
+    else
+        k_merge_small<int64_t><<<grid, FUSE_THREADS, 0, s>>>(args);
     return DBSP_OK;
 }
 
@@ -3411,86 +3282,40 @@ dbsp_status merge_small_batch_f64(hipStream_t s, const MergeArgs &args) {
 static std::atomic<uint32_t> g_mid_gen{0};
 
 dbsp_status merge_mid_batch(hipStream_t s, const MergeArgs &args,
-                            int64_t *scratch) {
+                            int64_t *scratch, bool wf64) {
     if (args.np == 0) return DBSP_OK;
     const uint32_t gen = ++g_mid_gen;
     dim3 grid(MERGE_MID_WGS, (uint32_t)args.np);
-    k_merge_mid_fused<int64_t><<<grid, FUSE_THREADS, 0, s>>>(args, scratch,
-                                                             gen);
+    if (wf64)
+        k_merge_mid_fused<double><<<grid, FUSE_THREADS, 0, s>>>(args, scratch,
+                                                                gen);
+    else
+        k_merge_mid_fused<int64_t><<<grid, FUSE_THREADS, 0, s>>>(args, scratch,
+                                                                 gen);
     return DBSP_OK;
 }
 
-dbsp_status merge_mid_batch_f64(hipStream_t s, const MergeArgs &args,
-                                int64_t *scratch) {
-    if (args.np == 0) return DBSP_OK;
-    const uint32_t gen = ++g_mid_gen;
-    dim3 grid(MERGE_MID_WGS, (uint32_t)args.np);
-    k_merge_mid_fused<double><<<grid, FUSE_THREADS, 0, s>>>(args, scratch,
-                                                            gen);
-    return DBSP_OK;
-}
-
-dbsp_status join_spine_rows(hipStream_t s, const uint64_t *dk,
-                            const uint64_t *dv, const int64_t *dw, int64_t nd,
+dbsp_status join_spine_rows(hipStream_t s, const Rows &delta,
                             const TraceArgs &t, int proj, uint64_t param,
-                            uint64_t **ok, uint64_t **ov, int64_t **ow,
-                            int64_t *out_n) {
-    if (nd == 0 || t.nb == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
+                            Rows *out) {
+    const int64_t nd = delta.n;
+    if (nd == 0 || t.nb == 0) return no_rows(out);
+    Scratch sc(s);
     uint32_t *cnts;
     uint64_t *counts;
-    HIP_CHECK(dbspk::cache_malloc((void **)&cnts, (int64_t)nd * t.nb * sizeof(uint32_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&counts, (nd + 1) * sizeof(uint64_t), s));
-    k_join_count_multi<<<grid_for(nd), BLK, 0, s>>>(dk, nd, t, cnts, counts);
+    HIP_CHECK(sc.get(&cnts, (int64_t)nd * t.nb * sizeof(uint32_t) + 8));
+    HIP_CHECK(sc.get(&counts, (nd + 1) * sizeof(uint64_t)));
+    k_join_count_multi<<<grid_for(nd), BLK, 0, s>>>(delta.k, nd, t, cnts,
+                                                    counts);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, counts, counts, nd, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv; int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(int64_t) + 8, s));
+    TRY_K(scan_exclusive(s, counts, counts, nd, &nout));
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
     if (nout > 0)
         k_join_emit_multi<<<grid_for((int64_t)nout), BLK, 0, s>>>(
-            dk, dv, dw, nd, t, cnts, counts, (int64_t)nout, proj, param, rk, rv,
-            rw);
-    HIP_CHECK(dbspk::cache_free(cnts, s));
-    HIP_CHECK(dbspk::cache_free(counts, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
-}
-
-dbsp_status join_count_scan_batch(hipStream_t s, const JoinCountArgs &args) {
-    if (args.np == 0) return DBSP_OK;
-    for (int i = 0; i < args.np; i++)
-        if (args.nd[i] > FUSE_MAX) return DBSP_ERR_INVALID;
-    k_join_probe_multi<<<dim3((uint32_t)(args.np * JPROBE_BLOCKS)), BLK, 0,
-                         s>>>(args);
-    k_join_scan_small<<<dim3((uint32_t)args.np), FUSE_THREADS, 0, s>>>(args);
-    return DBSP_OK;
-}
-
-
-dbsp_status emit_bases(hipStream_t s, const int64_t *totals, int np,
-                       int64_t cap, int64_t *bases, int64_t *out_total,
-                       int64_t *out_flag) {
-    k_emit_bases<<<1, 1, 0, s>>>(totals, np, cap, bases, out_total, out_flag);
-    return DBSP_OK;
-}
-
-dbsp_status join_emit_chain(hipStream_t s, const uint64_t *dk,
-                            const uint64_t *dv, const int64_t *dw,
-                            const int64_t *nd_dev, const TraceArgs &t,
-                            const int64_t *tn_dev, const uint32_t *cnts,
-                            const uint64_t *offsets, const int64_t *total_dev,
-                            const int64_t *base_dev, const int64_t *flag_dev,
-                            int64_t grid_cap, int proj, uint64_t param,
-                            uint64_t *ok, uint64_t *ov, int64_t *ow) {
-    k_join_emit_chain<<<grid_for(grid_cap), BLK, 0, s>>>(
-        dk, dv, dw, nd_dev, t, tn_dev, cnts, offsets, total_dev, base_dev,
-        flag_dev, proj, param, ok, ov, ow);
-    return DBSP_OK;
+            delta.k, delta.v, delta.w, nd, t, cnts, counts, (int64_t)nout,
+            proj, param, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
 dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args) {
@@ -3502,187 +3327,134 @@ dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args) {
     return DBSP_OK;
 }
 
+dbsp_status join_count_scan_batch(hipStream_t s, const JoinCountArgs &args) {
+    if (args.np == 0) return DBSP_OK;
+    TRY_K(join_probe_batch(s, args));
+    k_join_scan_small<<<dim3((uint32_t)args.np), FUSE_THREADS, 0, s>>>(args);
+    return DBSP_OK;
+}
+
 dbsp_status join_tail_small(hipStream_t s, const JoinTailArgs &a) {
     if (a.np < 0 || a.np > 3 || a.cap < FUSE_MAX) return DBSP_ERR_INVALID;
     k_join_tail_small<<<1, FUSE_THREADS, 0, s>>>(a);
     return DBSP_OK;
 }
 
-dbsp_status join_emit_prepared(hipStream_t s, const uint64_t *dk,
-                               const uint64_t *dv, const int64_t *dw,
-                               int64_t nd, const TraceArgs &t,
-                               const uint32_t *cnts, const uint64_t *offsets,
-                               int64_t n_out, int proj, uint64_t param,
-                               uint64_t *ok, uint64_t *ov, int64_t *ow) {
+dbsp_status join_emit_prepared(hipStream_t s, const Rows &delta,
+                               const TraceArgs &t, const uint32_t *cnts,
+                               const uint64_t *offsets, int64_t n_out,
+                               int proj, uint64_t param, const Rows &out) {
     if (n_out > 0)
         k_join_emit_multi<<<grid_for(n_out), BLK, 0, s>>>(
-            dk, dv, dw, nd, t, cnts, offsets, n_out, proj, param, ok, ov, ow);
+            delta.k, delta.v, delta.w, delta.n, t, cnts, offsets, n_out, proj,
+            param, out.k, out.v, out.w);
     return DBSP_OK;
 }
 
-dbsp_status join_rows(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
-                      const int64_t *dw, int64_t nd, const uint64_t *tk,
-                      const uint64_t *tv, const int64_t *tw, int64_t nt,
-                      int proj, uint64_t param, uint64_t **ok, uint64_t **ov,
-                      int64_t **ow, int64_t *out_n) {
-    if (nd == 0 || nt == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
+dbsp_status join_rows(hipStream_t s, const Rows &delta, const Rows &trace,
+                      int proj, uint64_t param, Rows *out) {
+    const int64_t nd = delta.n;
+    if (nd == 0 || trace.n == 0) return no_rows(out);
+    Scratch sc(s);
     uint64_t *counts, *starts;
-    HIP_CHECK(dbspk::cache_malloc((void **)&counts, (nd + 1) * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&starts, nd * sizeof(uint64_t), s));
-    k_join_count<<<grid_for(nd), BLK, 0, s>>>(dk, nd, tk, nt, counts, starts);
+    HIP_CHECK(sc.get(&counts, (nd + 1) * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&starts, nd * sizeof(uint64_t)));
+    k_join_count<<<grid_for(nd), BLK, 0, s>>>(delta.k, nd, trace.k, trace.n,
+                                              counts, starts);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, counts, counts, nd, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv; int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(int64_t) + 8, s));
+    TRY_K(scan_exclusive(s, counts, counts, nd, &nout));
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
     if (nout > 0)
         k_join_emit<<<grid_for((int64_t)nout), BLK, 0, s>>>(
-            dk, dv, dw, nd, tv, tw, counts, starts, (int64_t)nout, proj, param,
-            rk, rv, rw);
-    HIP_CHECK(dbspk::cache_free(counts, s));
-    HIP_CHECK(dbspk::cache_free(starts, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
+            delta.k, delta.v, delta.w, nd, trace.v, trace.w, counts, starts,
+            (int64_t)nout, proj, param, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
 template <int MODE>
 static dbsp_status agg_upsert_impl(hipStream_t s, const uint64_t *keys,
-                                   int64_t nd, const uint64_t *ik,
-                                   const uint64_t *iv, const int64_t *iw,
-                                   int64_t ni, const uint64_t *tok,
-                                   const uint64_t *tov, const int64_t *tow,
-                                   int64_t no, uint64_t **ok, uint64_t **ov,
-                                   int64_t **ow, int64_t *out_n) {
-    if (nd == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
+                                   int64_t nd, const Rows &in,
+                                   const Rows &out_trace, Rows *out) {
+    if (nd == 0) return no_rows(out);
+    Scratch sc(s);
     uint64_t *counts, *istart, *ostart, *newval, *hasnew, *offsets;
-    HIP_CHECK(dbspk::cache_malloc((void **)&counts, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&istart, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&ostart, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&newval, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&hasnew, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&offsets, nd * sizeof(uint64_t), s));
-    k_agg_count<MODE><<<grid_for(nd), BLK, 0, s>>>(keys, nd, ik, iw, ni, tok, no,
-                                                  counts, istart, ostart, newval,
-                                                  hasnew);
+    HIP_CHECK(sc.get(&counts, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&istart, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&ostart, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&newval, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&hasnew, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&offsets, nd * sizeof(uint64_t)));
+    k_agg_count<MODE><<<grid_for(nd), BLK, 0, s>>>(
+        keys, nd, in.k, in.w, in.n, out_trace.k, out_trace.n, counts, istart,
+        ostart, newval, hasnew);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, counts, offsets, nd, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv; int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(int64_t) + 8, s));
+    TRY_K(scan_exclusive(s, counts, offsets, nd, &nout));
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
     if (nout > 0)
-        k_agg_emit<MODE><<<grid_for(nd), BLK, 0, s>>>(keys, nd, iv, tov, tow,
-                                                     offsets, counts, istart,
-                                                     ostart, newval, hasnew, rk,
-                                                     rv, rw);
-    HIP_CHECK(dbspk::cache_free(counts, s));
-    HIP_CHECK(dbspk::cache_free(istart, s));
-    HIP_CHECK(dbspk::cache_free(ostart, s));
-    HIP_CHECK(dbspk::cache_free(newval, s));
-    HIP_CHECK(dbspk::cache_free(hasnew, s));
-    HIP_CHECK(dbspk::cache_free(offsets, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
+        k_agg_emit<MODE><<<grid_for(nd), BLK, 0, s>>>(
+            keys, nd, in.v, out_trace.v, out_trace.w, offsets, counts, istart,
+            ostart, newval, hasnew, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
-dbsp_status distinct_inc_rows(hipStream_t s, const uint64_t *dk,
-                              const uint64_t *dv, const int64_t *dw,
-                              int64_t nd, const TraceArgs &t, uint64_t **ok,
-                              uint64_t **ov, int64_t **ow, int64_t *out_n) {
-    if (nd == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
+dbsp_status agg_upsert_rows(hipStream_t s, AggMode mode, const uint64_t *keys,
+                            int64_t nd, const Rows &in, const Rows &out_trace,
+                            Rows *out) {
+    switch (mode) {
+    case AGG_LINEAR:
+        return agg_upsert_impl<AGG_LINEAR>(s, keys, nd, in, out_trace, out);
+    case AGG_MAX:
+        return agg_upsert_impl<AGG_MAX>(s, keys, nd, in, out_trace, out);
+    case AGG_LAST10:
+        return agg_upsert_impl<AGG_LAST10>(s, keys, nd, in, out_trace, out);
     }
+    return DBSP_ERR_INVALID;
+}
+
+dbsp_status distinct_inc_rows(hipStream_t s, const Rows &delta,
+                              const TraceArgs &t, Rows *out) {
+    const int64_t nd = delta.n;
+    if (nd == 0) return no_rows(out);
+    Scratch sc(s);
     uint64_t *flags, *fscan;
     int64_t *outw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, nd * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&outw, nd * sizeof(int64_t), s));
-    k_distinct_count<<<grid_for(nd), BLK, 0, s>>>(dk, dv, dw, nd, t, flags, outw);
+    HIP_CHECK(sc.get(&flags, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, nd * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&outw, nd * sizeof(int64_t)));
+    k_distinct_count<<<grid_for(nd), BLK, 0, s>>>(delta.k, delta.v, delta.w,
+                                                  nd, t, flags, outw);
     uint64_t nout = 0;
-    dbsp_status st = scan_exclusive(s, flags, fscan, nd, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv;
-    int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(int64_t) + 8, s));
-    k_compact<<<grid_for(nd), BLK, 0, s>>>(dk, dv, outw, flags, fscan, nd, rk,
-                                           rv, rw);
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
-    HIP_CHECK(dbspk::cache_free(outw, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
+    TRY_K(scan_exclusive(s, flags, fscan, nd, &nout));
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)nout, &r));
+    k_compact<<<grid_for(nd), BLK, 0, s>>>(delta.k, delta.v, outw, flags,
+                                           fscan, nd, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
-dbsp_status agg_linear_upsert_rows(hipStream_t s, const uint64_t *keys,
-                                   int64_t nd, const uint64_t *ik,
-                                   const uint64_t *iv, const int64_t *iw,
-                                   int64_t ni, const uint64_t *tok,
-                                   const uint64_t *tov, const int64_t *tow,
-                                   int64_t no, uint64_t **ok, uint64_t **ov,
-                                   int64_t **ow, int64_t *out_n) {
-    return agg_upsert_impl<0>(s, keys, nd, ik, iv, iw, ni, tok, tov, tow, no,
-                              ok, ov, ow, out_n);
-}
-
-dbsp_status agg_max_upsert_rows(hipStream_t s, const uint64_t *keys, int64_t nd,
-                                const uint64_t *ik, const uint64_t *iv,
-                                const int64_t *iw, int64_t ni,
-                                const uint64_t *tok, const uint64_t *tov,
-                                const int64_t *tow, int64_t no, uint64_t **ok,
-                                uint64_t **ov, int64_t **ow, int64_t *out_n) {
-    return agg_upsert_impl<1>(s, keys, nd, ik, iv, iw, ni, tok, tov, tow, no,
-                              ok, ov, ow, out_n);
-}
-
-dbsp_status agg_last10_upsert_rows(hipStream_t s, const uint64_t *keys,
-                                   int64_t nd, const uint64_t *ik,
-                                   const uint64_t *iv, const int64_t *iw,
-                                   int64_t ni, const uint64_t *tok,
-                                   const uint64_t *tov, const int64_t *tow,
-                                   int64_t no, uint64_t **ok, uint64_t **ov,
-                                   int64_t **ow, int64_t *out_n) {
-    return agg_upsert_impl<2>(s, keys, nd, ik, iv, iw, ni, tok, tov, tow, no,
-                              ok, ov, ow, out_n);
-}
-
-dbsp_status window_rows(hipStream_t s, const uint64_t *tk, const uint64_t *tv,
-                        const int64_t *tw, int64_t nt, const uint64_t *bk,
-                        const uint64_t *bv, const int64_t *bw, int64_t nb,
+dbsp_status window_rows(hipStream_t s, const Rows &trace, const Rows &batch,
                         int have_prev, uint64_t s0, uint64_t e0, uint64_t s1,
-                        uint64_t e1, uint64_t **ok, uint64_t **ov, int64_t **ow,
-                        int64_t *out_n) {
+                        uint64_t e1, Rows *out) {
+    Scratch sc(s);
     int64_t *d_ranges;
-    HIP_CHECK(dbspk::cache_malloc((void **)&d_ranges, 8 * sizeof(int64_t), s));
-    k_window_ranges<<<1, 1, 0, s>>>(tk, nt, bk, nb, have_prev, s0, e0, s1, e1,
-                                    d_ranges);
+    HIP_CHECK(sc.get(&d_ranges, 8 * sizeof(int64_t)));
+    k_window_ranges<<<1, 1, 0, s>>>(trace.k, trace.n, batch.k, batch.n,
+                                    have_prev, s0, e0, s1, e1, d_ranges);
     int64_t h_ranges[8];
     HIP_CHECK(hipMemcpyAsync(h_ranges, d_ranges, sizeof(h_ranges),
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     int64_t total = (h_ranges[1] - h_ranges[0]) + (h_ranges[3] - h_ranges[2]) +
                     (h_ranges[5] - h_ranges[4]) + (h_ranges[7] - h_ranges[6]);
-    uint64_t *rk, *rv; int64_t *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, total * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, total * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, total * sizeof(int64_t) + 8, s));
+    Rows r;
+    TRY_K(alloc_rows(sc, total, &r));
     if (total > 0)
-        k_window_emit<<<grid_for(total), BLK, 0, s>>>(tk, tv, tw, bk, bv, bw,
-                                                      d_ranges, rk, rv, rw);
-    HIP_CHECK(dbspk::cache_free(d_ranges, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = total;
-    return DBSP_OK;
+        k_window_emit<<<grid_for(total), BLK, 0, s>>>(
+            trace.k, trace.v, trace.w, batch.k, batch.v, batch.w, d_ranges,
+            r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
 dbsp_status window_ranges_multi(hipStream_t s, const TraceArgs &t,
@@ -3730,24 +3502,23 @@ dbsp_status window_ranges_chain(hipStream_t s, const TraceArgs &t,
 }
 
 dbsp_status window_emit_multi(hipStream_t s, const TraceArgs &t,
-                              const uint64_t *bk, const uint64_t *bv,
-                              const int64_t *bw, const int64_t *table,
-                              int nreg, int64_t total, uint64_t *ok,
-                              uint64_t *ov, int64_t *ow) {
+                              const Rows &batch, const int64_t *table,
+                              int nreg, int64_t total, const Rows &out) {
     if (total > 0)
-        k_window_emit_multi<<<grid_for(total), BLK, 0, s>>>(t, bk, bv, bw,
-                                                            table, nreg, total,
-                                                            ok, ov, ow);
+        k_window_emit_multi<<<grid_for(total), BLK, 0, s>>>(
+            t, batch.k, batch.v, batch.w, table, nreg, total, out.k, out.v,
+            out.w);
     return DBSP_OK;
 }
 
-dbsp_status shard_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                       const int64_t *w, int64_t n, int nshards, uint64_t *ok,
-                       uint64_t *ov, int64_t *ow, int64_t *h_offsets) {
+dbsp_status shard_rows(hipStream_t s, const Rows &in, int nshards,
+                       const Rows &out, int64_t *h_offsets) {
+    const int64_t n = in.n;
+    Scratch sc(s);
     uint64_t *hist;
-    HIP_CHECK(dbspk::cache_malloc((void **)&hist, (nshards + 1) * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&hist, (nshards + 1) * sizeof(uint64_t)));
     HIP_CHECK(hipMemsetAsync(hist, 0, (nshards + 1) * sizeof(uint64_t), s));
-    if (n > 0) k_shard_hist<<<grid_for(n), BLK, 0, s>>>(k, n, nshards, hist);
+    if (n > 0) k_shard_hist<<<grid_for(n), BLK, 0, s>>>(in.k, n, nshards, hist);
     uint64_t h_hist[64];
     HIP_CHECK(hipMemcpyAsync(h_hist, hist, nshards * sizeof(uint64_t),
                              hipMemcpyDeviceToHost, s));
@@ -3762,29 +3533,27 @@ dbsp_status shard_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
     HIP_CHECK(hipMemcpyAsync(hist, h_offsets, nshards * sizeof(int64_t),
                              hipMemcpyHostToDevice, s));
     if (n > 0)
-        k_shard_scatter<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, nshards, hist,
-                                                    ok, ov, ow);
-    HIP_CHECK(dbspk::cache_free(hist, s));
+        k_shard_scatter<<<grid_for(n), BLK, 0, s>>>(in.k, in.v, in.w, n,
+                                                    nshards, hist, out.k,
+                                                    out.v, out.w);
     return DBSP_OK;
 }
 
 // pair variant: both deltas' histograms land in one readback, so the
 // exchange pays ONE partition sync instead of two
-dbsp_status shard_rows_pair(hipStream_t s, const uint64_t *k0,
-                            const uint64_t *v0, const int64_t *w0, int64_t n0,
-                            const uint64_t *k1, const uint64_t *v1,
-                            const int64_t *w1, int64_t n1, int nshards,
-                            uint64_t *ok0, uint64_t *ov0, int64_t *ow0,
-                            uint64_t *ok1, uint64_t *ov1, int64_t *ow1,
+dbsp_status shard_rows_pair(hipStream_t s, const Rows &in0, const Rows &in1,
+                            int nshards, const Rows &out0, const Rows &out1,
                             int64_t *h_off0, int64_t *h_off1) {
+    const int64_t n0 = in0.n, n1 = in1.n;
+    Scratch sc(s);
     uint64_t *hist;
-    HIP_CHECK(dbspk::cache_malloc((void **)&hist,
-                                  2 * (nshards + 1) * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&hist, 2 * (nshards + 1) * sizeof(uint64_t)));
     HIP_CHECK(hipMemsetAsync(hist, 0, 2 * (nshards + 1) * sizeof(uint64_t), s));
     uint64_t *hist1 = hist + nshards + 1;
-    if (n0 > 0) k_shard_hist<<<grid_for(n0), BLK, 0, s>>>(k0, n0, nshards, hist);
+    if (n0 > 0)
+        k_shard_hist<<<grid_for(n0), BLK, 0, s>>>(in0.k, n0, nshards, hist);
     if (n1 > 0)
-        k_shard_hist<<<grid_for(n1), BLK, 0, s>>>(k1, n1, nshards, hist1);
+        k_shard_hist<<<grid_for(n1), BLK, 0, s>>>(in1.k, n1, nshards, hist1);
     uint64_t h_hist[130];
     HIP_CHECK(hipMemcpyAsync(h_hist, hist, sizeof(h_hist[0]) * (nshards + 1),
                              hipMemcpyDeviceToHost, s));
@@ -3809,12 +3578,11 @@ dbsp_status shard_rows_pair(hipStream_t s, const uint64_t *k0,
     HIP_CHECK(hipMemcpyAsync(hist1, cur + 65, nshards * sizeof(int64_t),
                              hipMemcpyHostToDevice, s));
     if (n0 > 0)
-        k_shard_scatter<<<grid_for(n0), BLK, 0, s>>>(k0, v0, w0, n0, nshards,
-                                                     hist, ok0, ov0, ow0);
+        k_shard_scatter<<<grid_for(n0), BLK, 0, s>>>(
+            in0.k, in0.v, in0.w, n0, nshards, hist, out0.k, out0.v, out0.w);
     if (n1 > 0)
-        k_shard_scatter<<<grid_for(n1), BLK, 0, s>>>(k1, v1, w1, n1, nshards,
-                                                     hist1, ok1, ov1, ow1);
-    HIP_CHECK(dbspk::cache_free(hist, s));
+        k_shard_scatter<<<grid_for(n1), BLK, 0, s>>>(
+            in1.k, in1.v, in1.w, n1, nshards, hist1, out1.k, out1.v, out1.w);
     return DBSP_OK;
 }
 
@@ -3972,27 +3740,26 @@ __global__ void k_shard_frames_chain(const uint64_t *k0, const uint64_t *v0,
     }
 }
 
-dbsp_status shard_frames_chain(hipStream_t s, const uint64_t *k0,
-                               const uint64_t *v0, const int64_t *w0,
-                               const int64_t *n0_dev, const uint64_t *k1,
-                               const uint64_t *v1, const int64_t *w1,
+dbsp_status shard_frames_chain(hipStream_t s, const Rows &in0,
+                               const int64_t *n0_dev, const Rows &in1,
                                const int64_t *n1_dev, int world, int64_t P0,
                                int64_t P1, int64_t n_cap, uint64_t *frame) {
     const int64_t S = 2 + 3 * P0 + 3 * P1;
     k_frames_init_headers<<<dim3(1), dim3(64), 0, s>>>(frame, world, S);
     k_shard_frames_chain<<<grid_for(n_cap > 0 ? n_cap : 1), BLK, 0, s>>>(
-        k0, v0, w0, n0_dev, k1, v1, w1, n1_dev, world, P0, P1, frame);
+        in0.k, in0.v, in0.w, n0_dev, in1.k, in1.v, in1.w, n1_dev, world, P0,
+        P1, frame);
     return DBSP_OK;
 }
 
 dbsp_status frames_unpack_pair(hipStream_t s, const uint64_t *frame,
                                int world, int64_t P0, int64_t P1,
-                               uint64_t *r0k, uint64_t *r0v, int64_t *r0w,
-                               uint64_t *r1k, uint64_t *r1v, int64_t *r1w,
+                               const Rows &r0, const Rows &r1,
                                int64_t *d_tot0, int64_t *d_tot1) {
     const int64_t total = (int64_t)world * (2 + 3 * P0 + 3 * P1);
     k_frames_unpack_pair<<<grid_for(total), BLK, 0, s>>>(
-        frame, world, P0, P1, r0k, r0v, r0w, r1k, r1v, r1w, d_tot0, d_tot1);
+        frame, world, P0, P1, r0.k, r0.v, r0.w, r1.k, r1.v, r1.w, d_tot0,
+        d_tot1);
     return DBSP_OK;
 }
 
@@ -4008,227 +3775,68 @@ dbsp_status columnize_events(hipStream_t s, const dbsp_event *ev, int64_t n,
 
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
-                                 uint64_t *k0, uint64_t *v0, int64_t *w0,
-                                 uint64_t *k1, uint64_t *v1, int64_t *w1,
+                                 const Rows &out0, const Rows &out1,
                                  uint64_t *ctr /* 2 device slots */) {
     HIP_CHECK(hipMemsetAsync(ctr, 0, 2 * sizeof(uint64_t), s));
     EventCols c{};
     if (cols) c = *cols;
     if (n > 0)
-        k_flatmap<<<grid_for(n), BLK, 0, s>>>(ev, c, n, query, ctr, k0, v0,
-                                              w0, ctr + 1, k1, v1, w1);
+        k_flatmap<<<grid_for(n), BLK, 0, s>>>(ev, c, n, query, ctr, out0.k,
+                                              out0.v, out0.w, ctr + 1, out1.k,
+                                              out1.v, out1.w);
     return DBSP_OK;
 }
 
 dbsp_status flatmap_events(hipStream_t s, const dbsp_event *ev,
-                           const EventCols *cols, int64_t n, int query, uint64_t *k0, uint64_t *v0, int64_t *w0,
-                           int64_t *n0, uint64_t *k1, uint64_t *v1, int64_t *w1,
-                           int64_t *n1) {
-    EventCols c{};
-    if (cols) c = *cols;
+                           const EventCols *cols, int64_t n, int query,
+                           Rows *out0, Rows *out1) {
+    Scratch sc(s);
     uint64_t *ctr;
-    HIP_CHECK(dbspk::cache_malloc((void **)&ctr, 2 * sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(ctr, 0, 2 * sizeof(uint64_t), s));
-    if (n > 0)
-        k_flatmap<<<grid_for(n), BLK, 0, s>>>(ev, c, n, query, ctr, k0, v0, w0,
-                                              ctr + 1, k1, v1, w1);
+    HIP_CHECK(sc.get(&ctr, 2 * sizeof(uint64_t)));
+    TRY_K(flatmap_events_chain(s, ev, cols, n, query, *out0, *out1, ctr));
     uint64_t h_ctr[2];
     HIP_CHECK(hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(dbspk::cache_free(ctr, s));
-    *n0 = (int64_t)h_ctr[0];
-    if (n1) *n1 = (int64_t)h_ctr[1];
+    out0->n = (int64_t)h_ctr[0];
+    out1->n = (int64_t)h_ctr[1];
     return DBSP_OK;
 }
 
-dbsp_status map_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                     const int64_t *w, int64_t n, int mode, uint64_t *ok,
-                     uint64_t *ov, int64_t *ow) {
-    if (n > 0)
-        k_map<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, mode, ok, ov, ow);
-    return DBSP_OK;
-}
-
-}  // namespace dbspk (reopened below after the extra kernels)
-
-// ---- multi-batch linear aggregate (spine batches summed; linear op) ----
-
-// f64 linear aggregate: per-key sums in batch-position order (deterministic)
-__global__ void k_agg_sum_f64(const uint64_t *keys, int64_t nd,
-                              const uint64_t *ik, const double *iw, int64_t ni,
-                              double *acc) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t key = keys[i];
-        int64_t lo = lower_bound_k(ik, ni, key);
-        int64_t hi = upper_bound_k(ik, ni, key);
-        double sum = 0.0;
-        for (int64_t t = lo; t < hi; t++) sum += iw[t];
-        acc[i] += sum;
-    }
-}
-
-// emit (key, bits(sum), +1) for sum != 0.0 (WeightedCount returns None for a
-// zero f64 aggregate — aggregate/mod.rs:129-156 with R = F64)
-__global__ void k_emit_nonzero_f64(const uint64_t *keys, const double *acc,
-                                   int64_t nd, uint64_t *ctr, uint64_t *ok,
-                                   uint64_t *ov, int64_t *ow) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (acc[i] != 0.0) {
-            uint64_t p = atomicAdd((unsigned long long *)ctr, 1ull);
-            ok[p] = keys[i];
-            double a = acc[i];
-            ov[p] = *(const uint64_t *)&a;
-            ow[p] = 1;
-        }
-    }
-}
-
-__global__ void k_agg_sum(const uint64_t *keys, int64_t nd, const uint64_t *ik,
-                          const int64_t *iw, int64_t ni, int64_t *acc) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t key = keys[i];
-        int64_t lo = lower_bound_k(ik, ni, key);
-        int64_t hi = upper_bound_k(ik, ni, key);
-        int64_t s = 0;
-        for (int64_t t = lo; t < hi; t++) s += iw[t];
-        acc[i] += s;
-    }
-}
-
-__global__ void k_emit_nonzero(const uint64_t *keys, const int64_t *acc,
-                               int64_t nd, uint64_t *ctr, uint64_t *ok,
-                               uint64_t *ov, int64_t *ow) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nd;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        if (acc[i] != 0) {
-            uint64_t p = atomicAdd((unsigned long long *)ctr, 1ull);
-            ok[p] = keys[i];
-            ov[p] = (uint64_t)acc[i];
-            ow[p] = 1;
-        }
-    }
-}
-
-__global__ void k_key_head_flags(const uint64_t *k, int64_t n, uint64_t *flags) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        flags[i] = (i == 0) || k[i] != k[i - 1];
-}
-
-__global__ void k_compact_keys(const uint64_t *k, const uint64_t *flags,
-                               const uint64_t *fscan, int64_t n, uint64_t *ok) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x)
-        if (flags[i]) ok[fscan[i]] = k[i];
-}
-
-namespace dbspk {
-
-// consolidate SORTED rows with f64 weights: deterministic segmented tree
-// (position-fixed order; tolerance 2 ulp * ceil(log2 run) vs sequential)
-dbsp_status consolidate_sorted_f64(hipStream_t s, const uint64_t *kk,
-                                   const uint64_t *vv, double *ww, int64_t n,
-                                   uint64_t **ok, uint64_t **ov, double **ow,
-                                   int64_t *out_n) {
-    if (n == 0) {
-        *ok = nullptr; *ov = nullptr; *ow = nullptr; *out_n = 0;
-        return DBSP_OK;
-    }
-    uint64_t *flags, *fscan, *hp;
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, n * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
-    k_head_flags<<<grid_for(n), BLK, 0, s>>>(kk, vv, n, flags);
-    uint64_t nseg = 0;
-    dbsp_status st = scan_exclusive(s, flags, fscan, n, &nseg);
-    if (st != DBSP_OK) return st;
-    HIP_CHECK(dbspk::cache_malloc((void **)&hp, nseg * sizeof(uint64_t) + 8, s));
-    k_seg_headpos<<<grid_for(n), BLK, 0, s>>>(flags, fscan, n, hp);
-    for (int64_t d = 1; d < n; d <<= 1)
-        k_seg_tree_round<<<grid_for(n), BLK, 0, s>>>(ww, flags, fscan, hp, n, d);
-    uint64_t *sk, *sv;
-    double *sw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&sk, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&sv, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&sw, nseg * sizeof(double) + 8, s));
-    k_seg_collect_f64<<<grid_for(n), BLK, 0, s>>>(kk, vv, ww, flags, fscan, n,
-                                                  sk, sv, sw);
-    uint64_t *nzflags, *nzscan;
-    HIP_CHECK(dbspk::cache_malloc((void **)&nzflags, nseg * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&nzscan, nseg * sizeof(uint64_t) + 8, s));
-    k_nonzero_flags_f64<<<grid_for(nseg), BLK, 0, s>>>(sw, nseg, nzflags);
-    uint64_t nout = 0;
-    st = scan_exclusive(s, nzflags, nzscan, nseg, &nout);
-    if (st != DBSP_OK) return st;
-    uint64_t *rk, *rv;
-    double *rw;
-    HIP_CHECK(dbspk::cache_malloc((void **)&rk, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rv, nout * sizeof(uint64_t) + 8, s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rw, nout * sizeof(double) + 8, s));
-    // k_compact copies the weight column bitwise (8 B) — valid for f64
-    k_compact<<<grid_for(nseg), BLK, 0, s>>>(sk, sv, (const int64_t *)sw,
-                                             nzflags, nzscan, nseg, rk, rv,
-                                             (int64_t *)rw);
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
-    HIP_CHECK(dbspk::cache_free(hp, s));
-    HIP_CHECK(dbspk::cache_free(sk, s));
-    HIP_CHECK(dbspk::cache_free(sv, s));
-    HIP_CHECK(dbspk::cache_free(sw, s));
-    HIP_CHECK(dbspk::cache_free(nzflags, s));
-    HIP_CHECK(dbspk::cache_free(nzscan, s));
-    *ok = rk; *ov = rv; *ow = rw; *out_n = (int64_t)nout;
-    return DBSP_OK;
-}
-
-dbsp_status agg_sum_batch_f64(hipStream_t s, const uint64_t *keys, int64_t nd,
-                              const uint64_t *ik, const double *iw, int64_t ni,
-                              double *acc) {
-    if (nd > 0 && ni > 0)
-        k_agg_sum_f64<<<grid_for(nd), BLK, 0, s>>>(keys, nd, ik, iw, ni, acc);
-    return DBSP_OK;
-}
-
-dbsp_status emit_nonzero_f64(hipStream_t s, const uint64_t *keys,
-                             const double *acc, int64_t nd, uint64_t *ok,
-                             uint64_t *ov, int64_t *ow, int64_t *h_count) {
-    uint64_t *ctr;
-    HIP_CHECK(dbspk::cache_malloc((void **)&ctr, sizeof(uint64_t), s));
-    HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof(uint64_t), s));
-    if (nd > 0)
-        k_emit_nonzero_f64<<<grid_for(nd), BLK, 0, s>>>(keys, acc, nd, ctr, ok,
-                                                        ov, ow);
-    uint64_t h = 0;
-    HIP_CHECK(hipMemcpyAsync(&h, ctr, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(dbspk::cache_free(ctr, s));
-    *h_count = (int64_t)h;
+dbsp_status map_rows(hipStream_t s, const Rows &in, int mode, const Rows &out) {
+    if (in.n > 0)
+        k_map<<<grid_for(in.n), BLK, 0, s>>>(in.k, in.v, in.w, in.n, mode,
+                                             out.k, out.v, out.w);
     return DBSP_OK;
 }
 
 dbsp_status agg_sum_batch(hipStream_t s, const uint64_t *keys, int64_t nd,
-                          const uint64_t *ik, const int64_t *iw, int64_t ni,
-                          int64_t *acc) {
-    if (nd > 0 && ni > 0)
-        k_agg_sum<<<grid_for(nd), BLK, 0, s>>>(keys, nd, ik, iw, ni, acc);
+                          const Rows &in, int64_t *acc, bool wf64) {
+    if (nd <= 0 || in.n <= 0) return DBSP_OK;
+    if (wf64)
+        k_agg_sum<double><<<grid_for(nd), BLK, 0, s>>>(
+            keys, nd, in.k, (const double *)in.w, in.n, (double *)acc);
+    else
+        k_agg_sum<int64_t><<<grid_for(nd), BLK, 0, s>>>(keys, nd, in.k, in.w,
+                                                        in.n, acc);
     return DBSP_OK;
 }
 
 dbsp_status emit_nonzero(hipStream_t s, const uint64_t *keys,
-                         const int64_t *acc, int64_t nd, uint64_t *ok,
-                         uint64_t *ov, int64_t *ow, int64_t *h_count) {
+                         const int64_t *acc, int64_t nd, bool wf64, Rows *out) {
+    Scratch sc(s);
     uint64_t *ctr;
-    HIP_CHECK(dbspk::cache_malloc((void **)&ctr, sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&ctr, sizeof(uint64_t)));
     HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof(uint64_t), s));
-    if (nd > 0)
-        k_emit_nonzero<<<grid_for(nd), BLK, 0, s>>>(keys, acc, nd, ctr, ok, ov, ow);
+    if (nd > 0 && wf64)
+        k_emit_nonzero<double><<<grid_for(nd), BLK, 0, s>>>(
+            keys, (const double *)acc, nd, ctr, out->k, out->v, out->w);
+    else if (nd > 0)
+        k_emit_nonzero<int64_t><<<grid_for(nd), BLK, 0, s>>>(
+            keys, acc, nd, ctr, out->k, out->v, out->w);
     uint64_t h = 0;
     HIP_CHECK(hipMemcpyAsync(&h, ctr, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(dbspk::cache_free(ctr, s));
-    *h_count = (int64_t)h;
+    out->n = (int64_t)h;
     return DBSP_OK;
 }
 
@@ -4239,19 +3847,18 @@ dbsp_status unique_keys(hipStream_t s, const uint64_t *kk, int64_t n,
         *out_n = 0;
         return DBSP_OK;
     }
+    Scratch sc(s);
     uint64_t *flags, *fscan;
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, n * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
     k_key_head_flags<<<grid_for(n), BLK, 0, s>>>(kk, n, flags);
     uint64_t nk = 0;
-    dbsp_status st = scan_exclusive(s, flags, fscan, n, &nk);
-    if (st != DBSP_OK) return st;
-    uint64_t *out;
-    HIP_CHECK(dbspk::cache_malloc((void **)&out, nk * sizeof(uint64_t) + 8, s));
-    k_compact_keys<<<grid_for(n), BLK, 0, s>>>(kk, flags, fscan, n, out);
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
-    *okeys = out;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &nk));
+    uint64_t *keys;
+    HIP_CHECK(sc.get(&keys, nk * sizeof(uint64_t) + 8));
+    k_compact_keys<<<grid_for(n), BLK, 0, s>>>(kk, flags, fscan, n, keys);
+    sc.keep(keys);
+    *okeys = keys;
     *out_n = (int64_t)nk;
     return DBSP_OK;
 }
@@ -4363,48 +3970,35 @@ __global__ void k_rolling_agg(const uint64_t *k, const uint64_t *v,
     }
 }
 
-#define TRY_K(x)                                                          \
-    do {                                                                  \
-        dbsp_status st_ = (x);                                            \
-        if (st_ != DBSP_OK) return st_;                                   \
-    } while (0)
-
 // build the radix-16 levels over the weight column w[0..n)
-static dbsp_status rt_build(hipStream_t s, const int64_t *w, int64_t n,
-                            RtLevels &t, int64_t **bufs) {
+// (the levels live in sc)
+static dbsp_status rt_build(Scratch &sc, const int64_t *w, int64_t n,
+                            RtLevels &t) {
     int64_t cur_n = n;
     const int64_t *cur = w;
     while (cur_n > 1 && t.nl < RT_MAX_LEVELS) {
         const int64_t nn = (cur_n + RT_RADIX - 1) / RT_RADIX;
-        HIP_CHECK(dbspk::cache_malloc((void **)&bufs[t.nl],
-                                      nn * sizeof(int64_t) + 8, s));
-        k_rt_reduce<<<grid_for(nn), BLK, 0, s>>>(cur, cur_n, bufs[t.nl], nn);
-        t.lv[t.nl] = bufs[t.nl];
+        int64_t *lv;
+        HIP_CHECK(sc.get(&lv, nn * sizeof(int64_t) + 8));
+        k_rt_reduce<<<grid_for(nn), BLK, 0, sc.stream()>>>(cur, cur_n, lv, nn);
+        t.lv[t.nl] = lv;
         t.n[t.nl] = nn;
-        cur = bufs[t.nl];
+        cur = lv;
         cur_n = nn;
         t.nl++;
     }
     return DBSP_OK;
 }
 
-static dbsp_status rt_free(hipStream_t s, const RtLevels &t, int64_t **bufs) {
-    for (int i = 0; i < t.nl; i++)
-        HIP_CHECK(dbspk::cache_free(bufs[i], s));
-    return DBSP_OK;
-}
-
-dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
-                             const uint64_t *v, const int64_t *w, int64_t n,
-                             uint64_t width, uint64_t *ok, uint64_t *ov,
-                             int64_t *ow) {
-    if (n <= 0) return DBSP_OK;
+dbsp_status rolling_agg_rows(hipStream_t s, const Rows &in, uint64_t width,
+                             const Rows &out) {
+    if (in.n <= 0) return DBSP_OK;
+    Scratch sc(s);
     RtLevels t{};
-    int64_t *bufs[RT_MAX_LEVELS] = {};
-    TRY_K(rt_build(s, w, n, t, bufs));
-    k_rolling_agg<<<grid_for(n), BLK, 0, s>>>(k, v, w, n, t, width, ok, ov,
-                                              ow);
-    return rt_free(s, t, bufs);
+    TRY_K(rt_build(sc, in.w, in.n, t));
+    k_rolling_agg<<<grid_for(in.n), BLK, 0, s>>>(in.k, in.v, in.w, in.n, t,
+                                                 width, out.k, out.v, out.w);
+    return DBSP_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -4564,20 +4158,22 @@ static inline uint64_t sat_add_u64(uint64_t a, uint64_t b) {
     return a + b < a ? UINT64_MAX : a + b;
 }
 
-dbsp_status roll_ranges(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
-                        int64_t n, uint64_t before, uint64_t after,
-                        uint64_t **ranges, int64_t *n_gather,
+dbsp_status roll_ranges(hipStream_t s, const Rows &delta, uint64_t before,
+                        uint64_t after, uint64_t **ranges, int64_t *n_gather,
                         int64_t *n_affected, int *err) {
+    const uint64_t *dk = delta.k, *dv = delta.v;
+    const int64_t n = delta.n;
     *ranges = nullptr;
     *n_gather = *n_affected = 0;
     *err = 0;
     if (n <= 0) return DBSP_OK;
     const uint64_t both = sat_add_u64(before, after);
+    Scratch sc(s);
     uint64_t *flags, *fscan, *rb;
     // flags[n] is the precondition error word
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, (n + 1) * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&rb, 6 * n * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&flags, (n + 1) * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&rb, 6 * n * sizeof(uint64_t)));
     HIP_CHECK(hipMemsetAsync(flags + n, 0, sizeof(uint64_t), s));
     k_roll_heads<<<grid_for(n), BLK, 0, s>>>(dk, dv, n, before, after, both,
                                              flags,
@@ -4592,44 +4188,35 @@ dbsp_status roll_ranges(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
             rb + 2 * n, rb + 3 * n, rb + 4 * n, rb + 5 * n);
         *n_gather = (int64_t)(total & ROLL_TMAX);
         *n_affected = (int64_t)(total >> 32);
+        sc.keep(rb);
         *ranges = rb;
     } else {
-        HIP_CHECK(dbspk::cache_free(rb, s));
+        HIP_CHECK(sc.release(rb));  // early: ahead of flags and fscan
         *err = 1;
     }
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
     return DBSP_OK;
 }
 
 dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
                          const uint64_t *rlo, const uint64_t *rhi, int64_t nr,
                          const TraceArgs &t, int mode, int64_t sign,
-                         uint64_t **ok, uint64_t **ov, int64_t **ow,
-                         int64_t *out_n) {
-    *ok = *ov = nullptr;
-    *ow = nullptr;
-    *out_n = 0;
-    if (nr <= 0 || t.nb <= 0) return DBSP_OK;
+                         Rows *out) {
+    if (nr <= 0 || t.nb <= 0) return no_rows(out);
     const int64_t np = nr * t.nb;
+    Scratch sc(s);
     uint64_t *cnt, *start;
-    HIP_CHECK(dbspk::cache_malloc((void **)&cnt, np * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&start, np * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&cnt, np * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&start, np * sizeof(uint64_t)));
     k_range_count<<<grid_for(np), BLK, 0, s>>>(rp, rlo, rhi, nr, t, mode, cnt,
                                                start);
     uint64_t total = 0;
     TRY_K(scan_exclusive(s, cnt, cnt, np, &total));
-    if (total > 0) {
-        HIP_CHECK(dbspk::cache_malloc((void **)ok, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)ov, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)ow, total * sizeof(int64_t) + 8, s));
-        k_range_emit<<<grid_for((int64_t)total), BLK, 0, s>>>(
-            t, np, cnt, start, (int64_t)total, sign, *ok, *ov, *ow);
-    }
-    *out_n = (int64_t)total;
-    HIP_CHECK(dbspk::cache_free(cnt, s));
-    HIP_CHECK(dbspk::cache_free(start, s));
-    return DBSP_OK;
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_range_emit<<<grid_for((int64_t)total), BLK, 0, s>>>(
+        t, np, cnt, start, (int64_t)total, sign, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -4754,8 +4341,7 @@ k_trunc_emit(TruncArgs a, const uint64_t *offsets, TruncOut o) {
 }
 
 dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
-                           uint64_t bound, uint64_t **ok, uint64_t **ov,
-                           int64_t **ow, int64_t *out_n) {
+                           uint64_t bound, Rows *out) {
     if (t.nb < 0 || t.nb > MAX_TRACE_BATCHES || (mode != 0 && mode != 1))
         return DBSP_ERR_INVALID;
     TruncArgs a{};
@@ -4764,9 +4350,7 @@ dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
     a.bound = bound;
     int64_t nblk = 0;
     for (int b = 0; b < t.nb; b++) {
-        ok[b] = ov[b] = nullptr;
-        ow[b] = nullptr;
-        out_n[b] = 0;
+        out[b] = Rows{};
         if (t.n[b] < 0) return DBSP_ERR_INVALID;
         a.blk0[b] = nblk;
         nblk += ceil_div(t.n[b], TRUNC_TILE);
@@ -4776,10 +4360,10 @@ dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
     if (nblk >= (int64_t)1 << 31) return DBSP_ERR_INVALID;  // grid.x limit
     // counts[nblk] = 0 so the scan leaves the grand total there; the
     // per-batch totals follow in the same buffer
+    Scratch sc(s);
     uint64_t *counts;
-    HIP_CHECK(dbspk::cache_malloc(
-        (void **)&counts,
-        (nblk + 1 + MAX_TRACE_BATCHES) * sizeof(uint64_t), s));
+    HIP_CHECK(sc.get(&counts,
+                     (nblk + 1 + MAX_TRACE_BATCHES) * sizeof(uint64_t)));
     int64_t *d_tot = (int64_t *)(counts + nblk + 1);
     HIP_CHECK(hipMemsetAsync(counts + nblk, 0, sizeof(uint64_t), s));
     k_trunc_count<<<dim3((uint32_t)nblk), BLK, 0, s>>>(a, counts);
@@ -4790,57 +4374,49 @@ dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));  // the one length sync
     TruncOut o{};
+    Rows r[MAX_TRACE_BATCHES];
     int64_t kept = 0;
     for (int b = 0; b < t.nb; b++) {
         const int64_t m = h_tot[b];
         if (m < 0 || m > t.n[b]) return DBSP_ERR_INTERNAL;
-        out_n[b] = m;
         kept += m;
         if (m == 0) continue;
-        HIP_CHECK(dbspk::cache_malloc((void **)&ok[b], m * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)&ov[b], m * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)&ow[b], m * sizeof(int64_t) + 8, s));
-        o.k[b] = ok[b];
-        o.v[b] = ov[b];
-        o.w[b] = ow[b];
+        TRY_K(alloc_rows(sc, m, &r[b]));
+        o.k[b] = r[b].k;
+        o.v[b] = r[b].v;
+        o.w[b] = r[b].w;
     }
     if (kept > 0)
         k_trunc_emit<<<dim3((uint32_t)nblk), BLK, 0, s>>>(a, counts, o);
-    HIP_CHECK(dbspk::cache_free(counts, s));
+    for (int b = 0; b < t.nb; b++) (void)give_rows(sc, r[b], &out[b]);
     return DBSP_OK;
 }
 
-dbsp_status roll_eval_rows(hipStream_t s, const uint64_t *sk,
-                           const uint64_t *sv, const int64_t *sw, int64_t n,
-                           const uint64_t *dk, const uint64_t *dv, int64_t nd,
-                           uint64_t before, uint64_t after, uint64_t **ok,
-                           uint64_t **ov, int64_t **ow, int64_t *out_n) {
-    *ok = *ov = nullptr;
-    *ow = nullptr;
-    *out_n = 0;
-    if (n <= 0 || nd <= 0) return DBSP_OK;
+dbsp_status roll_eval_rows(hipStream_t s, const Rows &slice,
+                           const Rows &delta, uint64_t before, uint64_t after,
+                           Rows *out) {
+    const int64_t n = slice.n;
+    if (n <= 0 || delta.n <= 0) return no_rows(out);
+    Scratch sc(s);
     uint64_t *flags, *fscan;
-    HIP_CHECK(dbspk::cache_malloc((void **)&flags, n * sizeof(uint64_t), s));
-    HIP_CHECK(dbspk::cache_malloc((void **)&fscan, n * sizeof(uint64_t), s));
-    k_roll_flags<<<grid_for(n), BLK, 0, s>>>(sk, sv, sw, n, dk, dv, nd, before,
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_roll_flags<<<grid_for(n), BLK, 0, s>>>(slice.k, slice.v, slice.w, n,
+                                             delta.k, delta.v, delta.n, before,
                                              after, flags);
     uint64_t total = 0;
     TRY_K(scan_exclusive(s, flags, fscan, n, &total));
-    if (total > 0) {
-        RtLevels t{};
-        int64_t *bufs[RT_MAX_LEVELS] = {};
-        TRY_K(rt_build(s, sw, n, t, bufs));
-        HIP_CHECK(dbspk::cache_malloc((void **)ok, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)ov, total * sizeof(uint64_t) + 8, s));
-        HIP_CHECK(dbspk::cache_malloc((void **)ow, total * sizeof(int64_t) + 8, s));
-        k_roll_emit<<<grid_for(n), BLK, 0, s>>>(sk, sv, sw, n, t, before, after,
-                                                flags, fscan, *ok, *ov, *ow);
-        TRY_K(rt_free(s, t, bufs));
-    }
-    *out_n = (int64_t)total;
-    HIP_CHECK(dbspk::cache_free(flags, s));
-    HIP_CHECK(dbspk::cache_free(fscan, s));
-    return DBSP_OK;
+    if (total == 0) return no_rows(out);
+    // an inner scope: the tree levels go back ahead of flags and fscan
+    Scratch lv(s);
+    RtLevels t{};
+    TRY_K(rt_build(lv, slice.w, n, t));
+    Rows r;
+    TRY_K(alloc_rows(lv, (int64_t)total, &r));
+    k_roll_emit<<<grid_for(n), BLK, 0, s>>>(slice.k, slice.v, slice.w, n, t,
+                                            before, after, flags, fscan, r.k,
+                                            r.v, r.w);
+    return give_rows(lv, r, out);
 }
 
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed) {

@@ -114,28 +114,38 @@ void cache_trim(hipStream_t s);
 // scope the tick-scale (64 KB..4 MB) free-list band: trace-scale engines
 // turn it off at init (see the definition for the measured pool interaction)
 void cache_small_set(bool on, hipStream_t s);
-}  // namespace dbspk
 
-namespace dbspk {
+// A row batch: three device columns of n rows.  f64 weights travel in w as
+// their bit patterns.  The engine's DevBatch is this type.
+struct Rows {
+    uint64_t *k = nullptr, *v = nullptr;
+    int64_t *w = nullptr;
+    int64_t n = 0;
+};
+
+// Conventions below: `const Rows &` inputs are read (n rows); `Rows *out`
+// receives FRESH columns from the big-buffer cache (null when empty) and
+// their length; a `const Rows &` destination names caller-provided columns,
+// and its comment says whether n is read or ignored.  `bool wf64` selects the
+// f64-weight instantiation (config C5: deterministic position-fixed
+// reduction order, tolerance 2 ulp * reduction depth), as Spine::wf64 does.
 
 dbsp_status scan_excl(hipStream_t s, const uint64_t *in, uint64_t *out,
                       int64_t n, uint64_t *h_total);
 void fill_u64(hipStream_t s, uint64_t *p, uint64_t v, int64_t n);
 
-dbsp_status sort_rows(hipStream_t s, uint64_t *kk, uint64_t *vv, int64_t *ww,
-                      int64_t n, uint64_t *kk2, uint64_t *vv2, int64_t *ww2,
+// sort rows by (k major, v minor), ping-ponging between rows and scratch
+// (both written; scratch must hold rows.n rows, its n is ignored)
+dbsp_status sort_rows(hipStream_t s, const Rows &rows, const Rows &scratch,
                       bool *result_in_scratch);
 
-dbsp_status consolidate_sorted(hipStream_t s, const uint64_t *kk,
-                               const uint64_t *vv, const int64_t *ww, int64_t n,
-                               uint64_t **ok, uint64_t **ov, int64_t **ow,
-                               int64_t *out_n);
+// consolidate SORTED rows.  The f64 path reduces in place: it OVERWRITES
+// in.w (the const covers the descriptor, not the columns).
+dbsp_status consolidate_sorted(hipStream_t s, const Rows &in, bool wf64,
+                               Rows *out);
 
-dbsp_status merge_rows(hipStream_t s, const uint64_t *ak, const uint64_t *av,
-                       const int64_t *aw, int64_t na, const uint64_t *bk,
-                       const uint64_t *bv, const int64_t *bw, int64_t nb,
-                       uint64_t **ok, uint64_t **ov, int64_t **ow,
-                       int64_t *out_n);
+dbsp_status merge_rows(hipStream_t s, const Rows &a, const Rows &b, bool wf64,
+                       Rows *out);
 
 dbsp_status wm_update(hipStream_t s, const uint64_t *ak, const int64_t *n_dev,
                       uint64_t width, uint64_t tumble, uint64_t lag,
@@ -151,16 +161,15 @@ dbsp_status window_ranges_chain(hipStream_t s, const TraceArgs &t,
                                 const int64_t *bn_dev,
                                 const unsigned long long *bounds,
                                 int64_t *table, int64_t *d_total);
-dbsp_status minmax_rows_chain(hipStream_t s, const uint64_t *k,
-                              const uint64_t *v, int64_t cap,
+// min/max of k and v with the length read from n_dev (rows.n is the capacity
+// that sizes the grid); results left in mm_dev[0..3], no sync
+dbsp_status minmax_rows_chain(hipStream_t s, const Rows &rows,
                               const int64_t *n_dev,
                               unsigned long long *mm_dev);
-dbsp_status shard_rows_pair(hipStream_t s, const uint64_t *k0,
-                            const uint64_t *v0, const int64_t *w0, int64_t n0,
-                            const uint64_t *k1, const uint64_t *v1,
-                            const int64_t *w1, int64_t n1, int nshards,
-                            uint64_t *ok0, uint64_t *ov0, int64_t *ow0,
-                            uint64_t *ok1, uint64_t *ov1, int64_t *ow1,
+// hash-partition two batches with one readback; out0/out1 hold in0.n/in1.n
+// rows (their n is ignored)
+dbsp_status shard_rows_pair(hipStream_t s, const Rows &in0, const Rows &in1,
+                            int nshards, const Rows &out0, const Rows &out1,
                             int64_t *h_off0, int64_t *h_off1);
 // device event columns (the §8f3 columnizer, input.rs:591-721): staged
 // events split once into SoA columns so the per-tick flatmaps read
@@ -173,10 +182,10 @@ dbsp_status columnize_events(hipStream_t s, const dbsp_event *ev, int64_t n,
                              uint64_t *kind, uint64_t *f0, uint64_t *f1,
                              uint64_t *f2, uint64_t *f3, uint64_t *f4,
                              int64_t *w);
+// out0/out1: capacity columns (n ignored); lengths land in ctr[0..1] (device)
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
-                                 uint64_t *k0, uint64_t *v0, int64_t *w0,
-                                 uint64_t *k1, uint64_t *v1, int64_t *w1,
+                                 const Rows &out0, const Rows &out1,
                                  uint64_t *ctr);
 
 // fixed-frame pair exchange (engine exchange fast path): both partitioned
@@ -199,248 +208,173 @@ struct FramePairArgs {
 };
 dbsp_status frames_pack_pair(hipStream_t s, const FramePairArgs &a);
 // chained variant: hash-partition both RAW streams straight into the frames
-// (lengths read from device counters; n_cap bounds the launch grid)
-dbsp_status shard_frames_chain(hipStream_t s, const uint64_t *k0,
-                               const uint64_t *v0, const int64_t *w0,
-                               const int64_t *n0_dev, const uint64_t *k1,
-                               const uint64_t *v1, const int64_t *w1,
+// (lengths read from device counters, in0.n/in1.n ignored; n_cap bounds the
+// launch grid)
+dbsp_status shard_frames_chain(hipStream_t s, const Rows &in0,
+                               const int64_t *n0_dev, const Rows &in1,
                                const int64_t *n1_dev, int world, int64_t P0,
                                int64_t P1, int64_t n_cap, uint64_t *frame);
+// r0/r1: capacity columns (n ignored); totals land in d_tot0/d_tot1 (device)
 dbsp_status frames_unpack_pair(hipStream_t s, const uint64_t *frame,
                                int world, int64_t P0, int64_t P1,
-                               uint64_t *r0k, uint64_t *r0v, int64_t *r0w,
-                               uint64_t *r1k, uint64_t *r1v, int64_t *r1w,
+                               const Rows &r0, const Rows &r1,
                                int64_t *d_tot0, int64_t *d_tot1);
 // fused single-workgroup sort+consolidate: up to SORT_BATCH_MAX (8)
 // independent small (n <= 8192) raw batches sorted+consolidated concurrently,
 // one workgroup each, lengths left in d_len[i] (device)
-dbsp_status sort_cons_small_batch(hipStream_t s, const SortArgs &args);
+dbsp_status sort_cons_small_batch(hipStream_t s, const SortArgs &args,
+                                  bool wf64);
 // min/max of k and v (one sync): mm = {kmin, vmin, kmax, vmax}
-dbsp_status minmax_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                        int64_t n, uint64_t mm[4]);
+dbsp_status minmax_rows(hipStream_t s, const Rows &rows, uint64_t mm[4]);
 // dense-range consolidate: weights scattered into a kspan*vspan histogram,
-// nonzero cells emitted in index order (sorted); i64 only
-dbsp_status sort_cons_dense(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                            const int64_t *w, int64_t n, uint64_t kbase,
+// nonzero cells emitted in index order (sorted); i64 only.  out names
+// caller-provided columns of in.n rows; its n is WRITTEN (one sync).
+dbsp_status sort_cons_dense(hipStream_t s, const Rows &in, uint64_t kbase,
                             uint64_t vbase, int64_t kspan, int64_t vspan,
-                            uint64_t *ok, uint64_t *ov, int64_t *ow,
-                            int64_t *out_n);
-// chained dense consolidate: length to *out_n_dev, no sync
-dbsp_status sort_cons_dense_chain(hipStream_t s, const uint64_t *k,
-                                  const uint64_t *v, const int64_t *w,
-                                  int64_t n, uint64_t kbase, uint64_t vbase,
-                                  int64_t kspan, int64_t vspan, uint64_t *ok,
-                                  uint64_t *ov, int64_t *ow,
-                                  int64_t *out_n_dev);
+                            Rows *out);
+// chained dense consolidate: length to *out_n_dev, no sync (out.n ignored)
+dbsp_status sort_cons_dense_chain(hipStream_t s, const Rows &in,
+                                  uint64_t kbase, uint64_t vbase,
+                                  int64_t kspan, int64_t vspan,
+                                  const Rows &out, int64_t *out_n_dev);
 
 // single-workgroup merges of up to MERGE_BATCH_MAX pairs of consolidated
 // batches (each na+nb <= 32768; the spine merges keep it for pairs <= 4096
 // and send larger ones to merge_mid_batch): one launch, no host sync; lengths
 // left in d_len[p] (device)
-dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args);
+dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args, bool wf64);
 // fixed-grid multi-WG merge with optional device-side b lengths (in-train
 // accumulator fold); scratch holds np * (MERGE_MID_SCRATCH) int64 slots
 #define MERGE_MID_SCRATCH 33
 dbsp_status merge_mid_batch(hipStream_t s, const MergeArgs &args,
-                            int64_t *scratch);
-dbsp_status merge_mid_batch_f64(hipStream_t s, const MergeArgs &args,
-                                int64_t *scratch);
+                            int64_t *scratch, bool wf64);
 
-// up to 3 single-workgroup join count+scan plans in ONE launch (nd <= 8192
-// each): per-plan per-row/per-batch cnts, exclusive offsets, totals to
-// d_total[i] (device)
+// the probe phase of a join over up to 3 plans (nd <= 8192 each): per-plan
+// per-row/per-batch cnts and, if asked, start positions; no scan
+dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args);
+// the probe plus the single-workgroup scan, two launches: exclusive offsets,
+// totals to d_total[i] (device)
 dbsp_status join_count_scan_batch(hipStream_t s, const JoinCountArgs &args);
-// chained emit machinery: per-plan bases from device totals, emit with every
-// size read device-side (flag short-circuits on lost speculation/overflow)
-dbsp_status emit_bases(hipStream_t s, const int64_t *totals, int np,
-                       int64_t cap, int64_t *bases, int64_t *out_total,
-                       int64_t *out_flag);
-dbsp_status join_emit_chain(hipStream_t s, const uint64_t *dk,
-                            const uint64_t *dv, const int64_t *dw,
-                            const int64_t *nd_dev, const TraceArgs &t,
-                            const int64_t *tn_dev, const uint32_t *cnts,
-                            const uint64_t *offsets, const int64_t *total_dev,
-                            const int64_t *base_dev, const int64_t *flag_dev,
-                            int64_t grid_cap, int proj, uint64_t param,
-                            uint64_t *ok, uint64_t *ov, int64_t *ow);
-// emit phase over precomputed cnts/offsets
-dbsp_status join_emit_prepared(hipStream_t s, const uint64_t *dk,
-                               const uint64_t *dv, const int64_t *dw,
-                               int64_t nd, const TraceArgs &t,
-                               const uint32_t *cnts, const uint64_t *offsets,
-                               int64_t n_out, int proj, uint64_t param,
-                               uint64_t *ok, uint64_t *ov, int64_t *ow);
+// the single-workgroup tail that consumes a probe which kept the starts
+dbsp_status join_tail_small(hipStream_t s, const JoinTailArgs &a);
+// emit phase over precomputed cnts/offsets into out (n_out rows; out.n
+// ignored)
+dbsp_status join_emit_prepared(hipStream_t s, const Rows &delta,
+                               const TraceArgs &t, const uint32_t *cnts,
+                               const uint64_t *offsets, int64_t n_out,
+                               int proj, uint64_t param, const Rows &out);
 
 // join delta against a whole spine (TraceArgs) in one count/emit pair
-dbsp_status join_spine_rows(hipStream_t s, const uint64_t *dk,
-                            const uint64_t *dv, const int64_t *dw, int64_t nd,
+dbsp_status join_spine_rows(hipStream_t s, const Rows &delta,
                             const TraceArgs &t, int proj, uint64_t param,
-                            uint64_t **ok, uint64_t **ov, int64_t **ow,
-                            int64_t *out_n);
+                            Rows *out);
 
-dbsp_status join_rows(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
-                      const int64_t *dw, int64_t nd, const uint64_t *tk,
-                      const uint64_t *tv, const int64_t *tw, int64_t nt,
-                      int proj, uint64_t param, uint64_t **ok, uint64_t **ov,
-                      int64_t **ow, int64_t *out_n);
+dbsp_status join_rows(hipStream_t s, const Rows &delta, const Rows &trace,
+                      int proj, uint64_t param, Rows *out);
 
 // incremental distinct over a whole spine (non-linear: the per-pair total
 // must be summed across batches before the indicator)
-dbsp_status distinct_inc_rows(hipStream_t s, const uint64_t *dk,
-                              const uint64_t *dv, const int64_t *dw,
-                              int64_t nd, const TraceArgs &t, uint64_t **ok,
-                              uint64_t **ov, int64_t **ow, int64_t *out_n);
+dbsp_status distinct_inc_rows(hipStream_t s, const Rows &delta,
+                              const TraceArgs &t, Rows *out);
 
-// the probe phase of join_count_scan_batch alone (counts and, if asked,
-// start positions; no scan), and the single-workgroup tail that consumes it
-dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args);
-dbsp_status join_tail_small(hipStream_t s, const JoinTailArgs &a);
-
-dbsp_status agg_linear_upsert_rows(hipStream_t s, const uint64_t *keys,
-                                   int64_t nd, const uint64_t *ik,
-                                   const uint64_t *iv, const int64_t *iw,
-                                   int64_t ni, const uint64_t *tok,
-                                   const uint64_t *tov, const int64_t *tow,
-                                   int64_t no, uint64_t **ok, uint64_t **ov,
-                                   int64_t **ow, int64_t *out_n);
-
-// q6's fold: avg of the last <= 10 vals in the key's run (cursor order)
-dbsp_status agg_last10_upsert_rows(hipStream_t s, const uint64_t *keys,
-                                   int64_t nd, const uint64_t *ik,
-                                   const uint64_t *iv, const int64_t *iw,
-                                   int64_t ni, const uint64_t *tok,
-                                   const uint64_t *tov, const int64_t *tow,
-                                   int64_t no, uint64_t **ok, uint64_t **ov,
-                                   int64_t **ow, int64_t *out_n);
-dbsp_status agg_max_upsert_rows(hipStream_t s, const uint64_t *keys, int64_t nd,
-                                const uint64_t *ik, const uint64_t *iv,
-                                const int64_t *iw, int64_t ni,
-                                const uint64_t *tok, const uint64_t *tov,
-                                const int64_t *tow, int64_t no, uint64_t **ok,
-                                uint64_t **ov, int64_t **ow, int64_t *out_n);
+// aggregate + upsert of the delta keys over the input trace `in`, retracting
+// against the output trace `out_trace`.  AGG_LAST10 is q6's fold: avg of the
+// last <= 10 vals in the key's run (cursor order).
+enum AggMode { AGG_LINEAR = 0, AGG_MAX = 1, AGG_LAST10 = 2 };
+dbsp_status agg_upsert_rows(hipStream_t s, AggMode mode, const uint64_t *keys,
+                            int64_t nd, const Rows &in, const Rows &out_trace,
+                            Rows *out);
 
 // multi-batch linear aggregate: accumulate per-delta-key weight sums of one
 // trace batch into acc[nd] (aggregation is linear in the trace, so spines are
-// summed batch by batch)
+// summed batch by batch); f64 sums run in batch-position order
 dbsp_status agg_sum_batch(hipStream_t s, const uint64_t *keys, int64_t nd,
-                          const uint64_t *ik, const int64_t *iw, int64_t ni,
-                          int64_t *acc);
-// emit (key, acc, +1) for acc != 0 (ticket append; caller consolidates)
+                          const Rows &in, int64_t *acc, bool wf64);
+// emit (key, acc, +1) for acc != 0 into out's caller-provided columns of nd
+// rows (ticket append; caller consolidates); out->n is WRITTEN (one sync).
+// f64: v holds the sum's bit pattern.
 dbsp_status emit_nonzero(hipStream_t s, const uint64_t *keys,
-                         const int64_t *acc, int64_t nd, uint64_t *ok,
-                         uint64_t *ov, int64_t *ow, int64_t *h_count);
+                         const int64_t *acc, int64_t nd, bool wf64, Rows *out);
 
-dbsp_status window_rows(hipStream_t s, const uint64_t *tk, const uint64_t *tv,
-                        const int64_t *tw, int64_t nt, const uint64_t *bk,
-                        const uint64_t *bv, const int64_t *bw, int64_t nb,
+dbsp_status window_rows(hipStream_t s, const Rows &trace, const Rows &batch,
                         int have_prev, uint64_t s0, uint64_t e0, uint64_t s1,
-                        uint64_t e1, uint64_t **ok, uint64_t **ov, int64_t **ow,
-                        int64_t *out_n);
+                        uint64_t e1, Rows *out);
 
 // multi-batch window: ranges for all spine batches + tick batch in one launch
 // (region table rows [src,lo,len,sign,goff]; total left in *d_total), then one
-// grid-stride emit
+// grid-stride emit into out (total rows; out.n and batch.n ignored)
 dbsp_status window_ranges_multi(hipStream_t s, const TraceArgs &t,
                                 const uint64_t *bk, int64_t bn, int have_prev,
                                 uint64_t s0, uint64_t e0, uint64_t s1,
                                 uint64_t e1, int64_t *table, int64_t *d_total);
 dbsp_status window_emit_multi(hipStream_t s, const TraceArgs &t,
-                              const uint64_t *bk, const uint64_t *bv,
-                              const int64_t *bw, const int64_t *table,
-                              int nreg, int64_t total, uint64_t *ok,
-                              uint64_t *ov, int64_t *ow);
+                              const Rows &batch, const int64_t *table,
+                              int nreg, int64_t total, const Rows &out);
 
-dbsp_status shard_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                       const int64_t *w, int64_t n, int nshards, uint64_t *ok,
-                       uint64_t *ov, int64_t *ow, int64_t *h_offsets);
+// out holds in.n rows (its n is ignored)
+dbsp_status shard_rows(hipStream_t s, const Rows &in, int nshards,
+                       const Rows &out, int64_t *h_offsets);
 
+// out0/out1 name caller-provided capacity columns; their n is WRITTEN (one
+// sync)
 dbsp_status flatmap_events(hipStream_t s, const dbsp_event *ev,
                            const EventCols *cols, int64_t n, int query,
-                           uint64_t *k0, uint64_t *v0, int64_t *w0,
-                           int64_t *n0, uint64_t *k1, uint64_t *v1,
-                           int64_t *w1, int64_t *n1);
+                           Rows *out0, Rows *out1);
 
-dbsp_status map_rows(hipStream_t s, const uint64_t *k, const uint64_t *v,
-                     const int64_t *w, int64_t n, int mode, uint64_t *ok,
-                     uint64_t *ov, int64_t *ow);
+// out holds in.n rows (its n is ignored)
+dbsp_status map_rows(hipStream_t s, const Rows &in, int mode, const Rows &out);
 
 // distinct keys of a consolidated (sorted) batch
 dbsp_status unique_keys(hipStream_t s, const uint64_t *kk, int64_t n,
                         uint64_t **okeys, int64_t *out_n);
 
-// ---- f64-weight variants (config C5: f64 sum aggregate; deterministic
-// position-fixed reduction order, tolerance 2 ulp * reduction depth) ----
-dbsp_status sort_cons_small_batch_f64(hipStream_t s, const SortArgs &args);
-dbsp_status merge_small_batch_f64(hipStream_t s, const MergeArgs &args);
-dbsp_status merge_rows_f64(hipStream_t s, const uint64_t *ak,
-                           const uint64_t *av, const double *aw, int64_t na,
-                           const uint64_t *bk, const uint64_t *bv,
-                           const double *bw, int64_t nb, uint64_t **ok,
-                           uint64_t **ov, double **ow, int64_t *out_n);
-dbsp_status consolidate_sorted_f64(hipStream_t s, const uint64_t *kk,
-                                   const uint64_t *vv, double *ww, int64_t n,
-                                   uint64_t **ok, uint64_t **ov, double **ow,
-                                   int64_t *out_n);
-dbsp_status agg_sum_batch_f64(hipStream_t s, const uint64_t *keys, int64_t nd,
-                              const uint64_t *ik, const double *iw, int64_t ni,
-                              double *acc);
-dbsp_status emit_nonzero_f64(hipStream_t s, const uint64_t *keys,
-                             const double *acc, int64_t nd, uint64_t *ok,
-                             uint64_t *ov, int64_t *ow, int64_t *h_count);
-
-// C5 synthetic operands: sorted-unique rows by construction
+// C5 synthetic operands: out.n (read) sorted-unique rows by construction
 // (k_i = stride*i + h(i)%jitter, jitter < stride; val_mode 0 = uniform f64
 // bits, 1 = zero)
-dbsp_status c5_gen_rows(hipStream_t s, int64_t n, uint64_t stride,
-                        uint64_t jitter, uint64_t seed, int val_mode,
-                        uint64_t *k, uint64_t *v, int64_t *w);
+dbsp_status c5_gen_rows(hipStream_t s, const Rows &out, uint64_t stride,
+                        uint64_t jitter, uint64_t seed, int val_mode);
 
 // radix-tree rolling aggregate (§8f4): per input row (partition, ts, w),
-// the weight sum over the partition's rows with time in [ts-width, ts]
-dbsp_status rolling_agg_rows(hipStream_t s, const uint64_t *k,
-                             const uint64_t *v, const int64_t *w, int64_t n,
-                             uint64_t width, uint64_t *ok, uint64_t *ov,
-                             int64_t *ow);
+// the weight sum over the partition's rows with time in [ts-width, ts];
+// out holds in.n rows (its n is ignored)
+dbsp_status rolling_agg_rows(hipStream_t s, const Rows &in, uint64_t width,
+                             const Rows &out);
 
 // ---- incremental partitioned rolling aggregate (rolling_aggregate.rs
 // :487-604); times and partitions < 2^32, ranges saturate at 0 / 2^32-1 ----
-// Merged run lists of a consolidated (p, ts)-sorted delta.  *ranges is one
-// 6*n-word device buffer (caller frees with cache_free) holding the columns
-// [gp | glo | ghi | ap | alo | ahi], each n words apart: the gather ranges
-// (p, [ts-before-after, ts+before+after]) in the first n_gather entries of
-// the g columns, the affected ranges (p, [ts-after, ts+before]) in the first
-// n_affected entries of the a columns.  *err = 1 (and no ranges) if a
-// partition or time is >= 2^32.  One host sync.
-dbsp_status roll_ranges(hipStream_t s, const uint64_t *dk, const uint64_t *dv,
-                        int64_t n, uint64_t before, uint64_t after,
-                        uint64_t **ranges, int64_t *n_gather,
+// Merged run lists of a consolidated (p, ts)-sorted delta (weights unread).
+// *ranges is one 6*n-word device buffer (caller frees with cache_free)
+// holding the columns [gp | glo | ghi | ap | alo | ahi], each n words apart:
+// the gather ranges (p, [ts-before-after, ts+before+after]) in the first
+// n_gather entries of the g columns, the affected ranges
+// (p, [ts-after, ts+before]) in the first n_affected entries of the a
+// columns.  *err = 1 (and no ranges) if a partition or time is >= 2^32.
+// One host sync.
+dbsp_status roll_ranges(hipStream_t s, const Rows &delta, uint64_t before,
+                        uint64_t after, uint64_t **ranges, int64_t *n_gather,
                         int64_t *n_affected, int *err);
 // copy the rows of every spine batch that fall in a range, weights times
 // sign.  mode 0: (k, v) in [(p, lo), (p, hi)]; mode 1: k in
 // [p<<32|lo, p<<32|hi].  Ranges must be disjoint; output is RAW (range-major,
-// batch-minor runs).  Buffers from the big-buffer cache (null when empty).
+// batch-minor runs).
 dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
                          const uint64_t *rlo, const uint64_t *rhi, int64_t nr,
                          const TraceArgs &t, int mode, int64_t sign,
-                         uint64_t **ok, uint64_t **ov, int64_t **ow,
-                         int64_t *out_n);
+                         Rows *out);
 // keep the rows of every spine batch whose time is >= bound, in order
 // (trace.rs:463-607 lower bound).  mode 0: time = v (rows (p, ts, w));
-// mode 1: time = k & 0xffffffff (rows (p<<32|ts, sum, w)).  ok/ov/ow/out_n
-// are caller arrays of t.nb entries: batch b's survivors in fresh buffers
-// from the big-buffer cache (null when none survive).  Stable, so a
-// consolidated batch stays consolidated.  One host sync for all lengths.
+// mode 1: time = k & 0xffffffff (rows (p<<32|ts, sum, w)).  out is a caller
+// array of t.nb entries: batch b's survivors in fresh columns (null when
+// none survive).  Stable, so a consolidated batch stays consolidated.  One
+// host sync for all lengths.
 dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
-                           uint64_t bound, uint64_t **ok, uint64_t **ov,
-                           int64_t **ow, int64_t *out_n);
-// per row (p, ts, w > 0) of the consolidated slice that the delta affects:
-// (p<<32|ts, sum of slice weights of p over [ts-before, ts+after], +1),
-// in slice order (sorted, distinct keys)
-dbsp_status roll_eval_rows(hipStream_t s, const uint64_t *sk,
-                           const uint64_t *sv, const int64_t *sw, int64_t n,
-                           const uint64_t *dk, const uint64_t *dv, int64_t nd,
-                           uint64_t before, uint64_t after, uint64_t **ok,
-                           uint64_t **ov, int64_t **ow, int64_t *out_n);
+                           uint64_t bound, Rows *out);
+// per row (p, ts, w > 0) of the consolidated slice that the delta affects
+// (delta's weights unread): (p<<32|ts, sum of slice weights of p over
+// [ts-before, ts+after], +1), in slice order (sorted, distinct keys)
+dbsp_status roll_eval_rows(hipStream_t s, const Rows &slice,
+                           const Rows &delta, uint64_t before, uint64_t after,
+                           Rows *out);
 
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 

@@ -65,6 +65,38 @@ def test_consolidate_f64_random_tolerance(ctx):
         _f64_zsets_close(got, exp)
 
 
+def _cancel_pairs_f64(rng, n_pairs, survivor=None):
+    """n_pairs distinct (k, v), each twice with weights +0.25*m and -0.25*m
+    (both +0.25*m for the pair at index `survivor`), shuffled."""
+    half = np.empty(n_pairs, dtype=ROW_DT)
+    half["k"] = rng.integers(0, 2**40, n_pairs)
+    half["v"] = rng.integers(0, 2**30, n_pairs)
+    assert len(np.unique(half[["k", "v"]])) == n_pairs
+    w = rng.integers(1, 9, n_pairs).astype(np.float64) * 0.25
+    half["w"] = w.view(np.int64)
+    other = half.copy()
+    if survivor is not None:
+        w[survivor] = -w[survivor]
+    other["w"] = (-w).view(np.int64)
+    return rng.permutation(np.concatenate([half, other]))
+
+
+def test_consolidate_f64_big_path_all_cancel(ctx):
+    """8,194 rows: the smallest size on the f64 big path (radix sort + global
+    segmented tree).  4,097 cancelling pairs leave nothing — zero sums of
+    either sign are dropped; one non-cancelling pair leaves exactly its row."""
+    rng = np.random.default_rng(34)
+    rows = _cancel_pairs_f64(rng, 4097)
+    assert len(rows) == 8194
+    assert len(oracle.consolidate_f64(rows)) == 0
+    assert len(ctx.sort_consolidate_f64(rows)) == 0
+    rows1 = _cancel_pairs_f64(rng, 4097, survivor=1234)
+    exp = oracle.consolidate_f64(rows1)
+    assert len(exp) == 1
+    got = ctx.sort_consolidate_f64(rows1)
+    assert np.array_equal(got, exp)
+
+
 def test_merge_f64(ctx):
     rng = np.random.default_rng(33)
     for na, nb in [(100, 100), (8000, 8000), (60_000, 40_000)]:

@@ -77,6 +77,32 @@ def test_sort_consolidate_parity(ctx):
         assert np.array_equal(got, exp), f"n={len(r)}"
 
 
+def test_sort_consolidate_big_path_all_cancel(ctx):
+    """Just above the chunked band (65,536 rows) and in a wide key box (no
+    dense route): every (k, v) pair appears with +w and -w, so the big-path
+    consolidate has 32,769 segments and no output; then with one survivor."""
+    rng = np.random.default_rng(11)
+    n = 32_769
+    half = np.empty(n, dtype=ROW_DT)
+    half["k"] = rng.integers(0, 2**40, n)
+    half["v"] = rng.integers(0, 2**30, n)
+    half["w"] = rng.integers(1, 4, n)
+    assert len(np.unique(half[["k", "v"]])) == n
+    neg = half.copy()
+    neg["w"] = -neg["w"]
+    rows = rng.permutation(np.concatenate([half, neg]))
+    assert len(rows) == 65_538
+    exp = oracle.consolidate(rows)
+    assert len(exp) == 0
+    got = ctx.sort_consolidate(rows)
+    assert len(got) == 0 and np.array_equal(got, exp)
+    one = np.array([(2**39 + 5, 77, 3)], dtype=ROW_DT)
+    rows1 = rng.permutation(np.concatenate([rows, one]))
+    got = ctx.sort_consolidate(rows1)
+    assert np.array_equal(got, one)
+    assert np.array_equal(got, oracle.consolidate(rows1))
+
+
 def test_merge_parity(ctx):
     rng = np.random.default_rng(2)
     for na, nb in [(0, 0), (0, 100), (100, 0), (1, 1), (5000, 3),
