@@ -594,6 +594,180 @@ __device__ inline uint32_t fuse_scan(uint32_t thread_sum, uint32_t *wave_tot,
     __shared__ uint64_t smax[2];                                           \
     __shared__ uint64_t smin[2];
 
+// ---- small-batch path of the fused sort (integer weights, n <= 1024) ----
+// One row per thread, held in registers.  Integer sums do not depend on the
+// order of their terms, so the sort needs neither stability nor an index
+// payload: it orders (k, v) and carries w along.  Threads past n hold the pad
+// row (~0, ~0, w = 0); a pad either joins a real (~0, ~0) segment adding 0 or
+// forms a zero-weight segment that the compaction drops, so the consolidation
+// treats all 1024 rows alike.
+
+// lane ^ JJ exchange inside the wave: quad permutes for 1 and 2, else bpermute
+template <int JJ>
+__device__ __forceinline__ uint32_t lane_xor32(uint32_t x) {
+    if constexpr (JJ == 1)
+        return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true);
+    else if constexpr (JJ == 2)
+        return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, true);
+    else
+        return (uint32_t)__shfl_xor((int)x, JJ, WAVE);
+}
+template <int JJ>
+__device__ __forceinline__ uint64_t lane_xor64(uint64_t x) {
+    const uint32_t lo = lane_xor32<JJ>((uint32_t)x);
+    const uint32_t hi = lane_xor32<JJ>((uint32_t)(x >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// one compare-exchange of a bitonic network against the partner's row: the
+// lower position of an ascending pair (and the upper of a descending one)
+// keeps the smaller (k, v).  Equal keys never move, so both sides agree.
+__device__ __forceinline__ void small_cmpx(uint64_t &k, uint64_t &v,
+                                           int64_t &w, uint64_t pk,
+                                           uint64_t pv, int64_t pw,
+                                           bool keep_min) {
+    const bool plt = pk < k || (pk == k && pv < v);
+    const bool pgt = pk > k || (pk == k && pv > v);
+    if (keep_min ? plt : pgt) {
+        k = pk;
+        v = pv;
+        w = pw;
+    }
+}
+
+// the compare distances JJ, JJ/2, .., 1 of one merge, all inside the wave
+template <int JJ>
+__device__ __forceinline__ void small_wave_merge(uint64_t &k, uint64_t &v,
+                                                 int64_t &w, bool up,
+                                                 int lane) {
+    const uint64_t pk = lane_xor64<JJ>(k);
+    const uint64_t pv = lane_xor64<JJ>(v);
+    const int64_t pw = (int64_t)lane_xor64<JJ>((uint64_t)w);
+    small_cmpx(k, v, w, pk, pv, pw, ((lane & JJ) == 0) == up);
+    if constexpr (JJ > 1) small_wave_merge<JJ / 2>(k, v, w, up, lane);
+}
+
+// exclusive prefix of this wave and the total over the 16 per-wave counts in
+// cells[0..16), computed by every wave for itself: one barrier (the
+// caller's, after the cells were written) instead of fuse_scan's three
+__device__ __forceinline__ uint32_t small_wave_base(const uint32_t *cells,
+                                                    int wid, int lane,
+                                                    uint32_t *total) {
+    const int nw = FUSE_THREADS / WAVE;
+    const uint32_t t = lane < nw ? cells[lane] : 0;
+    uint32_t sc = t;
+    for (int d = 1; d < nw; d <<= 1) {
+        const uint32_t up = __shfl_up(sc, d, WAVE);
+        if (lane >= d) sc += up;
+    }
+    *total = __shfl(sc, nw - 1, WAVE);
+    return __shfl(sc - t, wid, WAVE);
+}
+
+// Sort + consolidate the block's rows (thread tid holds row tid, pads past
+// n) into ok/ov/ow and *out_len.  0 < n <= FUSE_THREADS, block-uniform; all
+// 1024 threads call it.  Global memory is touched by the final store only.
+//
+// Bitonic network over p2 = max(64, pow2 >= n) positions.  Distances below 64
+// exchange across lanes; distances >= 64 go through LDS, double-buffered so
+// each costs ONE block barrier (6 at p2 = 512, 10 at 1024).  Waves wholly
+// past p2 hold pads only (already in place: pads are the maximum) and skip
+// the compares but reach every barrier.  The consolidation adds 4 barriers.
+//
+// LDS: bufA = k[2][1024] + w[2][1024], bufB = v[2][1024] + sums[1024] +
+// edge k/v[16]; cnt[0..16) holds the second scan's cells.
+__device__ __forceinline__ void sort_cons_small_rows(
+    uint64_t k, uint64_t v, int64_t w, int64_t n, uint64_t *ok, uint64_t *ov,
+    int64_t *ow, int64_t *out_len, uint32_t *bufA, uint32_t *bufB,
+    uint32_t *cnt, uint32_t *wave_tot) {
+    const int tid = threadIdx.x;
+    const int wid = tid / WAVE;
+    const int lane = tid % WAVE;
+    const uint64_t lt = ((uint64_t)1 << lane) - 1;
+    uint64_t *xk = (uint64_t *)bufA;
+    int64_t *xw = (int64_t *)bufA + 2 * FUSE_THREADS;
+    uint64_t *xv = (uint64_t *)bufB;
+    unsigned long long *sums =
+        (unsigned long long *)bufB + 2 * FUSE_THREADS;
+    uint64_t *edge_k = (uint64_t *)bufB + 3 * FUSE_THREADS;
+    uint64_t *edge_v = edge_k + FUSE_THREADS / WAVE;
+
+    sums[tid] = 0;  // ordered before the adds by the barriers below
+
+    int p2 = WAVE;
+    while (p2 < n) p2 <<= 1;
+    const bool active = wid * WAVE < p2;  // wave-uniform
+
+    // ---- sort ----
+    if (active) {
+        small_wave_merge<1>(k, v, w, (tid & 2) == 0, lane);
+        small_wave_merge<2>(k, v, w, (tid & 4) == 0, lane);
+        small_wave_merge<4>(k, v, w, (tid & 8) == 0, lane);
+        small_wave_merge<8>(k, v, w, (tid & 16) == 0, lane);
+        small_wave_merge<16>(k, v, w, (tid & 32) == 0, lane);
+        small_wave_merge<32>(k, v, w, (tid & 64) == 0, lane);
+    }
+    int step = 0;
+    for (int kk = 2 * WAVE; kk <= p2; kk <<= 1) {
+        const bool up = (tid & kk) == 0;
+        for (int jj = kk >> 1; jj >= WAVE; jj >>= 1, step++) {
+            const int b = (step & 1) * FUSE_THREADS;
+            if (active) {
+                xk[b + tid] = k;
+                xv[b + tid] = v;
+                xw[b + tid] = w;
+            }
+            __syncthreads();
+            if (active) {
+                const int p = b + (tid ^ jj);  // < p2: jj < p2 and tid < p2
+                small_cmpx(k, v, w, xk[p], xv[p], xw[p],
+                           ((tid & jj) == 0) == up);
+            }
+        }
+        if (active) small_wave_merge<32>(k, v, w, up, lane);
+    }
+
+    // ---- consolidate ----
+    // head flags from the left neighbour; lane 0 takes the previous wave's
+    // last row through LDS
+    if (lane == WAVE - 1) {
+        edge_k[wid] = k;
+        edge_v[wid] = v;
+    }
+    __syncthreads();
+    uint64_t lk_ = __shfl_up(k, 1, WAVE);
+    uint64_t lv_ = __shfl_up(v, 1, WAVE);
+    if (lane == 0 && wid > 0) {
+        lk_ = edge_k[wid - 1];
+        lv_ = edge_v[wid - 1];
+    }
+    const bool head = tid == 0 || lk_ != k || lv_ != v;
+    const uint64_t hm = __ballot(head);
+    if (lane == 0) wave_tot[wid] = (uint32_t)__popcll(hm);
+    __syncthreads();
+    uint32_t nseg;
+    const uint32_t hbase = small_wave_base(wave_tot, wid, lane, &nseg);
+    // heads at or before this row, minus 1: < 1024 by construction
+    const uint32_t seg =
+        hbase + (uint32_t)__popcll(hm & lt) + (head ? 1u : 0u) - 1u;
+    if (w != 0) atomicAdd(&sums[seg], (unsigned long long)w);
+    __syncthreads();
+    const int64_t tot = head ? (int64_t)sums[seg] : 0;
+    const bool nz = tot != 0;  // a nonzero segment holds a real row
+    const uint64_t zm = __ballot(nz);
+    if (lane == 0) cnt[wid] = (uint32_t)__popcll(zm);
+    __syncthreads();
+    uint32_t nout;
+    const uint32_t zbase = small_wave_base(cnt, wid, lane, &nout);
+    const uint32_t p = zbase + (uint32_t)__popcll(zm & lt);
+    if (nz && (int64_t)p < n) {
+        ok[p] = k;
+        ov[p] = v;
+        ow[p] = tot;
+    }
+    if (tid == 0) *out_len = (int64_t)nout;
+}
+
 template <typename W>
 __device__ __forceinline__ void sort_cons_body(
     const uint64_t *kin, const uint64_t *vin, const W *win, int64_t n,
@@ -627,12 +801,26 @@ __device__ __forceinline__ void sort_cons_body(
         return;
     }
 
-    const int rounds = (int)((n + FUSE_THREADS - 1) / FUSE_THREADS);  // <= 8
+    if constexpr (sizeof(W) == 8 && (W)0.5 == (W)0) {  // integer weights
+        if (n <= FUSE_THREADS) {  // block-uniform: one row per thread
+            const bool real = tid < n;
+            const uint64_t k = real ? kin[tid] : ~0ull;
+            const uint64_t v = real ? vin[tid] : ~0ull;
+            const int64_t w = real ? (int64_t)win[tid] : 0;
+            sort_cons_small_rows(k, v, w, n, ok, ov, (int64_t *)ow, out_len,
+                                 bufA, bufB, cnt, wave_tot);
+            return;
+        }
+    }
+
+    const int rounds =(int)((n + FUSE_THREADS - 1) / FUSE_THREADS);  // <= 8
     const int nwaves = FUSE_THREADS / WAVE;
     uint32_t *src = bufA, *dst = bufB;
 
     if (n <= 2048) {
         // ---- bitonic fast path ----
+        // (f64 weights, and integer batches of 1025..2048 rows: smaller
+        // integer batches left through sort_cons_small_rows above)
         // Sub-2k tick batches (delta sides, tick outputs) are where the
         // radix path is pass-count-bound (~35 us regardless of n: ~16+
         // digit passes of block-wide ballots and syncs).  A stable LDS
@@ -2047,6 +2235,11 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_scan_small(
 // are unrolled to MAX_TRACE_BATCHES predicated loads, so they are issued
 // together instead of one load latency per batch.
 //
+// A combined total within one row per thread (<= 1024) never reaches the
+// capacity buffer: thread o keeps emitted row o in registers and the sort's
+// small-batch path takes it from there.  d_final is then >= 0, and the host
+// reads the capacity buffer only when d_final < 0.
+//
 // Verdicts (the host reads them after the tail readback):
 //   totals[p]  plan p's row total, -1 if one of its lengths is a lost
 //              speculation; offsets[p][] (plan-local) is written for every
@@ -2144,6 +2337,12 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_tail_small(
     // ---- emit: only if the combined rows fit the capacity buffer ----
     const int64_t acc = total;
     const bool okf = !neg && acc <= a.cap;
+    // within one row per thread the rows go to the sort in registers and
+    // skip the capacity buffer: the host reads that buffer only when
+    // d_final < 0, and this branch always leaves d_final >= 0
+    const bool onchip = okf && total <= FUSE_THREADS;
+    uint64_t rk = ~0ull, rv = ~0ull;  // pad row for threads past the total
+    int64_t rw = 0;
     if (okf) {
         for (uint32_t o = tid; o < total; o += FUSE_THREADS) {
             int lo = 0, hi = R;
@@ -2172,9 +2371,16 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_tail_small(
             uint64_t hi_o, lo_o;
             const bool valid = proj_out(a.proj[p], 0, key, a.dv[p][i],
                                         t.v[b][ti], hi_o, lo_o);
-            a.ek[o] = hi_o;
-            a.ev[o] = lo_o;
-            a.ew[o] = valid ? a.dw[p][i] * t.w[b][ti] : 0;
+            const int64_t wo = valid ? a.dw[p][i] * t.w[b][ti] : 0;
+            if (onchip) {  // o == tid: this thread's only row
+                rk = hi_o;
+                rv = lo_o;
+                rw = wo;
+            } else {
+                a.ek[o] = hi_o;
+                a.ev[o] = lo_o;
+                a.ew[o] = wo;
+            }
         }
     }
     __syncthreads();  // the cells are the sort's buffers from here on
@@ -2184,6 +2390,15 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_join_tail_small(
     }
     if (!okf || acc > FUSE_MAX) {
         if (tid == 0) *a.d_final = -1;
+        return;
+    }
+    if (onchip) {  // block-uniform
+        if (acc == 0) {
+            if (tid == 0) *a.d_final = 0;
+            return;
+        }
+        sort_cons_small_rows(rk, rv, rw, acc, a.ok, a.ov, a.ow, a.d_final,
+                             bufA, bufB, cnt, wave_tot);
         return;
     }
     // the emitted rows were stored by this workgroup; the barrier above
