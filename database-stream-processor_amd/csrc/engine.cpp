@@ -83,10 +83,10 @@ struct KernelStat {
 //                        consumed after the next train's readbacks have
 //                        landed, so it cannot live inside a base
 enum : int {
-    LEN_SLOTS = 56,
+    LEN_SLOTS = 60,
     LEN_OP = 0,
-    LEN_TICK = 18,       // kernel-written slots of a tick base
-    LEN_BASE_N = 26,     // slots per tick base, host tail block included
+    LEN_TICK = 20,       // kernel-written slots of a tick base
+    LEN_BASE_N = 28,     // slots per tick base, host tail block included
     LEN_BASE0 = 0,
     LEN_BASE1 = LEN_BASE_N,
     LEN_ROUND = 2 * LEN_BASE_N,
@@ -98,18 +98,24 @@ enum : int {
     L_DENSE = 5,         // q5: chained dense-sort length of the bid delta
     L_FINAL = 6,         // output (final) sort length
     L_WIN = 7,           // single-spine window total (q5, window_vs_spine)
-    L_RAW = 8,           // 8/9: flatmap raw lengths of streams A/B
+    L_RAW = 8,           // 8/9: flatmap raw lengths of streams A/B: the
+                         // flatmap's ticket counters.  A taking delta sort
+                         // (q3's train) hands them back zeroed and leaves
+                         // the lengths at L_RAWN instead
     L_DELTA = 10,        // 10/11: consolidated delta lengths (-1: overflow)
     L_WIN2 = 12,         // 12/13: q8's two window totals (-1: lost spec)
     L_MINMAX = 12,       // 12..15: q5's {kmin, vmin, kmax, vmax} of the bids
     L_XCHG = 16,         // 16/17: framed-exchange receive totals (-1:
                          // frame overflow); q3's unsharded train reuses them
                          // for its two accumulator-merge lengths
+    L_RAWN = 18,         // 18/19: raw lengths as a taking delta sort saw
+                         // them (what the head readback of a train carries
+                         // in place of L_RAW, which then reads 0)
     // A chained q3 tick reads back twice.
     // HEAD: device [L_HEAD, L_HEAD + L_HEAD_N) to the same host offsets.  It
     // carries what is final once the delta sorts and the accumulator merge
-    // are: L_RAW, L_DELTA and L_XCHG.  The host wakes on it for the
-    // speculation verdict.
+    // are: L_RAW (or L_RAWN behind a taking sort), L_DELTA and L_XCHG.  The
+    // host wakes on it for the speculation verdict.
     L_HEAD = L_RAW,
     L_HEAD_N = LEN_TICK - L_RAW,
     // TAIL: device [L_PLAN, L_FINAL] — everything the join tail kernel
@@ -119,10 +125,10 @@ enum : int {
     // sorts) may run between a tail readback landing and its consumption.
     LH_TAIL_SHIFT = LEN_TICK,
     LH_TAIL_N = L_FINAL - L_PLAN + 1,
-    LH_PLAN = L_PLAN + LH_TAIL_SHIFT,              // 18..20
-    LH_EMIT_TOTAL = L_EMIT_TOTAL + LH_TAIL_SHIFT,  // 21
-    LH_EMIT_FLAG = L_EMIT_FLAG + LH_TAIL_SHIFT,    // 22
-    LH_FINAL = L_FINAL + LH_TAIL_SHIFT,            // 24
+    LH_PLAN = L_PLAN + LH_TAIL_SHIFT,              // 20..22
+    LH_EMIT_TOTAL = L_EMIT_TOTAL + LH_TAIL_SHIFT,  // 23
+    LH_EMIT_FLAG = L_EMIT_FLAG + LH_TAIL_SHIFT,    // 24
+    LH_FINAL = L_FINAL + LH_TAIL_SHIFT,            // 26
 };
 static_assert(LEN_BASE1 + LEN_BASE_N <= LEN_ROUND &&
                   LEN_ROUND + LEN_ROUND_N <= LEN_SLOTS,
@@ -135,8 +141,14 @@ static_assert(L_PLAN + 3 <= L_EMIT_TOTAL && L_EMIT_TOTAL < L_EMIT_FLAG &&
 static_assert(L_HEAD <= L_RAW && L_HEAD <= L_DELTA &&
                   L_DELTA + 2 <= L_HEAD + L_HEAD_N &&
                   L_XCHG + 2 <= L_HEAD + L_HEAD_N &&
+                  L_HEAD <= L_RAWN && L_RAWN + 2 <= L_HEAD + L_HEAD_N &&
                   L_HEAD + L_HEAD_N <= LEN_TICK,
               "the head readback carries raw, delta and merge lengths");
+static_assert(L_XCHG + 2 <= L_RAWN && L_RAWN + 2 <= LEN_TICK,
+              "the taken raw lengths have slots of their own");
+static_assert(LEN_OP + SORT_BATCH_MAX <= L_RAW,
+              "no op scratch slot aliases a flatmap counter: only flatmaps "
+              "and taking sorts write those (dbsp_ctx::raw_zero)");
 static_assert(LH_PLAN >= LEN_TICK && LH_PLAN >= LEN_OP + SORT_BATCH_MAX &&
                   LH_PLAN + LH_TAIL_N <= LEN_BASE_N,
               "tail-readback host range stays inside its base, clear of "
@@ -159,6 +171,18 @@ struct dbsp_ctx {
     int64_t *h_len = nullptr;
     int64_t *d_mid = nullptr;  // merge_mid per-WG count scratch
                                // (MERGE_BATCH_MAX pairs)
+    // "raw counters known zero", per tick base (0: LEN_BASE0, 1: LEN_BASE1):
+    // the base's L_RAW pair holds 0 once everything enqueued so far has run,
+    // because the last thing enqueued that writes it is a taking sort behind
+    // the flatmap.  flatmap_chain consumes it (skips its memset and clears
+    // it: the flatmap dirties the counters); only sort_pair_chain's taking
+    // form sets it.  Nothing else writes those two slots.
+    bool raw_zero[2] = {false, false};
+    bool q3_fold = true;       // in-train fold by k_acc_fold (DBSP_Q3_FOLD=0:
+                               // merge_mid_batch, for comparison)
+    bool q3_take = true;       // the train's sorts take the flatmap counters
+                               // (DBSP_Q3_TAKE=0: plain sorts, so every
+                               // flatmap keeps its counter fill)
     int timer_depth = 0;  // ScopedTimer nesting guard (shared event pair)
     // per-tick transient bump arena (reset at each engine tick; falls back to
     // the stream-ordered pool when exhausted)
@@ -283,6 +307,10 @@ extern "C" dbsp_status dbsp_ctx_create(dbsp_ctx **out, int device) {
     c->force_shard = fs && fs[0] == '1';
     const char *fk = getenv("DBSP_Q3_FORK");
     c->q3_fork = !c->profile && !(fk && fk[0] == '0');
+    const char *fo = getenv("DBSP_Q3_FOLD");
+    c->q3_fold = !(fo && fo[0] == '0');
+    const char *tk = getenv("DBSP_Q3_TAKE");
+    c->q3_take = !(tk && tk[0] == '0');
     HIP_CHECK_ST(hipMalloc(&c->d_len, LEN_SLOTS * sizeof(int64_t)));
     HIP_CHECK_ST(hipMalloc(&c->d_mid, MERGE_BATCH_MAX * MERGE_MID_SCRATCH *
                                           sizeof(int64_t)));
@@ -461,15 +489,30 @@ static inline void sort_slot(SortArgs &sa, int i, const DevBatch &in,
     sa.ok[i] = out.k; sa.ov[i] = out.v; sa.ow[i] = out.w;
 }
 
+// the taking form: the length comes from the producer's counter `take`,
+// which the sort hands back zeroed, leaving what it saw at `seen`; in.n is
+// the capacity of the input columns
+static inline void sort_slot_take(SortArgs &sa, int i, const DevBatch &in,
+                                  const DevBatch &scratch, const DevBatch &out,
+                                  int64_t *take, int64_t *seen) {
+    sort_slot(sa, i, in, scratch, out, take);
+    sa.n_dev[i] = nullptr;
+    sa.n_take[i] = take;
+    sa.n_seen[i] = seen;
+    sa.n_cap[i] = in.n;
+}
+
 // pair p of a batched merge: a + b -> out.  dnb (a device length slot)
-// overrides b's host length, which then stays 0.
+// overrides b's host length, which then stays 0; bcap bounds it for the
+// accumulator fold (out holds a.n + bcap rows).
 static inline void merge_pair(MergeArgs &ma, int p, const DevBatch &a,
                               const DevBatch &b, const DevBatch &out,
-                              const int64_t *dnb = nullptr) {
+                              const int64_t *dnb = nullptr, int64_t bcap = 0) {
     ma.ak[p] = a.k; ma.av[p] = a.v; ma.aw[p] = a.w; ma.na[p] = a.n;
     ma.bk[p] = b.k; ma.bv[p] = b.v; ma.bw[p] = b.w;
     ma.nb[p] = dnb ? 0 : b.n;
     ma.dnb[p] = dnb;
+    ma.bcap[p] = dnb ? bcap : b.n;
     ma.ok[p] = out.k; ma.ov[p] = out.v; ma.ow[p] = out.w;
 }
 
@@ -801,6 +844,38 @@ extern "C" dbsp_status dbsp_merge(dbsp_ctx *c, const dbsp_batch *a,
     DevBatch res;
     TRY(merge_batches(c, as_batch(a), as_batch(b), res));
     TRY(dbsp_ctx_sync(c));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_acc_fold(dbsp_ctx *c, const dbsp_batch *acc,
+                                     const dbsp_batch *delta, dbsp_batch *out) {
+    const DevBatch a = as_batch(acc), b = as_batch(delta);
+    if (a.n < 0 || b.n > 8192) return DBSP_ERR_INVALID;
+    // the delta length travels through a device slot, verbatim, as the
+    // train's does (a negative one is the poison the fold must pass on)
+    const int64_t bcap = b.n > 0 ? b.n : 0;
+    DevBatch res;
+    TRY(alloc_batch(c, a.n + bcap, res));
+    c->h_len[LEN_OP] = b.n;
+    HIP_CHECK_ST(hipMemcpyAsync(c->d_len + LEN_OP, c->h_len + LEN_OP,
+                                sizeof(int64_t), hipMemcpyHostToDevice,
+                                c->stream));
+    MergeArgs ma{};
+    ma.np = 1;
+    merge_pair(ma, 0, a, b, res, c->d_len + LEN_OP, bcap);
+    ma.d_len = c->d_len + LEN_OP + 1;
+    dbsp_status st;
+    {
+        ScopedTimer t(c, 1, (double)(a.n + bcap) * 48.0);
+        st = dbspk::acc_fold_batch(c->stream, ma, false);
+    }
+    if (st == DBSP_OK) st = read_len(c, LEN_OP + 1, 1);
+    if (st == DBSP_OK) st = checked_len(c, LEN_OP + 1, res.n);
+    if (st != DBSP_OK) {
+        free_batch(c, res);
+        return st;
+    }
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -1615,10 +1690,44 @@ static dbsp_status shard_exchange_pair(dbsp_ctx *c, DevBatch l0, DevBatch l1,
     return sort_pair(c, r0, r1, o0, o1);
 }
 
+static inline double host_us() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
+}
+
+// DBSP_COMMIT_PROF=1: host time of q3_enqueue_train split by group of
+// runtime calls (printed with the commit's line).  hook_mark(i) charges the
+// time since the previous mark to group i.
+enum : int {
+    HK_FLATMAP,  // raw-stream arena bumps, counter fill (if any), flatmap
+    HK_SORT,     // sort scratch + delta allocations, delta sorts
+    HK_ALLOC,    // accumulator-result allocations
+    HK_FORK,     // fork event record + side-stream wait
+    HK_MERGE,    // accumulator fold / merge launch
+    HK_HEAD,     // head copy + ev_tick record
+    HK_PROBE,    // plan build + probe launch
+    HK_TAIL,     // join tail buffers + launch
+    HK_JOIN,     // join wait + tail copy + ev_tail record
+    HK_N
+};
+static const bool g_hook_prof = []() {
+    const char *v = getenv("DBSP_COMMIT_PROF");
+    return v && v[0] == '1';
+}();
+static double g_hook_t = 0, g_hook_us[HK_N];
+static inline void hook_mark(int i) {
+    if (!g_hook_prof) return;
+    const double t = host_us();
+    g_hook_us[i] += t - g_hook_t;
+    g_hook_t = t;
+}
+
 // flatmap events slice into up to two raw streams, then sort+consolidate
 static dbsp_status build_deltas_chain(dbsp_engine *e, const dbsp_event *d_ev,
                                       int64_t n, DevBatch &rawA, DevBatch &rawB,
-                                      DevBatch &oA, DevBatch &oB, int sb = 0);
+                                      DevBatch &oA, DevBatch &oB, int sb = 0,
+                                      bool take = false);
 
 // If d_ev points into the staged event array, return its column-split view
 // (shifted to the same offset) so the flatmap reads coalesced SoA streams.
@@ -1634,7 +1743,10 @@ static bool staged_cols(dbsp_engine *e, const dbsp_event *d_ev,
 }
 
 // chained flatmap: allocate both raw streams (transient) and launch the
-// flatmap with its two row counters left on device at d_len[sb + L_RAW..]
+// flatmap with its two row counters left on device at d_len[sb + L_RAW..].
+// The counters are zeroed by a memset in front of the flatmap unless the
+// base's raw_zero flag says a taking sort already did it; either way the
+// flag is cleared, because the flatmap leaves them non-zero.
 static dbsp_status flatmap_chain(dbsp_engine *e, const dbsp_event *d_ev,
                                  int64_t n, DevBatch &rawA, DevBatch &rawB,
                                  int sb = LEN_BASE0) {
@@ -1644,19 +1756,25 @@ static dbsp_status flatmap_chain(dbsp_engine *e, const dbsp_event *d_ev,
     TRY(alloc_batch(c, cap, rawB, true));
     dbspk::EventCols cols{};
     const bool hc = staged_cols(e, d_ev, cols);
+    bool &known_zero = c->raw_zero[sb == LEN_BASE1];
+    const bool ctr_zero = known_zero;
+    known_zero = false;
     return dbspk::flatmap_events_chain(c->stream, d_ev, hc ? &cols : nullptr,
                                        n, e->query, rawA, rawB,
-                                       (uint64_t *)(c->d_len + sb + L_RAW));
+                                       (uint64_t *)(c->d_len + sb + L_RAW),
+                                       ctr_zero);
 }
 
 // speculative fused sort of two chained streams: input lengths read from the
 // device slots nA/nB, output lengths (or -1) left at d_len[sb + L_DELTA..];
-// oA/oB stay pending (n = -1) until the caller's readback
+// oA/oB stay pending (n = -1) until the caller's readback.  take: nA/nB are
+// the base's flatmap counters (L_RAW); the sort hands them back zeroed,
+// leaves the lengths at L_RAWN and so re-establishes raw_zero for the base.
 static dbsp_status sort_pair_chain(dbsp_ctx *c, const DevBatch &inA,
                                    const DevBatch &inB, int64_t capA,
-                                   int64_t capB, const int64_t *nA,
-                                   const int64_t *nB, int sb, int64_t n_events,
-                                   DevBatch &oA, DevBatch &oB) {
+                                   int64_t capB, int64_t *nA, int64_t *nB,
+                                   int sb, int64_t n_events, DevBatch &oA,
+                                   DevBatch &oB, bool take = false) {
     DevBatch sA, sB;
     TRY(alloc_batch(c, capA, sA, true));
     TRY(alloc_batch(c, capB, sB, true));
@@ -1664,13 +1782,19 @@ static dbsp_status sort_pair_chain(dbsp_ctx *c, const DevBatch &inA,
     TRY(alloc_batch(c, capB, oB));
     SortArgs sa{};
     sa.nb = 2;
-    sort_slot(sa, 0, inA, sA, oA, nA);
-    sort_slot(sa, 1, inB, sB, oB, nB);
+    if (take) {
+        sort_slot_take(sa, 0, inA, sA, oA, nA, c->d_len + sb + L_RAWN);
+        sort_slot_take(sa, 1, inB, sB, oB, nB, c->d_len + sb + L_RAWN + 1);
+    } else {
+        sort_slot(sa, 0, inA, sA, oA, nA);
+        sort_slot(sa, 1, inB, sB, oB, nB);
+    }
     sa.d_len = c->d_len + sb + L_DELTA;
     {
         ScopedTimer t(c, 0, (double)n_events * 48.0);
         TRY(dbspk::sort_cons_small_batch(c->stream, sa, false));
     }
+    if (take) c->raw_zero[sb == LEN_BASE1] = true;
     oA.n = -1;
     oB.n = -1;
     return DBSP_OK;
@@ -1757,12 +1881,16 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
 // sized paths if the speculation lost.
 static dbsp_status build_deltas_chain(dbsp_engine *e, const dbsp_event *d_ev,
                                       int64_t n, DevBatch &rawA, DevBatch &rawB,
-                                      DevBatch &oA, DevBatch &oB, int sb) {
+                                      DevBatch &oA, DevBatch &oB, int sb,
+                                      bool take) {
     dbsp_ctx *c = e->ctx;
     const int64_t cap = n > 0 ? n : 1;
     TRY(flatmap_chain(e, d_ev, n, rawA, rawB, sb));
-    return sort_pair_chain(c, rawA, rawB, cap, cap, c->d_len + sb + L_RAW,
-                           c->d_len + sb + L_RAW + 1, sb, n, oA, oB);
+    hook_mark(HK_FLATMAP);
+    TRY(sort_pair_chain(c, rawA, rawB, cap, cap, c->d_len + sb + L_RAW,
+                        c->d_len + sb + L_RAW + 1, sb, n, oA, oB, take));
+    hook_mark(HK_SORT);
+    return DBSP_OK;
 }
 
 // Sharded chained front (q3-class pair streams): flatmap -> hash-scatter
@@ -2627,8 +2755,8 @@ extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
 // per-spine memtable) is off the critical path: nothing in the tick reads
 // its result — the probes read the pre-insert spines — so it FORKS to a side
 // stream:
-//   main: flatmap -> delta sorts -> record ev_fork
-//   side: wait ev_fork -> accumulator merge -> head readback -> record ev_tick
+//   main: flatmap (no fill) -> delta sorts (take) -> record ev_fork
+//   side: wait ev_fork -> accumulator fold -> head readback -> record ev_tick
 //   main: probe -> join tail -> wait ev_tick -> tail readback -> record ev_tail
 // Ordering argument (what buffer recycling and slot reuse rest on):
 //  1. The main stream joins the side stream (wait ev_tick, the side
@@ -2643,9 +2771,29 @@ extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
 //     tick t enqueued on the main stream before the enqueue of train t+1.
 //  3. Hence any two users of a recycled buffer, of a length slot or of the
 //     merge scratch d_mid are ordered exactly as they were on one stream.
-//     d_mid in particular: the spill rounds of commit t are main-stream work
-//     enqueued before ev_fork(t+1) (rule 2) and after the join of train t
-//     (rule 1), so they never overlap a side merge.
+//     The accumulator fold uses no d_mid; rule 2 still carries the recycled
+//     buffers and length slots, and d_mid under DBSP_Q3_FOLD=0: the spill
+//     rounds of commit t are main-stream work enqueued before ev_fork(t+1)
+//     (rule 2) and after the join of train t (rule 1), so they never
+//     overlap a side merge.
+//
+// Counter hand-back: a train's delta sorts TAKE the flatmap's two ticket
+// counters (L_RAW of the train's base): each sort block reads its counter,
+// leaves the length at L_RAWN of the same base and writes 0 back.  So the
+// next flatmap on that base is launched without a counter fill
+// (dbsp_ctx::raw_zero says when that holds; every path that runs a plain
+// sort behind its flatmap keeps the fill and leaves the flag clear).
+// Ordering: flatmap(t) and the taking sort(t) are consecutive main-stream
+// launches.  Between that sort and the next flatmap on the same base — a
+// later train's, or a single step's on base 0, main-stream work behind it
+// either way — nothing reads or writes the two counters: the side stream's
+// head readback copies the base's head range, where it finds the lengths at
+// L_RAWN (the L_RAW words it also copies are dead), a lost speculation
+// replays from H[L_RAWN], and no op scratch slot aliases L_RAW
+// (static_assert above).  If the invariant broke anyway, the counters would
+// overshoot: the flatmap stores nothing at or past its capacity, the taking
+// sort poisons a count above the capacity, and the replay refuses a raw
+// count above the tick's event count.
 // Under DBSP_PROFILE (ScopedTimer's events assume one stream) and with
 // DBSP_Q3_FORK=0 the side work stays on the main stream, in the same order.
 //
@@ -3041,8 +3189,15 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         c->arena_off = save_off;
         T.pending = false;
     };
+    if (g_hook_prof) {
+        memset(g_hook_us, 0, sizeof(g_hook_us));
+        g_hook_t = host_us();
+    }
+    // the delta sorts TAKE the flatmap's counters (lengths to L_RAWN,
+    // counters handed back zeroed), so this base's next flatmap needs no
+    // counter fill: see "counter hand-back" above the q3 tick
     dbsp_status st = build_deltas_chain(e, d_ev, n, T.rawA, T.rawP, T.oA,
-                                        T.oP, sb);
+                                        T.oP, sb, /*take=*/c->q3_take);
     if (st != DBSP_OK) {
         bail();
         return st;
@@ -3073,10 +3228,12 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
                 bail();
                 return DBSP_OK;
             }
+            // a delta has at most one row per event: res holds acc.n + n
             merge_pair(ma, s, acc, s == 0 ? T.oA : T.oP, T.res[s],
-                       c->d_len + sb + L_DELTA + s);
+                       c->d_len + sb + L_DELTA + s, /*bcap=*/n);
             ma.np++;
         }
+        hook_mark(HK_ALLOC);
         // result lengths ride in the base's L_XCHG pair (unused on the
         // unsharded train path), inside the head readback's range
         ma.d_len = c->d_len + sb + L_XCHG;
@@ -3086,10 +3243,18 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
             HIP_CHECK_ST(hipEventRecord(c->ev_fork[evi], c->stream));
             HIP_CHECK_ST(hipStreamWaitEvent(ss, c->ev_fork[evi], 0));
         }
-        TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid, false));
+        hook_mark(HK_FORK);
+        // the fold needs no scratch and no barrier between workgroups;
+        // DBSP_Q3_FOLD=0 keeps the general merge here for comparison
+        if (c->q3_fold)
+            TRY(dbspk::acc_fold_batch(ss, ma, false));
+        else
+            TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid, false));
+        hook_mark(HK_MERGE);
     }
     TRY(read_len_to(c, sb + L_HEAD, sb + L_HEAD, L_HEAD_N, /*sync=*/false, ss));
     HIP_CHECK_ST(hipEventRecord(c->ev_tick[evi], ss));
+    hook_mark(HK_HEAD);
     // from here on a bail must rejoin the side stream first: whatever the
     // main stream runs next may recycle the buffers the merge is writing
     auto bail_joined = [&](void) {
@@ -3103,6 +3268,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         TRY(q3_plan_count(e, T.oA, T.oP, true, sb, n, T.plans, T.np, jca_np,
                           arena_ok));
     }
+    hook_mark(HK_PROBE);
     if (!arena_ok || jca_np == 0) {
         bail_joined();
         return DBSP_OK;  // fall back: next step runs the unpipelined body
@@ -3114,6 +3280,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         bail_joined();
         return DBSP_OK;
     }
+    hook_mark(HK_TAIL);
     // join: the tail readback and ev_tail follow BOTH streams' work, so
     // ev_tail — and anything enqueued on the main stream after this train —
     // is behind everything the train launched on either stream
@@ -3122,6 +3289,7 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
     // tail barrier: the commit's output-length and plan-total reads (host
     // LH_* slots) wait this event just before consuming them
     (void)hipEventRecord(c->ev_tail[evi], c->stream);
+    hook_mark(HK_JOIN);
     T.arena_base = c->arena_base;
     T.arena_off = c->arena_off;
     c->arena_base = save_base;
@@ -3149,17 +3317,8 @@ static void q3_maybe_enqueue_train(dbsp_engine *e) {
 }
 
 // commit a pipelined train: wait its event, read verdicts, insert, publish
-static inline double host_us() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
-}
-
 static dbsp_status q3_commit_train(dbsp_engine *e) {
-    static const bool prof = []() {
-        const char *v = getenv("DBSP_COMMIT_PROF");
-        return v && v[0] == '1';
-    }();
+    const bool prof = g_hook_prof;
     static int prof_n = 0;
     double t0 = prof ? host_us() : 0;
     dbsp_ctx *c = e->ctx;
@@ -3179,9 +3338,17 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
         // re-materialize the deltas from the raw flatmap outputs (arena of
         // the train's half — untouched until the next enqueue) and replay
         // the tick explicitly
+        // The train's sorts took the counters, so the raw lengths are at
+        // L_RAWN (L_RAW with DBSP_Q3_TAKE=0).  A count above the tick's
+        // event count cannot come from a flatmap that started at zero (the
+        // flatmap stored no row past the capacity either): refuse to sort
+        // it.
         DevBatch dA, dP;
-        T.rawA.n = H[L_RAW];
-        T.rawP.n = H[L_RAW + 1];
+        const int l_raw = c->q3_take ? L_RAWN : L_RAW;
+        T.rawA.n = H[l_raw];
+        T.rawP.n = H[l_raw + 1];
+        if (T.rawA.n < 0 || T.rawA.n > T.n || T.rawP.n < 0 || T.rawP.n > T.n)
+            return DBSP_ERR_INTERNAL;
         TRY(sort_consolidate_batch(c, T.rawA, dA));
         TRY(sort_consolidate_batch(c, T.rawP, dP));
         return q3_body(e, T.ev, T.n, dA, dP, DevBatch{}, DevBatch{},
@@ -3246,8 +3413,13 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     double t3 = prof ? host_us() : 0;
     if (prof && ++prof_n % 50 == 0)
         fprintf(stderr,
-                "[commit] wait %.1f verdict %.1f swap+hook(total %.1f, hook %.1f) us\n",
-                t1 - t0, t2 - t1, t3 - t2, th1 - th0);
+                "[commit] wait %.1f verdict %.1f swap+hook(total %.1f, hook %.1f) us\n"
+                "[hook] flatmap %.1f sort %.1f alloc %.1f fork %.1f merge %.1f "
+                "head %.1f probe %.1f tail %.1f join %.1f us\n",
+                t1 - t0, t2 - t1, t3 - t2, th1 - th0, g_hook_us[HK_FLATMAP],
+                g_hook_us[HK_SORT], g_hook_us[HK_ALLOC], g_hook_us[HK_FORK],
+                g_hook_us[HK_MERGE], g_hook_us[HK_HEAD], g_hook_us[HK_PROBE],
+                g_hook_us[HK_TAIL], g_hook_us[HK_JOIN]);
     // this tick's plan totals and output lengths land with the tail
     // readback, past ev_tick — wait the tail before consuming them
     (void)hipEventSynchronize(c->ev_tail[T.evi]);

@@ -1163,7 +1163,25 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_sort_cons_small(SortArgs ar
     int64_t n = args.n[batch];
     int64_t *out_len = args.d_len + batch;
     SORT_CONS_LDS
-    if (args.n_dev[batch]) {
+    if (args.n_take[batch]) {
+        // take the producer's counter: one thread reads it, records it in
+        // the readback slot and hands the counter back zeroed; the block
+        // learns the length through LDS, so no thread can read the zero
+        __shared__ int64_t s_take;
+        if (threadIdx.x == 0) {
+            const int64_t seen = *args.n_take[batch];
+            s_take = seen;
+            *args.n_seen[batch] = seen;
+            *args.n_take[batch] = 0;
+        }
+        __syncthreads();
+        const int64_t n_take = s_take;
+        if (n_take > FUSE_MAX || n_take < 0 || n_take > args.n_cap[batch]) {
+            if (threadIdx.x == 0) *out_len = -1;  // speculation lost
+            return;
+        }
+        n = n_take;
+    } else if (args.n_dev[batch]) {
         const int64_t n_chain = *args.n_dev[batch];
         if (n_chain > FUSE_MAX || n_chain < 0) {  // speculation lost
             if (threadIdx.x == 0) *out_len = -1;
@@ -2075,6 +2093,151 @@ __global__ __launch_bounds__(FUSE_THREADS, 4) void k_merge_mid_fused(
     }
 }
 
+// Accumulator fold (the in-train merge's special case): A is a consolidated
+// accumulator whose length the host knows, B a consolidated delta of at most
+// FUSE_MAX rows whose length is on the device.  With so small a B every
+// output position follows from B's lower bounds in A alone:
+//   lb[j]  = lower bound of B[j] in A (nondecreasing: B is sorted)
+//   s[j]   = +1 if B[j] matches no A row, 0 if it matches A[lb[j]] and the
+//            summed weight survives, -1 if the sum is zero
+//   S      = exclusive prefix of s, S[nb] its total
+//   A[i]   goes to i + S[J], J = #{j : lb[j] <= i}; it is B[J-1]'s partner
+//          iff lb[J-1] == i and B[J-1] matched (B's rows are distinct, so at
+//          most one does, and of a run sharing one lower bound only the last)
+//   B[j]   unmatched goes to lb[j] + S[j]
+//   length = na + S[nb]
+// Every workgroup computes lb, the flags and S for ALL of B redundantly (one
+// global binary search per row; A is cache-resident) and keeps them in LDS —
+// 4 + 4 + 1 bytes per row, 72 KiB at FUSE_MAX plus the scan's cells, so two
+// workgroups fit a CU's 160 KiB — then emits its own slice of A and the
+// unmatched B rows whose lower bound falls in it (lb == na: the last
+// workgroup).  No count pass, no scratch and no inter-workgroup traffic.
+// Stores are guarded by the output capacity na + bcap, so rows that are not
+// consolidated (a caller's error) give a wrong batch, never a stray store.
+#define FOLD_EQ 1u      // B[j] equals A[lb[j]]
+#define FOLD_CANCEL 2u  // ... and the weights sum to zero
+template <typename W>
+__global__ __launch_bounds__(FUSE_THREADS, 4) void k_acc_fold(MergeArgs args) {
+    __shared__ uint32_t s_lb[FUSE_MAX];
+    __shared__ uint32_t s_S[FUSE_MAX + 1];  // int32 sums carried mod 2^32
+    __shared__ uint8_t s_fl[FUSE_MAX];
+    __shared__ uint32_t wave_tot[FUSE_THREADS / WAVE + 1];
+    const int p = blockIdx.y;
+    const int wg = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int64_t na = args.na[p];
+    const int nwg = dbspk::acc_fold_wgs(na);
+    if (wg >= nwg) return;  // the grid is sized for the launch's longest A
+    const int64_t nb64 = args.dnb[p] ? *args.dnb[p] : args.nb[p];
+    const int64_t bcap = args.bcap[p];
+    int64_t *out_len = args.d_len + p;
+    if (na < 0 || na > ACC_FOLD_NA_MAX || nb64 < 0 || nb64 > FUSE_MAX ||
+        nb64 > bcap) {  // failed upstream speculation: poison the length
+        if (tid == 0 && wg == 0) *out_len = -1;
+        return;
+    }
+    const int nb = (int)nb64;
+    const uint64_t *ak = args.ak[p], *av = args.av[p];
+    const W *aw = (const W *)args.aw[p];
+    const uint64_t *bk = args.bk[p], *bv = args.bv[p];
+    const W *bw = (const W *)args.bw[p];
+    uint64_t *ok = args.ok[p], *ov = args.ov[p];
+    W *ow = (W *)args.ow[p];
+    const uint64_t ocap = (uint64_t)(na + bcap);
+
+    // classify all of B (strided: coalesced B reads)
+    for (int j = tid; j < nb; j += FUSE_THREADS) {
+        const uint64_t k = bk[j], v = bv[j];
+        int64_t lo = 0, hi = na;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            const uint64_t mk = ak[mid];
+            if (mk < k || (mk == k && av[mid] < v)) lo = mid + 1;
+            else hi = mid;
+        }
+        uint32_t f = 0;
+        if (lo < na && ak[lo] == k && av[lo] == v)
+            f = (aw[lo] + bw[j] == (W)0) ? (FOLD_EQ | FOLD_CANCEL) : FOLD_EQ;
+        s_lb[j] = (uint32_t)lo;
+        s_fl[j] = (uint8_t)f;
+    }
+    __syncthreads();
+    // S: consecutive items per thread, one block scan
+    {
+        const int items = (nb + FUSE_THREADS - 1) / FUSE_THREADS;  // <= 8
+        const int j0 = min(tid * items, nb), j1 = min(j0 + items, nb);
+        uint32_t sum = 0;
+        for (int j = j0; j < j1; j++) {
+            const uint32_t f = s_fl[j];
+            sum += f == 0 ? 1u : (f & FOLD_CANCEL) ? ~0u : 0u;
+        }
+        uint32_t tot;
+        uint32_t run = fuse_scan(sum, wave_tot, &tot);
+        for (int j = j0; j < j1; j++) {
+            s_S[j] = run;
+            const uint32_t f = s_fl[j];
+            run += f == 0 ? 1u : (f & FOLD_CANCEL) ? ~0u : 0u;
+        }
+        if (tid == 0) s_S[nb] = tot;
+    }
+    __syncthreads();
+
+    const int64_t per = (na + nwg - 1) / nwg;
+    const int64_t a0 = min((int64_t)wg * per, na);
+    const int64_t a1 = min(a0 + per, na);
+    // B rows whose lower bound falls in [a0, a1): [jlo, jhi)
+    int jlo, jhi;
+    {
+        int lo = 0, hi = nb;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((int64_t)s_lb[mid] < a0) lo = mid + 1; else hi = mid;
+        }
+        jlo = lo;
+        hi = nb;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((int64_t)s_lb[mid] < a1) lo = mid + 1; else hi = mid;
+        }
+        jhi = lo;
+    }
+    // the slice of A: J lies in [jlo, jhi]
+    for (int64_t i = a0 + tid; i < a1; i += FUSE_THREADS) {
+        int lo = jlo, hi = jhi;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((int64_t)s_lb[mid] <= i) lo = mid + 1; else hi = mid;
+        }
+        const int J = lo;
+        W w = aw[i];
+        bool keep = true;
+        if (J > 0 && (int64_t)s_lb[J - 1] == i && (s_fl[J - 1] & FOLD_EQ)) {
+            if (s_fl[J - 1] & FOLD_CANCEL) keep = false;
+            else w = w + bw[J - 1];
+        }
+        const uint64_t o = (uint64_t)(i + (int64_t)(int32_t)s_S[J]);
+        if (keep && o < ocap) {
+            ok[o] = ak[i];
+            ov[o] = av[i];
+            ow[o] = w;
+        }
+    }
+    // the unmatched B rows of the slice; those past the end of A (lb == na)
+    // belong to the last workgroup
+    if (wg == nwg - 1) jhi = nb;
+    for (int j = jlo + tid; j < jhi; j += FUSE_THREADS) {
+        if (s_fl[j] != 0) continue;
+        const uint64_t o =
+            (uint64_t)((int64_t)s_lb[j] + (int64_t)(int32_t)s_S[j]);
+        if (o < ocap) {
+            ok[o] = bk[j];
+            ov[o] = bv[j];
+            ow[o] = bw[j];
+        }
+    }
+    if (wg == 0 && tid == 0) *out_len = na + (int64_t)(int32_t)s_S[nb];
+}
+
 // ---------------------------------------------------------------------------
 // multi-batch spine join: the reference reads a spine through a k-way
 // CursorList (trace/cursor/cursor_list.rs); join is linear in the trace, so
@@ -2859,20 +3022,47 @@ __global__ void k_shard_scatter(const uint64_t *k, const uint64_t *v,
 // consolidate that follows sorts)
 // ---------------------------------------------------------------------------
 
-// wave-aggregated ticket append: one atomicAdd per wave per predicate
-// instead of one per matching row (the flatmap's counters were the hottest
-// atomics in the tick)
-__device__ inline uint64_t wave_append(unsigned long long *ctr, bool pred) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    const uint64_t m = __ballot(pred);
-    if (m == 0) return 0;
+// block-aggregated ticket append for both output streams at once: wave
+// ballots rank the lanes, the block's first wave scans the per-wave counts
+// and takes ONE ticket per stream per block from the global counters (none
+// for a stream without a match), and LDS hands every wave its base.  The
+// per-wave atomics this replaces serialised on the two counter words: at
+// q3's ~1 % selectivity nearly every matching row paid its own.  Every
+// thread of the block calls it (two barriers).
+#define FLATMAP_BLK 1024
+#define FLATMAP_WAVES (FLATMAP_BLK / WAVE)
+__device__ inline void block_append2(unsigned long long *c0,
+                                     unsigned long long *c1, bool p0, bool p1,
+                                     uint32_t (*s_cnt)[FLATMAP_WAVES],
+                                     unsigned long long (*s_base)[FLATMAP_WAVES],
+                                     uint64_t &pos0, uint64_t &pos1) {
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1), wid = tid / WAVE;
+    const uint64_t m0 = __ballot(p0), m1 = __ballot(p1);
+    if (lane == 0) {
+        s_cnt[0][wid] = (uint32_t)__popcll(m0);
+        s_cnt[1][wid] = (uint32_t)__popcll(m1);
+    }
+    __syncthreads();
+    if (tid < 2 * FLATMAP_WAVES) {  // one 16-lane group per stream
+        const int st = tid / FLATMAP_WAVES, w = tid % FLATMAP_WAVES;
+        const uint32_t c = s_cnt[st][w];
+        uint32_t inc = c;
+        for (int d = 1; d < FLATMAP_WAVES; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d, FLATMAP_WAVES);
+            if (w >= d) inc += up;
+        }
+        const uint32_t total = __shfl(inc, FLATMAP_WAVES - 1, FLATMAP_WAVES);
+        unsigned long long base = 0;
+        if (w == 0 && total > 0)
+            base = atomicAdd(st ? c1 : c0, (unsigned long long)total);
+        base = (unsigned long long)__shfl((long long)base, 0, FLATMAP_WAVES);
+        s_base[st][w] = base + (inc - c);
+    }
+    __syncthreads();
     const uint64_t lt = ((uint64_t)1 << lane) - 1;
-    unsigned long long base = 0;
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    if (lane == leader)
-        base = atomicAdd(ctr, (unsigned long long)__popcll(m));
-    base = (unsigned long long)__shfl((long long)base, leader, WAVE);
-    return base + (uint64_t)__popcll(m & lt);
+    pos0 = s_base[0][wid] + (uint64_t)__popcll(m0 & lt);
+    pos1 = s_base[1][wid] + (uint64_t)__popcll(m1 & lt);
 }
 
 __global__ void k_columnize(const dbsp_event *ev, int64_t n, uint64_t *kind,
@@ -2891,18 +3081,21 @@ __global__ void k_columnize(const dbsp_event *ev, int64_t n, uint64_t *kind,
     }
 }
 
-__global__ void k_flatmap(const dbsp_event *ev, dbspk::EventCols cols, int64_t n,
-                          int query,
-                          uint64_t *c0, uint64_t *k0, uint64_t *v0, int64_t *w0,
-                          uint64_t *c1, uint64_t *k1, uint64_t *v1, int64_t *w1) {
-    // wave-uniform outer loop (wb is the wave's first row) so the ballots in
-    // wave_append see every lane
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t wb = blockIdx.x * (int64_t)blockDim.x +
-                      (threadIdx.x & ~(int64_t)(WAVE - 1));
-         wb < n; wb += stride) {
-        const int64_t i = wb + lane;
+// cap0/cap1: rows of the output columns.  A ticket at or past the capacity
+// advances the counter but stores nothing, so a counter that did not start
+// at zero shows as an impossible length downstream, never as a stray store.
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, int query,
+        uint64_t *c0, uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0,
+        uint64_t *c1, uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1) {
+    __shared__ uint32_t s_cnt[2][FLATMAP_WAVES];
+    __shared__ unsigned long long s_base[2][FLATMAP_WAVES];
+    // block-uniform outer loop (base is the block's first row) so the
+    // barriers in block_append2 see every thread
+    const int64_t stride = (int64_t)gridDim.x * FLATMAP_BLK;
+    for (int64_t base = blockIdx.x * (int64_t)FLATMAP_BLK; base < n;
+         base += stride) {
+        const int64_t i = base + threadIdx.x;
         dbsp_event e{};
         const bool act = i < n;
         if (act) {
@@ -2914,93 +3107,70 @@ __global__ void k_flatmap(const dbsp_event *ev, dbspk::EventCols cols, int64_t n
                 e = ev[i];
             }
         }
+        // per query: the predicate and the row of each stream
+        bool p0 = false, p1 = false;
+        uint64_t rk0 = 0, rv0 = 0, rk1 = 0, rv1 = 0;
+        int64_t rw0 = e.w, rw1 = e.w;
         if (query == 3) {
             // q3.rs:37-49
-            const bool p0 = act && e.kind == 1 && e.f2 == 10;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                k0[pos0] = e.f1; v0[pos0] = e.f0; w0[pos0] = e.w;
-            }
-            const bool p1 = act && e.kind == 0 &&
-                            (e.f3 == 1 || e.f3 == 2 || e.f3 == 3);  // CA,ID,OR
-            const uint64_t pos1 = wave_append((unsigned long long *)c1, p1);
-            if (p1) {
-                k1[pos1] = e.f0;
-                v1[pos1] = (e.f1 << 8) | ((e.f2 & 0xF) << 4) | (e.f3 & 0xF);
-                w1[pos1] = e.w;
-            }
+            p0 = act && e.kind == 1 && e.f2 == 10;
+            rk0 = e.f1; rv0 = e.f0;
+            p1 = act && e.kind == 0 &&
+                 (e.f3 == 1 || e.f3 == 2 || e.f3 == 3);  // CA,ID,OR
+            rk1 = e.f0;
+            rv1 = (e.f1 << 8) | ((e.f2 & 0xF) << 4) | (e.f3 & 0xF);
         } else if (query == 4) {
             // q4.rs:45-56: auctions by id (validity window + category packed
             // into the val), bids by auction (dt + price packed)
-            const bool p0 = act && e.kind == 1;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                k0[pos0] = e.f0;
-                v0[pos0] = (e.f3 << 28) | (((e.f4 - e.f3) & 0xFFFFFFull) << 4) |
-                           (e.f2 & 0xFull);
-                w0[pos0] = e.w;
-            }
-            const bool p1 = act && e.kind == 2;
-            const uint64_t pos1 = wave_append((unsigned long long *)c1, p1);
-            if (p1) {
-                k1[pos1] = e.f0;
-                v1[pos1] = (e.f3 << 27) | (e.f2 & 0x7FFFFFFull);
-                w1[pos1] = e.w;
-            }
+            p0 = act && e.kind == 1;
+            rk0 = e.f0;
+            rv0 = (e.f3 << 28) | (((e.f4 - e.f3) & 0xFFFFFFull) << 4) |
+                  (e.f2 & 0xFull);
+            p1 = act && e.kind == 2;
+            rk1 = e.f0;
+            rv1 = (e.f3 << 27) | (e.f2 & 0x7FFFFFFull);
         } else if (query == 6) {
             // q6.rs:46-57: auctions by id (seller + validity window packed:
             // dt 28 bits from bit 36, duration 16 bits, seller 20 bits),
             // bids by auction as q4
-            const bool p0 = act && e.kind == 1;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                k0[pos0] = e.f0;
-                v0[pos0] = (e.f3 << 36) | (((e.f4 - e.f3) & 0xFFFFull) << 20) |
-                           (e.f1 & 0xFFFFFull);
-                w0[pos0] = e.w;
-            }
-            const bool p1 = act && e.kind == 2;
-            const uint64_t pos1 = wave_append((unsigned long long *)c1, p1);
-            if (p1) {
-                k1[pos1] = e.f0;
-                v1[pos1] = (e.f3 << 27) | (e.f2 & 0x7FFFFFFull);
-                w1[pos1] = e.w;
-            }
+            p0 = act && e.kind == 1;
+            rk0 = e.f0;
+            rv0 = (e.f3 << 36) | (((e.f4 - e.f3) & 0xFFFFull) << 20) |
+                  (e.f1 & 0xFFFFFull);
+            p1 = act && e.kind == 2;
+            rk1 = e.f0;
+            rv1 = (e.f3 << 27) | (e.f2 & 0x7FFFFFFull);
         } else if (query == 5) {
             // q5.rs:79-83: bids by time
-            const bool p0 = act && e.kind == 2;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                k0[pos0] = e.f3; v0[pos0] = e.f0; w0[pos0] = e.w;
-            }
+            p0 = act && e.kind == 2;
+            rk0 = e.f3; rv0 = e.f0;
         } else if (query == 8) {
             // q8.rs:50-60
-            const bool p0 = act && e.kind == 0;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                // (id, name) packed ORDER-PRESERVING as id*1024+name: the
-                // name dictionary is the generator's ~1000-value space
-                // (people.rs name draw), so 10 bits suffice — and the packed
-                // range stays ~2^20 per tick instead of id<<32 spanning 2^42,
-                // which halves the delta sort's digit passes
-                k0[pos0] = e.f4; v0[pos0] = (e.f0 << 10) | (e.f1 & 0x3FFull);
-                w0[pos0] = e.w;
-            }
-            const bool p1 = act && e.kind == 1;
-            const uint64_t pos1 = wave_append((unsigned long long *)c1, p1);
-            if (p1) {
-                k1[pos1] = e.f3; v1[pos1] = e.f1; w1[pos1] = e.w;
-            }
+            p0 = act && e.kind == 0;
+            // (id, name) packed ORDER-PRESERVING as id*1024+name: the
+            // name dictionary is the generator's ~1000-value space
+            // (people.rs name draw), so 10 bits suffice — and the packed
+            // range stays ~2^20 per tick instead of id<<32 spanning 2^42,
+            // which halves the delta sort's digit passes
+            rk0 = e.f4; rv0 = (e.f0 << 10) | (e.f1 & 0x3FFull);
+            p1 = act && e.kind == 1;
+            rk1 = e.f3; rv1 = e.f1;
         } else if (query == 101) {
             // bids.map_index(|b| (b.auction, (b.date_time, b.price))) with
             // the price weighed into the weight (aggregate/mod.rs:297-323):
             // the input of partitioned_rolling_aggregate_linear
-            const bool p0 = act && e.kind == 2;
-            const uint64_t pos0 = wave_append((unsigned long long *)c0, p0);
-            if (p0) {
-                k0[pos0] = e.f0; v0[pos0] = e.f3;
-                w0[pos0] = e.w * (int64_t)e.f2;
-            }
+            p0 = act && e.kind == 2;
+            rk0 = e.f0; rv0 = e.f3;
+            rw0 = e.w * (int64_t)e.f2;
+        }
+        uint64_t pos0, pos1;
+        block_append2((unsigned long long *)c0, (unsigned long long *)c1, p0,
+                      p1, s_cnt, s_base, pos0, pos1);
+        if (p0 && pos0 < (uint64_t)cap0) {
+            k0[pos0] = rk0; v0[pos0] = rv0; w0[pos0] = rw0;
+        }
+        if (p1 && pos1 < (uint64_t)cap1) {
+            k1[pos1] = rk1; v1[pos1] = rv1; w1[pos1] = rw1;
         }
     }
 }
@@ -3510,6 +3680,29 @@ dbsp_status merge_mid_batch(hipStream_t s, const MergeArgs &args,
     return DBSP_OK;
 }
 
+dbsp_status acc_fold_batch(hipStream_t s, const MergeArgs &args, bool wf64) {
+    if (args.np == 0) return DBSP_OK;
+    if (args.np < 0 || args.np > MERGE_BATCH_MAX) return DBSP_ERR_INVALID;
+    MergeArgs a = args;
+    int wgs = 1;
+    for (int i = 0; i < a.np; i++) {
+        if (a.na[i] < 0 || a.na[i] > ACC_FOLD_NA_MAX) return DBSP_ERR_INVALID;
+        if (!a.dnb[i]) {
+            if (a.nb[i] < 0 || a.nb[i] > FUSE_MAX) return DBSP_ERR_INVALID;
+            a.bcap[i] = a.nb[i];
+        } else if (a.bcap[i] < 0) {
+            return DBSP_ERR_INVALID;
+        }
+        wgs = std::max(wgs, acc_fold_wgs(a.na[i]));
+    }
+    const dim3 grid((uint32_t)wgs, (uint32_t)a.np);
+    if (wf64)
+        k_acc_fold<double><<<grid, FUSE_THREADS, 0, s>>>(a);
+    else
+        k_acc_fold<int64_t><<<grid, FUSE_THREADS, 0, s>>>(a);
+    return DBSP_OK;
+}
+
 dbsp_status join_spine_rows(hipStream_t s, const Rows &delta,
                             const TraceArgs &t, int proj, uint64_t param,
                             Rows *out) {
@@ -3991,14 +4184,15 @@ dbsp_status columnize_events(hipStream_t s, const dbsp_event *ev, int64_t n,
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
                                  const Rows &out0, const Rows &out1,
-                                 uint64_t *ctr /* 2 device slots */) {
-    HIP_CHECK(hipMemsetAsync(ctr, 0, 2 * sizeof(uint64_t), s));
+                                 uint64_t *ctr /* 2 device slots */,
+                                 bool ctr_zero) {
+    if (!ctr_zero) HIP_CHECK(hipMemsetAsync(ctr, 0, 2 * sizeof(uint64_t), s));
     EventCols c{};
     if (cols) c = *cols;
     if (n > 0)
-        k_flatmap<<<grid_for(n), BLK, 0, s>>>(ev, c, n, query, ctr, out0.k,
-                                              out0.v, out0.w, ctr + 1, out1.k,
-                                              out1.v, out1.w);
+        k_flatmap<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
+            ev, c, n, query, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1,
+            out1.k, out1.v, out1.w, out1.n);
     return DBSP_OK;
 }
 

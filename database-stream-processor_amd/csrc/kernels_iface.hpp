@@ -34,6 +34,15 @@ struct SortArgs {
     // length exceeds the fused capacity the kernel writes out_len = -1 and
     // the host re-sorts through the sized paths after its next sync.
     const int64_t *n_dev[SORT_BATCH_MAX];
+    // optional per-batch TAKE (overrides n[b] and n_dev[b]): the length is
+    // read from the producer's device counter n_take[b], which the sort block
+    // hands back ZEROED for the producer's next run; the length it saw is
+    // stored to n_seen[b] (a readback slot).  n_cap[b] is the number of input
+    // rows that may be read: a counter above it (or above the fused capacity)
+    // writes out_len = -1 and sorts nothing.
+    int64_t *n_take[SORT_BATCH_MAX];
+    int64_t *n_seen[SORT_BATCH_MAX];
+    int64_t n_cap[SORT_BATCH_MAX];
 };
 
 // batched single-workgroup merges (one pair per workgroup; each na+nb <= 32768)
@@ -52,6 +61,9 @@ struct MergeArgs {
     // tick's delta, whose consolidated length lives in a d_len slot); null =>
     // use nb.  A negative device length (failed speculation) => emit -1.
     const int64_t *dnb[MERGE_BATCH_MAX];
+    // acc_fold_batch with dnb only: rows of b that may be read; the output
+    // columns hold na + bcap rows.  A device length above it emits -1.
+    int64_t bcap[MERGE_BATCH_MAX];
     uint64_t *ok[MERGE_BATCH_MAX];
     uint64_t *ov[MERGE_BATCH_MAX];
     int64_t *ow[MERGE_BATCH_MAX];
@@ -182,11 +194,14 @@ dbsp_status columnize_events(hipStream_t s, const dbsp_event *ev, int64_t n,
                              uint64_t *kind, uint64_t *f0, uint64_t *f1,
                              uint64_t *f2, uint64_t *f3, uint64_t *f4,
                              int64_t *w);
-// out0/out1: capacity columns (n ignored); lengths land in ctr[0..1] (device)
+// out0/out1: capacity columns, n = their capacity in rows (a row whose ticket
+// is at or past it is counted but not stored); lengths land in ctr[0..1]
+// (device).  ctr_zero: the caller knows both counters hold 0 already (a
+// taking sort handed them back, see SortArgs::n_take), so no memset is queued.
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
                                  const Rows &out0, const Rows &out1,
-                                 uint64_t *ctr);
+                                 uint64_t *ctr, bool ctr_zero = false);
 
 // fixed-frame pair exchange (engine exchange fast path): both partitioned
 // streams packed into per-peer segments of fixed capacity P0/P1 rows with a
@@ -248,6 +263,24 @@ dbsp_status merge_small_batch(hipStream_t s, const MergeArgs &args, bool wf64);
 #define MERGE_MID_SCRATCH 33
 dbsp_status merge_mid_batch(hipStream_t s, const MergeArgs &args,
                             int64_t *scratch, bool wf64);
+
+// accumulator fold: a (consolidated, na known on the host) plus b (a
+// consolidated delta of at most 8192 rows whose length is read from dnb[p],
+// or nb[p] when dnb[p] is null) for up to MERGE_BATCH_MAX pairs in one launch.
+// Every workgroup classifies all of b against a and emits its own slice of a
+// with the b rows that land in it: no count pass, no scratch, nothing passes
+// between workgroups.  Lengths are left in d_len[p]; a negative or oversized
+// device length gives -1.  Pair p runs on acc_fold_wgs(na[p]) workgroups of
+// ceil(na / wgs) consecutive a rows each; b rows past the end of a go to the
+// last one.
+#define ACC_FOLD_SLICE 1024  // a workgroup's slice is at most this many rows
+#define ACC_FOLD_WGS_MAX 64  // ... until na exceeds 64 * 1024
+#define ACC_FOLD_NA_MAX ((int64_t)1 << 30)
+__host__ __device__ static inline int acc_fold_wgs(int64_t na) {
+    const int64_t g = (na + ACC_FOLD_SLICE - 1) / ACC_FOLD_SLICE;
+    return (int)(g < 1 ? 1 : g > ACC_FOLD_WGS_MAX ? ACC_FOLD_WGS_MAX : g);
+}
+dbsp_status acc_fold_batch(hipStream_t s, const MergeArgs &args, bool wf64);
 
 // the probe phase of a join over up to 3 plans (nd <= 8192 each): per-plan
 // per-row/per-batch cnts and, if asked, start positions; no scan

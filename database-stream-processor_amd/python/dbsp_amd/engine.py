@@ -68,6 +68,10 @@ def _L():
                                            ctypes.POINTER(BatchStruct), vp]
         L.dbsp_xxh3_u64.restype = u64
         L.dbsp_xxh3_u64.argtypes = [u64, u64]
+        L.dbsp_acc_fold.restype = i32
+        L.dbsp_acc_fold.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                    ctypes.POINTER(BatchStruct),
+                                    ctypes.POINTER(BatchStruct)]
         L.dbsp_sort_consolidate_f64.restype = i32
         L.dbsp_sort_consolidate_f64.argtypes = [vp, vp, vp, vp, i64,
                                                 ctypes.POINTER(BatchStruct)]
@@ -248,6 +252,25 @@ class Ctx:
         res = self.download_rows(out)
         for x in (a, b, out):
             self.free_batch(x)
+        return res
+
+    def acc_fold(self, a_rows, b_rows, b_len=None) -> np.ndarray:
+        """Fold the small delta b into the accumulator a (both consolidated).
+        b_len overrides the delta length handed to the kernel (the poison
+        test passes -1)."""
+        a = self.upload_rows(a_rows)
+        b = self.upload_rows(b_rows)
+        if b_len is not None:
+            b.len = b_len
+        out = BatchStruct()
+        try:
+            _check(self._lib.dbsp_acc_fold(self._h, ctypes.byref(a),
+                                           ctypes.byref(b),
+                                           ctypes.byref(out)), "acc_fold")
+            res = self.download_rows(out)
+        finally:
+            for x in (a, b, out):
+                self.free_batch(x)
         return res
 
     def join(self, delta_rows, trace_rows, proj, param=0) -> np.ndarray:

@@ -145,6 +145,16 @@ dbsp_status dbsp_sort_consolidate(dbsp_ctx *ctx,
 dbsp_status dbsp_merge(dbsp_ctx *ctx, const dbsp_batch *a, const dbsp_batch *b,
                        dbsp_batch *out);
 
+/* Fold a small consolidated delta (at most 8192 rows) into a consolidated
+ * accumulator: the same result as dbsp_merge(acc, delta), by the kernel the
+ * pipelined q3 tick uses for its in-train accumulator merge.  The delta's
+ * length reaches the kernel through a device length slot, verbatim, as it
+ * does there; a negative length is that path's poison and comes back as
+ * DBSP_ERR_INTERNAL with `out` untouched.  Synchronous: out->len is final on
+ * return. */
+dbsp_status dbsp_acc_fold(dbsp_ctx *ctx, const dbsp_batch *acc,
+                          const dbsp_batch *delta, dbsp_batch *out);
+
 /* Delta x trace join with projection.
  * Replaces Join::eval (operator/join.rs:436-473) and the JoinTrace::eval inner
  * loop (operator/join.rs:732-787) at root scope (Time = (), time/mod.rs:223-235).
