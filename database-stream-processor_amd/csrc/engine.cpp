@@ -776,9 +776,22 @@ static TraceArgs trace_args_of(const Spine &sp) {
 // in_sp is the input integral INCLUDING the current tick, out_sp the integral
 // of this operator's own outputs EXCLUDING it.  step() is defined below the
 // spine helpers it uses.
+//
+// agg (fixed at creation) selects the aggregator.  DBSP_ROLL_SUM: rows
+// (partition, ts, w), the value weighed into w.  DBSP_ROLL_MAX / _MIN
+// (partitioned_rolling_aggregate<TS, V, Agg>, rolling_aggregate.rs:235-321;
+// aggregate/max.rs:36-55, min.rs:38-57): rows (partition, ts << 32 | val, w),
+// one output per time holding a row of w > 0, its value the extreme val of
+// ANY non-zero weight over range_of(ts).  The output rows have the sum's
+// form, so out_sp, its retraction gather and its sweep are shared.
 struct RollingOp {
     uint64_t before = 10000, after = 0;
+    dbsp_roll_agg agg = DBSP_ROLL_SUM;
     Spine in_sp, out_sp;
+
+    bool time_hi() const { return agg != DBSP_ROLL_SUM; }  // time = v >> 32
+    // in_sp's range-gather and truncation mode (out_sp's is always 1)
+    int in_mode() const { return time_hi() ? 2 : 0; }
 
     // delta: consolidated rows (partition, ts, w), retained by the caller;
     // out: the tick's consolidated output delta (p<<32|ts, sum, +-1).
@@ -1332,7 +1345,7 @@ struct dbsp_engine {
     Spine c5_trace;   // (k, f64-bits val, +1 i64) join-side trace
     Spine c5_wint;    // f64-WEIGHTED integral of the weighed join stream
     Spine c5_out;     // aggregate output trace (k -> f64 sum bits, i64 w)
-    // query 101 state: per-auction rolling bid volume
+    // query 101 / 102 state: per-auction rolling bid volume / highest bid
     RollingOp roll;
     bool roll_stepped = false;  // rolling_init is rejected after a step
     bool roll_lateness_on = false;  // watermark-bounded state (off by default)
@@ -1384,12 +1397,14 @@ struct dbsp_engine {
 extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
                                           int query, int rank, int world) {
     if (query != 0 && query != 3 && query != 4 && query != 5 &&
-        query != 6 && query != 8 && query != 100 && query != 101)
+        query != 6 && query != 8 && query != 100 && query != 101 &&
+        query != 102)
         return DBSP_ERR_INVALID;
 
     dbsp_engine *e = new dbsp_engine();
     e->ctx = ctx;
     e->query = query;
+    if (query == 102) e->roll.agg = DBSP_ROLL_MAX;
     e->rank = rank;
     e->world = world;
     if (ctx) {
@@ -2442,8 +2457,8 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     uint64_t *rb = nullptr;
     int64_t n_gather = 0, n_affected = 0;
     int err = 0;
-    TRY(dbspk::roll_ranges(c->stream, delta, before, after, &rb, &n_gather,
-                           &n_affected, &err));
+    TRY(dbspk::roll_ranges(c->stream, delta, time_hi(), before, after, &rb,
+                           &n_gather, &n_affected, &err));
     if (err) return DBSP_ERR_INVALID;
     {
         DevBatch cpy;
@@ -2455,15 +2470,20 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     // gather + consolidate the slice of the input integral
     DevBatch raw, slice;
     TRY(dbspk::range_gather(c->stream, rb, rb + n, rb + 2 * n, n_gather,
-                            trace_args_of(in_sp), 0, 1, &raw));
+                            trace_args_of(in_sp), in_mode(), 1, &raw));
     int64_t moved = raw.n;
     TRY(sort_consolidate_batch(c, raw, slice));
     // insertions
     std::vector<DevBatch> parts;
     if (slice.n > 0) {
         DevBatch ins;
-        TRY(dbspk::roll_eval_rows(c->stream, slice, delta, before, after,
-                                  &ins));
+        if (time_hi())
+            TRY(dbspk::roll_eval_minmax_rows(c->stream, slice, delta,
+                                             agg == DBSP_ROLL_MIN, before,
+                                             after, &ins));
+        else
+            TRY(dbspk::roll_eval_rows(c->stream, slice, delta, before, after,
+                                      &ins));
         moved += ins.n;
         if (ins.n > 0) parts.push_back(ins);
     }
@@ -2504,7 +2524,7 @@ dbsp_status RollingOp::step_wm(dbsp_ctx *c, const DevBatch &delta, uint64_t x,
     if (nwm > 0 && delta.n > 0) {
         // stable, so the survivors are still a consolidated delta
         DevBatch surv;
-        TRY(truncate_batch(c, delta, 0, nwm, surv));
+        TRY(truncate_batch(c, delta, in_mode(), nwm, surv));
         dropped = delta.n - surv.n;
         const dbsp_status st = step(c, surv, out);
         free_batch(c, surv);
@@ -2525,7 +2545,8 @@ dbsp_status RollingOp::sweep(dbsp_ctx *c, int mode) {
         TraceArgs t{};  // every batch, empty ones too: outputs are per batch
         for (auto &b : sp.batches) trace_push(t, b);
         DevBatch kept[MAX_TRACE_BATCHES];
-        TRY(dbspk::truncate_spine(c->stream, t, mode, lower_bound(), kept));
+        TRY(dbspk::truncate_spine(c->stream, t, mode == 0 ? in_mode() : 1,
+                                  lower_bound(), kept));
         std::vector<DevBatch> old;
         old.swap(sp.batches);
         for (auto &b : old) free_batch(c, b);
@@ -2560,7 +2581,7 @@ struct dbsp_rolling {
 extern "C" dbsp_status dbsp_truncate_below(dbsp_ctx *c, const dbsp_batch *in,
                                            int mode, uint64_t bound,
                                            dbsp_batch *out) {
-    if (!c || !in || !out || in->len < 0 || (mode != 0 && mode != 1))
+    if (!c || !in || !out || in->len < 0 || mode < 0 || mode > 2)
         return DBSP_ERR_INVALID;
     DevBatch ib{in->k, in->v, in->w, in->len}, res;
     TRY(truncate_batch(c, ib, mode, bound, res));
@@ -2569,14 +2590,50 @@ extern "C" dbsp_status dbsp_truncate_below(dbsp_ctx *c, const dbsp_batch *in,
     return DBSP_OK;
 }
 
-extern "C" dbsp_status dbsp_rolling_create(dbsp_ctx *c, uint64_t before,
-                                           uint64_t after, dbsp_rolling **out) {
-    if (!c || !out) return DBSP_ERR_INVALID;
+static bool roll_agg_valid(dbsp_roll_agg agg) {
+    return agg == DBSP_ROLL_SUM || agg == DBSP_ROLL_MAX ||
+           agg == DBSP_ROLL_MIN;
+}
+
+extern "C" dbsp_status dbsp_rolling_create_agg(dbsp_ctx *c, dbsp_roll_agg agg,
+                                               uint64_t before, uint64_t after,
+                                               dbsp_rolling **out) {
+    if (!c || !out || !roll_agg_valid(agg)) return DBSP_ERR_INVALID;
     dbsp_rolling *r = new dbsp_rolling();
     r->ctx = c;
+    r->op.agg = agg;
     r->op.before = before;
     r->op.after = after;
     *out = r;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_rolling_create(dbsp_ctx *c, uint64_t before,
+                                           uint64_t after, dbsp_rolling **out) {
+    return dbsp_rolling_create_agg(c, DBSP_ROLL_SUM, before, after, out);
+}
+
+// Rolling Max / Min batch primitive (the radix tree with Agg::Semigroup =
+// max | min, radix_tree/updater.rs:393 leaves, rolling_aggregate.rs:487-604
+// queries): per row (partition, ts << 32 | val, w) of a consolidated batch,
+// the extreme val over that partition's rows with time in
+// [ts - before, ts + after], whatever their weight's sign.
+extern "C" dbsp_status dbsp_rolling_minmax(dbsp_ctx *c, const dbsp_batch *in,
+                                           dbsp_roll_agg agg, uint64_t before,
+                                           uint64_t after, dbsp_batch *out) {
+    if (!c || !in || !out || in->len < 0 ||
+        (agg != DBSP_ROLL_MAX && agg != DBSP_ROLL_MIN))
+        return DBSP_ERR_INVALID;
+    DevBatch res;
+    TRY(alloc_batch(c, in->len > 0 ? in->len : 1, res));
+    {
+        ScopedTimer t(c, 3, 0.0);
+        TRY(dbspk::rolling_minmax_rows(c->stream, as_batch(in),
+                                       agg == DBSP_ROLL_MIN, before, after,
+                                       res));
+    }
+    res.n = in->len;
+    put_batch(out, res);
     return DBSP_OK;
 }
 
@@ -2659,6 +2716,12 @@ extern "C" dbsp_status dbsp_rolling_destroy(dbsp_rolling *r) {
 // the flatmap weighs the price into the weight, one stream through
 // build_deltas (which also exchanges by auction on sharded ranks:
 // partitions are independent), then the operator.
+// ---- query 102: per-auction rolling highest (or lowest) bid ----
+// the same map_index into .partitioned_rolling_aggregate(Max | Min, range):
+// the flatmap keeps the price as the value, v = date_time << 32 | price, and
+// everything else is query 101's step with the operator's other aggregator.
+static bool is_rolling_query(int query) { return query == 101 || query == 102; }
+
 static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
                              int64_t n) {
     dbsp_ctx *c = e->ctx;
@@ -2676,7 +2739,9 @@ static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
         if (d.n > 0) {
             uint64_t mm[4];
             TRY(dbspk::minmax_rows(c->stream, d, mm));
-            x = mm[3] > e->roll_lateness ? mm[3] - e->roll_lateness : 0;
+            // the largest time seen: v itself, or its upper half
+            const uint64_t tmax = e->roll.time_hi() ? mm[3] >> 32 : mm[3];
+            x = tmax > e->roll_lateness ? tmax - e->roll_lateness : 0;
         }
         st = e->roll.step_wm(c, d, x, e->output);
     } else {
@@ -2689,7 +2754,8 @@ static dbsp_status q101_step(dbsp_engine *e, const dbsp_event *d_ev,
 
 extern "C" dbsp_status dbsp_engine_rolling_lateness(dbsp_engine *e,
                                                     uint64_t lateness_ms) {
-    if (!e || e->query != 101 || e->roll_stepped) return DBSP_ERR_INVALID;
+    if (!e || !is_rolling_query(e->query) || e->roll_stepped)
+        return DBSP_ERR_INVALID;
     e->roll_lateness = lateness_ms;
     e->roll_lateness_on = true;
     return DBSP_OK;
@@ -2700,7 +2766,7 @@ extern "C" dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e,
                                                  int64_t *out_rows,
                                                  int64_t *late_rows,
                                                  int64_t *sweeps) {
-    if (!e || e->query != 101) return DBSP_ERR_INVALID;
+    if (!e || !is_rolling_query(e->query)) return DBSP_ERR_INVALID;
     if (in_rows) *in_rows = e->roll.in_sp.total();
     if (out_rows) *out_rows = e->roll.out_sp.total();
     if (late_rows) *late_rows = e->roll.late_rows;
@@ -2711,9 +2777,19 @@ extern "C" dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e,
 extern "C" dbsp_status dbsp_engine_rolling_init(dbsp_engine *e,
                                                 uint64_t before_ms,
                                                 uint64_t after_ms) {
-    if (!e || e->query != 101 || e->roll_stepped) return DBSP_ERR_INVALID;
+    if (!e || !is_rolling_query(e->query) || e->roll_stepped)
+        return DBSP_ERR_INVALID;
     e->roll.before = before_ms;
     e->roll.after = after_ms;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e,
+                                               dbsp_roll_agg agg) {
+    if (!e || e->query != 102 || e->roll_stepped ||
+        (agg != DBSP_ROLL_MAX && agg != DBSP_ROLL_MIN))
+        return DBSP_ERR_INVALID;
+    e->roll.agg = agg;
     return DBSP_OK;
 }
 
@@ -4212,7 +4288,8 @@ extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
         case 6: return q6_step(e, d_ev, hi - lo);
         case 5: return q5_step(e, d_ev, hi - lo);
         case 8: return q8_step(e, d_ev, hi - lo);
-        case 101: return q101_step(e, d_ev, hi - lo);
+        case 101:
+        case 102: return q101_step(e, d_ev, hi - lo);
     }
     return DBSP_ERR_INVALID;
 }
@@ -4259,7 +4336,8 @@ extern "C" dbsp_status dbsp_engine_step(dbsp_engine *e, const dbsp_event *events
         case 6: st = q6_step(e, d_ev, n); break;
         case 5: st = q5_step(e, d_ev, n); break;
         case 8: st = q8_step(e, d_ev, n); break;
-        case 101: st = q101_step(e, d_ev, n); break;
+        case 101:
+        case 102: st = q101_step(e, d_ev, n); break;
         default: st = DBSP_ERR_INVALID;
     }
     (void)dbspk::cache_free(d_ev, c->stream);

@@ -3175,6 +3175,47 @@ __global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap(
     }
 }
 
+// Query 102's front, a kernel of its own so that k_flatmap (on q3's measured
+// path) stays as it is: bids.map_index(|b| (b.auction, (b.date_time,
+// b.price))) with the price kept as the value, v = date_time << 32 | price:
+// the input of partitioned_rolling_aggregate(Max | Min).  A date_time or
+// price that does not fit its half of v goes out under a partition >= 2^32,
+// which the operator's precondition rejects.  One stream; counter and
+// capacity as k_flatmap's stream 0 (block_append2 numbers both streams and
+// leaves the counter of one without a match alone).
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_tv(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1) {
+    __shared__ uint32_t s_cnt[2][FLATMAP_WAVES];
+    __shared__ unsigned long long s_base[2][FLATMAP_WAVES];
+    const int64_t stride = (int64_t)gridDim.x * FLATMAP_BLK;
+    for (int64_t base = blockIdx.x * (int64_t)FLATMAP_BLK; base < n;
+         base += stride) {
+        const int64_t i = base + threadIdx.x;
+        uint64_t kind = 0, auction = 0, price = 0, dt = 0;
+        int64_t w = 0;
+        if (i < n) {
+            if (cols.kind) {
+                kind = cols.kind[i]; auction = cols.f0[i]; price = cols.f2[i];
+                dt = cols.f3[i]; w = cols.w[i];
+            } else {
+                const dbsp_event e = ev[i];
+                kind = e.kind; auction = e.f0; price = e.f2; dt = e.f3;
+                w = e.w;
+            }
+        }
+        const bool p0 = i < n && kind == 2;
+        uint64_t pos0, pos1;
+        block_append2((unsigned long long *)c0, (unsigned long long *)c1, p0,
+                      false, s_cnt, s_base, pos0, pos1);
+        if (p0 && pos0 < (uint64_t)cap0) {
+            k0[pos0] = ((price | dt) >> 32) ? ~0ull : auction;
+            v0[pos0] = (dt << 32) | (price & 0xFFFFFFFFull);
+            w0[pos0] = w;
+        }
+    }
+}
+
 // generic per-row map for the small derived streams (q5/q8):
 // mode 0: (k,v) -> (v>>10, (v&0x3FF)<<32 | (k&lo32))  [q8 people_by_id map_index]
 // mode 1: (k,v) -> (v, 0)                             [q8 auctions map / q5 windowed-bids map]
@@ -4189,7 +4230,10 @@ dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
     if (!ctr_zero) HIP_CHECK(hipMemsetAsync(ctr, 0, 2 * sizeof(uint64_t), s));
     EventCols c{};
     if (cols) c = *cols;
-    if (n > 0)
+    if (n > 0 && query == 102)
+        k_flatmap_bid_tv<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
+            ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1);
+    else if (n > 0)
         k_flatmap<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
             ev, c, n, query, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1,
             out1.k, out1.v, out1.w, out1.n);
@@ -4298,36 +4342,82 @@ struct RtLevels {
     int64_t n[RT_MAX_LEVELS];
 };
 
+// The tree's semigroup (Agg::Semigroup, rolling_aggregate.rs:487-604): how
+// two nodes combine, the identity an empty range yields, and the leaf read
+// from the row array's 8-byte leaf column.  RtSum's leaves are the weights
+// (the linear aggregate); RtMax / RtMin read the value half of a row's
+// v = ts << 32 | val (the per-time Max / Min aggregate, aggregate/max.rs
+// :36-55, min.rs:38-57, folded over a run of rows by the level-0 reduce).
+// Both identities are also legal values: a query range is never empty.
+struct RtSum {
+    static __device__ __forceinline__ int64_t identity() { return 0; }
+    static __device__ __forceinline__ int64_t leaf(int64_t x) { return x; }
+    static __device__ __forceinline__ int64_t combine(int64_t a, int64_t b) {
+        return a + b;
+    }
+};
+struct RtMax {
+    static __device__ __forceinline__ int64_t identity() { return 0; }
+    static __device__ __forceinline__ int64_t leaf(int64_t x) {
+        return x & 0xFFFFFFFFll;
+    }
+    static __device__ __forceinline__ int64_t combine(int64_t a, int64_t b) {
+        return a > b ? a : b;
+    }
+};
+struct RtMin {
+    static __device__ __forceinline__ int64_t identity() {
+        return 0xFFFFFFFFll;
+    }
+    static __device__ __forceinline__ int64_t leaf(int64_t x) {
+        return x & 0xFFFFFFFFll;
+    }
+    static __device__ __forceinline__ int64_t combine(int64_t a, int64_t b) {
+        return a < b ? a : b;
+    }
+};
+
+// one 16:1 level.  LEAF: `in` is the row array's leaf column (level 0);
+// otherwise it is the level below.  Every thread walks its 16 consecutive
+// elements (the row-per-16-lanes form has not been written or measured).
+template <class A, bool LEAF>
 __global__ void k_rt_reduce(const int64_t *in, int64_t n, int64_t *out,
                             int64_t n_out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_out;
          i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t s = 0;
+        int64_t s = A::identity();
         const int64_t lo = i * RT_RADIX;
         const int64_t hi = lo + RT_RADIX < n ? lo + RT_RADIX : n;
-        for (int64_t j = lo; j < hi; j++) s += in[j];
+        for (int64_t j = lo; j < hi; j++)
+            s = A::combine(s, LEAF ? A::leaf(in[j]) : in[j]);
         out[i] = s;
     }
 }
 
-// range weight-sum over [a, b) using the tree: peel unaligned edges at each
-// level (<= 15 adds per level per side), then ascend — O(log16 n) work
+// range aggregate over the rows [a, b) using the tree: peel unaligned edges
+// at each level (<= 15 combines per level per side), then ascend —
+// O(log16 n) work.  leaf: the column the tree was built over.
+template <class A>
+__device__ inline int64_t rt_range(const int64_t *leaf, const RtLevels &t,
+                                   int64_t a, int64_t b) {
+    int64_t acc = A::identity();
+    // level 0: the leaf column through the accessor
+    while ((a % RT_RADIX) != 0 && a < b) acc = A::combine(acc, A::leaf(leaf[a++]));
+    while ((b % RT_RADIX) != 0 && a < b) acc = A::combine(acc, A::leaf(leaf[--b]));
+    int lvl = 0;
+    while (a < b) {
+        a /= RT_RADIX;
+        b /= RT_RADIX;
+        const int64_t *cur = t.lv[lvl++];
+        while ((a % RT_RADIX) != 0 && a < b) acc = A::combine(acc, cur[a++]);
+        while ((b % RT_RADIX) != 0 && a < b) acc = A::combine(acc, cur[--b]);
+    }
+    return acc;
+}
 __device__ inline int64_t rt_range_sum(const int64_t *w, int64_t nw,
                                        const RtLevels &t, int64_t a,
                                        int64_t b) {
-    int64_t sum = 0;
-    const int64_t *cur = w;
-    int lvl = -1;
-    while (a < b) {
-        while ((a % RT_RADIX) != 0 && a < b) sum += cur[a++];
-        while ((b % RT_RADIX) != 0 && a < b) sum += cur[--b];
-        if (a >= b) break;
-        a /= RT_RADIX;
-        b /= RT_RADIX;
-        lvl++;
-        cur = t.lv[lvl];
-    }
-    return sum;
+    return rt_range<RtSum>(w, t, a, b);
 }
 
 // first row of the (k, v)-sorted rows [lo, hi) with (k, v) >= (kk, vv) /
@@ -4379,17 +4469,23 @@ __global__ void k_rolling_agg(const uint64_t *k, const uint64_t *v,
     }
 }
 
-// build the radix-16 levels over the weight column w[0..n)
-// (the levels live in sc)
-static dbsp_status rt_build(Scratch &sc, const int64_t *w, int64_t n,
+// build the radix-16 levels over the leaf column leaf[0..n): the weights for
+// RtSum, the v column for RtMax / RtMin (the levels live in sc)
+template <class A>
+static dbsp_status rt_build(Scratch &sc, const int64_t *leaf, int64_t n,
                             RtLevels &t) {
     int64_t cur_n = n;
-    const int64_t *cur = w;
+    const int64_t *cur = leaf;
     while (cur_n > 1 && t.nl < RT_MAX_LEVELS) {
         const int64_t nn = (cur_n + RT_RADIX - 1) / RT_RADIX;
         int64_t *lv;
         HIP_CHECK(sc.get(&lv, nn * sizeof(int64_t) + 8));
-        k_rt_reduce<<<grid_for(nn), BLK, 0, sc.stream()>>>(cur, cur_n, lv, nn);
+        if (t.nl == 0)
+            k_rt_reduce<A, true><<<grid_for(nn), BLK, 0, sc.stream()>>>(
+                cur, cur_n, lv, nn);
+        else
+            k_rt_reduce<A, false><<<grid_for(nn), BLK, 0, sc.stream()>>>(
+                cur, cur_n, lv, nn);
         t.lv[t.nl] = lv;
         t.n[t.nl] = nn;
         cur = lv;
@@ -4404,7 +4500,7 @@ dbsp_status rolling_agg_rows(hipStream_t s, const Rows &in, uint64_t width,
     if (in.n <= 0) return DBSP_OK;
     Scratch sc(s);
     RtLevels t{};
-    TRY_K(rt_build(sc, in.w, in.n, t));
+    TRY_K(rt_build<RtSum>(sc, in.w, in.n, t));
     k_rolling_agg<<<grid_for(in.n), BLK, 0, s>>>(in.k, in.v, in.w, in.n, t,
                                                  width, out.k, out.v, out.w);
     return DBSP_OK;
@@ -4440,16 +4536,20 @@ __device__ inline uint64_t roll_hi(uint64_t ts, uint64_t above) {
 // numbers both.  The delta is (p, ts)-sorted and each list's widths are
 // uniform, so a run breaks exactly where the partition changes or this row's
 // range starts past the previous row's end.  Raises the precondition word.
+// TSH: where a row's time sits in v: 0 for rows (p, ts, w), 32 for rows
+// (p, ts << 32 | val, w), whose equal-time rows merge into one run like any
+// other overlap and whose v can raise nothing.
+template <int TSH>
 __global__ void k_roll_heads(const uint64_t *dk, const uint64_t *dv, int64_t n,
                              uint64_t before, uint64_t after, uint64_t both,
                              uint64_t *flags, unsigned long long *err) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t p = dk[i], ts = dv[i];
+        const uint64_t p = dk[i], ts = dv[i] >> TSH;
         if (p > ROLL_TMAX || ts > ROLL_TMAX) atomicOr(err, 1ull);
         uint64_t hg = 1, ha = 1;
         if (i > 0 && dk[i - 1] == p) {
-            const uint64_t tp = dv[i - 1];
+            const uint64_t tp = dv[i - 1] >> TSH;
             hg = roll_lo(ts, both) > roll_hi(tp, both);
             ha = roll_lo(ts, after) > roll_hi(tp, before);
         }
@@ -4458,6 +4558,7 @@ __global__ void k_roll_heads(const uint64_t *dk, const uint64_t *dv, int64_t n,
 }
 
 // run r of a list takes lo from its first row and hi from its last
+template <int TSH>
 __global__ void k_roll_ranges(const uint64_t *dk, const uint64_t *dv, int64_t n,
                               uint64_t before, uint64_t after, uint64_t both,
                               const uint64_t *flags, const uint64_t *fscan,
@@ -4465,7 +4566,7 @@ __global__ void k_roll_ranges(const uint64_t *dk, const uint64_t *dv, int64_t n,
                               uint64_t *ap, uint64_t *alo, uint64_t *ahi) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t p = dk[i], ts = dv[i];
+        const uint64_t p = dk[i], ts = dv[i] >> TSH;
         const uint64_t f = flags[i], sc = fscan[i];
         const uint64_t fn = i + 1 < n ? flags[i + 1] : ~0ull;
         const uint64_t hg = f & 1, ha = (f >> 32) & 1;
@@ -4482,7 +4583,9 @@ __global__ void k_roll_ranges(const uint64_t *dk, const uint64_t *dv, int64_t n,
 // range-gather count: one thread per (range, spine batch) pair, two binary
 // searches.  mode 0: rows (k, v) in [(p, lo), (p, hi)] (the input trace);
 // mode 1: rows with k in [p<<32|lo, p<<32|hi] (the output trace, whose key
-// packs partition and time).  Empty batches and ranges count 0.
+// packs partition and time); mode 2: rows (k, v) in [(p, lo<<32),
+// (p, hi<<32|0xffffffff)] (an input trace whose v packs time and value).
+// Empty batches and ranges count 0.
 __global__ void k_range_count(const uint64_t *rp, const uint64_t *rlo,
                               const uint64_t *rhi, int64_t nr, TraceArgs t,
                               int mode, uint64_t *cnt, uint64_t *start) {
@@ -4498,6 +4601,10 @@ __global__ void k_range_count(const uint64_t *rp, const uint64_t *rlo,
             if (mode == 0) {
                 lo = lex_lower(t.k[b], t.v[b], 0, n, p, lo_t);
                 hi = lex_upper(t.k[b], t.v[b], lo, n, p, hi_t);
+            } else if (mode == 2) {
+                lo = lex_lower(t.k[b], t.v[b], 0, n, p, lo_t << 32);
+                hi = lex_upper(t.k[b], t.v[b], lo, n, p,
+                               (hi_t << 32) | ROLL_TMAX);
             } else {
                 lo = lower_bound_k(t.k[b], n, (p << 32) | lo_t);
                 hi = lo + upper_bound_k(t.k[b] + lo, n - lo, (p << 32) | hi_t);
@@ -4567,9 +4674,9 @@ static inline uint64_t sat_add_u64(uint64_t a, uint64_t b) {
     return a + b < a ? UINT64_MAX : a + b;
 }
 
-dbsp_status roll_ranges(hipStream_t s, const Rows &delta, uint64_t before,
-                        uint64_t after, uint64_t **ranges, int64_t *n_gather,
-                        int64_t *n_affected, int *err) {
+dbsp_status roll_ranges(hipStream_t s, const Rows &delta, bool time_hi,
+                        uint64_t before, uint64_t after, uint64_t **ranges,
+                        int64_t *n_gather, int64_t *n_affected, int *err) {
     const uint64_t *dk = delta.k, *dv = delta.v;
     const int64_t n = delta.n;
     *ranges = nullptr;
@@ -4584,17 +4691,26 @@ dbsp_status roll_ranges(hipStream_t s, const Rows &delta, uint64_t before,
     HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
     HIP_CHECK(sc.get(&rb, 6 * n * sizeof(uint64_t)));
     HIP_CHECK(hipMemsetAsync(flags + n, 0, sizeof(uint64_t), s));
-    k_roll_heads<<<grid_for(n), BLK, 0, s>>>(dk, dv, n, before, after, both,
-                                             flags,
-                                             (unsigned long long *)(flags + n));
+    unsigned long long *d_err = (unsigned long long *)(flags + n);
+    if (time_hi)
+        k_roll_heads<32><<<grid_for(n), BLK, 0, s>>>(dk, dv, n, before, after,
+                                                     both, flags, d_err);
+    else
+        k_roll_heads<0><<<grid_for(n), BLK, 0, s>>>(dk, dv, n, before, after,
+                                                    both, flags, d_err);
     uint64_t h_err = 0, total = 0;
     HIP_CHECK(hipMemcpyAsync(&h_err, flags + n, sizeof(uint64_t),
                              hipMemcpyDeviceToHost, s));
     TRY_K(scan_exclusive(s, flags, fscan, n, &total));  // syncs: err + lengths
     if (h_err == 0) {
-        k_roll_ranges<<<grid_for(n), BLK, 0, s>>>(
-            dk, dv, n, before, after, both, flags, fscan, rb, rb + n,
-            rb + 2 * n, rb + 3 * n, rb + 4 * n, rb + 5 * n);
+        if (time_hi)
+            k_roll_ranges<32><<<grid_for(n), BLK, 0, s>>>(
+                dk, dv, n, before, after, both, flags, fscan, rb, rb + n,
+                rb + 2 * n, rb + 3 * n, rb + 4 * n, rb + 5 * n);
+        else
+            k_roll_ranges<0><<<grid_for(n), BLK, 0, s>>>(
+                dk, dv, n, before, after, both, flags, fscan, rb, rb + n,
+                rb + 2 * n, rb + 3 * n, rb + 4 * n, rb + 5 * n);
         *n_gather = (int64_t)(total & ROLL_TMAX);
         *n_affected = (int64_t)(total >> 32);
         sc.keep(rb);
@@ -4651,7 +4767,7 @@ dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
 struct TruncArgs {
     TraceArgs t;
     int64_t blk0[MAX_TRACE_BATCHES + 1];  // first tile of batch b; [nb] = all
-    int mode;        // 0: time = v; 1: time = low 32 bits of k
+    int mode;        // 0: time = v; 1: time = low 32 bits of k; 2: v >> 32
     uint64_t bound;
 };
 struct TruncOut {
@@ -4671,15 +4787,16 @@ k_trunc_count(TruncArgs a, uint64_t *counts) {
     __shared__ uint32_t wave_cnt[TRUNC_WAVES];
     const int64_t blk = blockIdx.x;
     const int b = trunc_batch_of(a, blk);
-    const uint64_t *tc = a.mode == 0 ? a.t.v[b] : a.t.k[b];
-    const uint64_t mask = a.mode == 0 ? ~0ull : ROLL_TMAX;
+    const uint64_t *tc = a.mode == 1 ? a.t.k[b] : a.t.v[b];
+    const uint64_t mask = a.mode == 1 ? ROLL_TMAX : ~0ull;
+    const int tsh = a.mode == 2 ? 32 : 0;
     const int64_t n = a.t.n[b];
     const int64_t base = (blk - a.blk0[b]) * TRUNC_TILE + threadIdx.x;
     uint32_t c = 0;  // wave-uniform
 #pragma unroll
     for (int it = 0; it < TRUNC_ITEMS; it++) {
         const int64_t i = base + it * BLK;
-        const bool keep = i < n && (tc[i] & mask) >= a.bound;
+        const bool keep = i < n && ((tc[i] & mask) >> tsh) >= a.bound;
         c += (uint32_t)__popcll(__ballot(keep));
     }
     if ((threadIdx.x & (WAVE - 1)) == 0) wave_cnt[threadIdx.x / WAVE] = c;
@@ -4706,13 +4823,14 @@ k_trunc_emit(TruncArgs a, const uint64_t *offsets, TruncOut o) {
     const uint64_t off0 = offsets[blk];
     if (offsets[blk + 1] == off0) return;  // nothing of this tile survives
     const int b = trunc_batch_of(a, blk);
-    const uint64_t *tc = a.mode == 0 ? a.t.v[b] : a.t.k[b];
-    const uint64_t *oc = a.mode == 0 ? a.t.k[b] : a.t.v[b];
-    uint64_t *otc = a.mode == 0 ? o.v[b] : o.k[b];
-    uint64_t *ooc = a.mode == 0 ? o.k[b] : o.v[b];
+    const uint64_t *tc = a.mode == 1 ? a.t.k[b] : a.t.v[b];
+    const uint64_t *oc = a.mode == 1 ? a.t.v[b] : a.t.k[b];
+    uint64_t *otc = a.mode == 1 ? o.k[b] : o.v[b];
+    uint64_t *ooc = a.mode == 1 ? o.v[b] : o.k[b];
     const int64_t *wc = a.t.w[b];
     int64_t *owc = o.w[b];
-    const uint64_t mask = a.mode == 0 ? ~0ull : ROLL_TMAX;
+    const uint64_t mask = a.mode == 1 ? ROLL_TMAX : ~0ull;
+    const int tsh = a.mode == 2 ? 32 : 0;
     const int64_t n = a.t.n[b];
     const int64_t base = (blk - a.blk0[b]) * TRUNC_TILE + threadIdx.x;
     const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
@@ -4721,7 +4839,7 @@ k_trunc_emit(TruncArgs a, const uint64_t *offsets, TruncOut o) {
     for (int it = 0; it < TRUNC_ITEMS; it++) {
         const int64_t i = base + it * BLK;
         tv[it] = i < n ? tc[i] : 0;
-        bal[it] = __ballot(i < n && (tv[it] & mask) >= a.bound);
+        bal[it] = __ballot(i < n && ((tv[it] & mask) >> tsh) >= a.bound);
         if (lane == 0)
             pre[it * TRUNC_WAVES + wid] = (uint64_t)__popcll(bal[it]);
     }
@@ -4751,7 +4869,7 @@ k_trunc_emit(TruncArgs a, const uint64_t *offsets, TruncOut o) {
 
 dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
                            uint64_t bound, Rows *out) {
-    if (t.nb < 0 || t.nb > MAX_TRACE_BATCHES || (mode != 0 && mode != 1))
+    if (t.nb < 0 || t.nb > MAX_TRACE_BATCHES || mode < 0 || mode > 2)
         return DBSP_ERR_INVALID;
     TruncArgs a{};
     a.t = t;
@@ -4819,12 +4937,160 @@ dbsp_status roll_eval_rows(hipStream_t s, const Rows &slice,
     // an inner scope: the tree levels go back ahead of flags and fscan
     Scratch lv(s);
     RtLevels t{};
-    TRY_K(rt_build(lv, slice.w, n, t));
+    TRY_K(rt_build<RtSum>(lv, slice.w, n, t));
     Rows r;
     TRY_K(alloc_rows(lv, (int64_t)total, &r));
     k_roll_emit<<<grid_for(n), BLK, 0, s>>>(slice.k, slice.v, slice.w, n, t,
                                             before, after, flags, fscan, r.k,
                                             r.v, r.w);
+    return give_rows(lv, r, out);
+}
+
+// ---------------------------------------------------------------------------
+// Rolling Max / Min (partitioned_rolling_aggregate<TS, V, Agg> with Agg = Max
+// or Min, rolling_aggregate.rs:235-321; eval at :487-604 combining nodes with
+// Agg::Semigroup).  Rows are (p, ts << 32 | val, w), so (k, v) order is
+// (p, ts, val) order and a time's rows are one run.  The aggregate of a time
+// is the extreme val over its rows of ANY non-zero weight (max.rs:36-55,
+// min.rs:38-57: the first / last value "with non-zero weight" — a
+// consolidated batch holds no other), which the RtMax / RtMin tree folds
+// over row ranges.  Every row range is two lexicographic searches over the
+// packed v: [(p, lo << 32), (p, hi << 32 | 0xffffffff)].
+// ---------------------------------------------------------------------------
+
+// batch primitive: per row i, the extreme over its partition's rows with time
+// in range_of(ts_i)
+template <class A>
+__global__ void k_rolling_minmax(const uint64_t *k, const uint64_t *v,
+                                 int64_t n, RtLevels t, uint64_t before,
+                                 uint64_t after, uint64_t *ok, uint64_t *ov,
+                                 int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = k[i], ts = v[i] >> 32;
+        const int64_t qlo = lex_lower(k, v, 0, n, p, roll_lo(ts, before) << 32);
+        const int64_t qhi = lex_upper(k, v, qlo, n, p,
+                                      (roll_hi(ts, after) << 32) | ROLL_TMAX);
+        ok[i] = p;
+        ov[i] = v[i];
+        ow[i] = rt_range<A>((const int64_t *)v, t, qlo, qhi);
+    }
+}
+
+dbsp_status rolling_minmax_rows(hipStream_t s, const Rows &in, bool is_min,
+                                uint64_t before, uint64_t after,
+                                const Rows &out) {
+    if (in.n <= 0) return DBSP_OK;
+    Scratch sc(s);
+    RtLevels t{};
+    const int64_t *leaf = (const int64_t *)in.v;
+    if (is_min) {
+        TRY_K(rt_build<RtMin>(sc, leaf, in.n, t));
+        k_rolling_minmax<RtMin><<<grid_for(in.n), BLK, 0, s>>>(
+            in.k, in.v, in.n, t, before, after, out.k, out.v, out.w);
+    } else {
+        TRY_K(rt_build<RtMax>(sc, leaf, in.n, t));
+        k_rolling_minmax<RtMax><<<grid_for(in.n), BLK, 0, s>>>(
+            in.k, in.v, in.n, t, before, after, out.k, out.v, out.w);
+    }
+    return DBSP_OK;
+}
+
+// pos[i] = 1 iff slice row i has positive weight; pos[n] = 0, so the
+// exclusive scan over n + 1 entries counts the positive rows of any row range
+__global__ void k_roll_pos(const int64_t *sw, int64_t n, uint64_t *pos) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i <= n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        pos[i] = i < n && sw[i] > 0;
+}
+
+// One flag per TIME: the head row of a (p, ts) run is flagged iff some row of
+// the run has w > 0 (the value loop breaks at the first !weight.le0(),
+// rolling_aggregate.rs:572-592, so a time emits once however many values it
+// holds) and the delta has a row of partition p with time in range_of(ts).
+// The run's end is one binary search and its positive rows one difference of
+// the prefix count, so a hot time costs its head thread O(log n) like any
+// other.
+__global__ void k_roll_mm_flags(const uint64_t *sk, const uint64_t *sv,
+                                int64_t n, const uint64_t *ppos,
+                                const uint64_t *dk, const uint64_t *dv,
+                                int64_t nd, uint64_t before, uint64_t after,
+                                uint64_t *flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t p = sk[i], ts = sv[i] >> 32;
+        uint64_t f = 0;
+        if (i == 0 || sk[i - 1] != p || (sv[i - 1] >> 32) != ts) {
+            const int64_t end =
+                lex_upper(sk, sv, i, n, p, (ts << 32) | ROLL_TMAX);
+            if (ppos[end] > ppos[i]) {
+                const int64_t j =
+                    lex_lower(dk, dv, 0, nd, p, roll_lo(ts, before) << 32);
+                f = j < nd && dk[j] == p &&
+                    (dv[j] >> 32) <= roll_hi(ts, after);
+            }
+        }
+        flags[i] = f;
+    }
+}
+
+template <class A>
+__global__ void k_roll_mm_emit(const uint64_t *sk, const uint64_t *sv,
+                               int64_t n, RtLevels t, uint64_t before,
+                               uint64_t after, const uint64_t *flags,
+                               const uint64_t *fscan, uint64_t *ok,
+                               uint64_t *ov, int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t p = sk[i], ts = sv[i] >> 32;
+        const int64_t qlo =
+            lex_lower(sk, sv, 0, n, p, roll_lo(ts, before) << 32);
+        const int64_t qhi = lex_upper(sk, sv, qlo, n, p,
+                                      (roll_hi(ts, after) << 32) | ROLL_TMAX);
+        const int64_t o = (int64_t)fscan[i];
+        ok[o] = (p << 32) | ts;
+        ov[o] = (uint64_t)rt_range<A>((const int64_t *)sv, t, qlo, qhi);
+        ow[o] = 1;
+    }
+}
+
+dbsp_status roll_eval_minmax_rows(hipStream_t s, const Rows &slice,
+                                  const Rows &delta, bool is_min,
+                                  uint64_t before, uint64_t after, Rows *out) {
+    const int64_t n = slice.n;
+    if (n <= 0 || delta.n <= 0) return no_rows(out);
+    Scratch sc(s);
+    uint64_t *ppos, *flags, *fscan;
+    HIP_CHECK(sc.get(&ppos, (n + 1) * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_roll_pos<<<grid_for(n + 1), BLK, 0, s>>>(slice.w, n, ppos);
+    TRY_K(scan_exclusive(s, ppos, ppos, n + 1, nullptr));
+    k_roll_mm_flags<<<grid_for(n), BLK, 0, s>>>(slice.k, slice.v, n, ppos,
+                                                delta.k, delta.v, delta.n,
+                                                before, after, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));
+    if (total == 0) return no_rows(out);
+    // an inner scope: the tree levels go back ahead of the flag columns
+    Scratch lv(s);
+    RtLevels t{};
+    Rows r;
+    const int64_t *leaf = (const int64_t *)slice.v;
+    if (is_min) {
+        TRY_K(rt_build<RtMin>(lv, leaf, n, t));
+        TRY_K(alloc_rows(lv, (int64_t)total, &r));
+        k_roll_mm_emit<RtMin><<<grid_for(n), BLK, 0, s>>>(
+            slice.k, slice.v, n, t, before, after, flags, fscan, r.k, r.v,
+            r.w);
+    } else {
+        TRY_K(rt_build<RtMax>(lv, leaf, n, t));
+        TRY_K(alloc_rows(lv, (int64_t)total, &r));
+        k_roll_mm_emit<RtMax><<<grid_for(n), BLK, 0, s>>>(
+            slice.k, slice.v, n, t, before, after, flags, fscan, r.k, r.v,
+            r.w);
+    }
     return give_rows(lv, r, out);
 }
 

@@ -382,21 +382,25 @@ dbsp_status rolling_agg_rows(hipStream_t s, const Rows &in, uint64_t width,
 // n_gather entries of the g columns, the affected ranges
 // (p, [ts-after, ts+before]) in the first n_affected entries of the a
 // columns.  *err = 1 (and no ranges) if a partition or time is >= 2^32.
-// One host sync.
-dbsp_status roll_ranges(hipStream_t s, const Rows &delta, uint64_t before,
-                        uint64_t after, uint64_t **ranges, int64_t *n_gather,
-                        int64_t *n_affected, int *err);
+// time_hi: the delta's rows are (p, ts << 32 | val) and the time is v >> 32
+// (rows of one (p, ts) have equal ranges and fall into one run); otherwise
+// the time is v.  One host sync.
+dbsp_status roll_ranges(hipStream_t s, const Rows &delta, bool time_hi,
+                        uint64_t before, uint64_t after, uint64_t **ranges,
+                        int64_t *n_gather, int64_t *n_affected, int *err);
 // copy the rows of every spine batch that fall in a range, weights times
 // sign.  mode 0: (k, v) in [(p, lo), (p, hi)]; mode 1: k in
-// [p<<32|lo, p<<32|hi].  Ranges must be disjoint; output is RAW (range-major,
-// batch-minor runs).
+// [p<<32|lo, p<<32|hi]; mode 2: (k, v) in [(p, lo<<32), (p, hi<<32|0xffffffff)]
+// (rows whose v packs ts << 32 | val).  Ranges must be disjoint; output is
+// RAW (range-major, batch-minor runs).
 dbsp_status range_gather(hipStream_t s, const uint64_t *rp,
                          const uint64_t *rlo, const uint64_t *rhi, int64_t nr,
                          const TraceArgs &t, int mode, int64_t sign,
                          Rows *out);
 // keep the rows of every spine batch whose time is >= bound, in order
 // (trace.rs:463-607 lower bound).  mode 0: time = v (rows (p, ts, w));
-// mode 1: time = k & 0xffffffff (rows (p<<32|ts, sum, w)).  out is a caller
+// mode 1: time = k & 0xffffffff (rows (p<<32|ts, sum, w)); mode 2: time =
+// v >> 32 (rows (p, ts<<32|val, w)).  out is a caller
 // array of t.nb entries: batch b's survivors in fresh columns (null when
 // none survive).  Stable, so a consolidated batch stays consolidated.  One
 // host sync for all lengths.
@@ -408,6 +412,25 @@ dbsp_status truncate_spine(hipStream_t s, const TraceArgs &t, int mode,
 dbsp_status roll_eval_rows(hipStream_t s, const Rows &slice,
                            const Rows &delta, uint64_t before, uint64_t after,
                            Rows *out);
+
+
+// ---- rolling Max / Min (partitioned_rolling_aggregate with Agg = Max | Min,
+// rolling_aggregate.rs:235-321; aggregate/max.rs:36-55, min.rs:38-57) over
+// rows (p, ts << 32 | val, w) ----
+// batch primitive: per row of the consolidated batch, (k, v, M) with M the
+// max (is_min: min) of val over the partition's rows with time in
+// [ts - before, ts + after], weights of either sign counting; out holds in.n
+// rows (its n is ignored)
+dbsp_status rolling_minmax_rows(hipStream_t s, const Rows &in, bool is_min,
+                                uint64_t before, uint64_t after,
+                                const Rows &out);
+// per TIME (p, ts) of the consolidated slice that holds a row of w > 0 and
+// that the delta affects (delta's weights unread): (p<<32|ts, M over
+// [ts-before, ts+after] of the slice, +1), in slice order (sorted, distinct
+// keys)
+dbsp_status roll_eval_minmax_rows(hipStream_t s, const Rows &slice,
+                                  const Rows &delta, bool is_min,
+                                  uint64_t before, uint64_t after, Rows *out);
 
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 

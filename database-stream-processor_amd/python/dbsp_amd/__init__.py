@@ -26,6 +26,8 @@ EVENT_DT = np.dtype([
 ROW_DT = np.dtype([("k", "<u8"), ("v", "<u8"), ("w", "<i8")])
 
 KIND_PERSON, KIND_AUCTION, KIND_BID = 0, 1, 2
+# dbsp_roll_agg: the rolling operator's aggregator
+ROLL_SUM, ROLL_MAX, ROLL_MIN = 0, 1, 2
 
 
 def _load(path: Path) -> ctypes.CDLL:

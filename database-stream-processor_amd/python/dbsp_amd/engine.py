@@ -9,7 +9,8 @@ import ctypes
 
 import numpy as np
 
-from . import EVENT_DT, ROW_DT, load_hip_lib
+from . import (EVENT_DT, ROLL_MAX, ROLL_MIN, ROLL_SUM, ROW_DT,
+               load_hip_lib)
 
 _lib = None
 
@@ -121,6 +122,15 @@ def _L():
                                        ctypes.POINTER(BatchStruct)]
         L.dbsp_rolling_create.restype = i32
         L.dbsp_rolling_create.argtypes = [vp, u64, u64, ctypes.POINTER(vp)]
+        L.dbsp_rolling_create_agg.restype = i32
+        L.dbsp_rolling_create_agg.argtypes = [vp, i32, u64, u64,
+                                              ctypes.POINTER(vp)]
+        L.dbsp_rolling_minmax.restype = i32
+        L.dbsp_rolling_minmax.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                          i32, u64, u64,
+                                          ctypes.POINTER(BatchStruct)]
+        L.dbsp_engine_rolling_agg.restype = i32
+        L.dbsp_engine_rolling_agg.argtypes = [vp, i32]
         L.dbsp_rolling_step.restype = i32
         L.dbsp_rolling_step.argtypes = [vp, vp, vp, vp, i64,
                                         ctypes.POINTER(BatchStruct)]
@@ -422,9 +432,27 @@ class Ctx:
             self.free_batch(x)
         return res
 
+    def rolling_minmax(self, rows, agg, before, after):
+        """Per row (partition, ts << 32 | val, w) of a consolidated batch:
+        (k, v, M) with M the "max" or "min" of val over the partition's rows
+        with time in [ts - before, ts + after]."""
+        code = roll_agg_code(agg)
+        inp = self.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_rolling_minmax(self._h, ctypes.byref(inp), code,
+                                           before, after, ctypes.byref(out))
+        if st == 0:
+            self.sync()
+        res = self.download_rows(out) if st == 0 else None
+        for x in (inp, out):
+            self.free_batch(x)
+        _check(st, "rolling_minmax")
+        return res
+
     def truncate_below(self, rows, mode, bound):
         """Rows whose time is >= bound, in order.  mode 0: time = v (rows
-        (partition, ts, w)); mode 1: time = k & 0xffffffff."""
+        (partition, ts, w)); mode 1: time = k & 0xffffffff; mode 2: time =
+        v >> 32 (rows (partition, ts << 32 | val, w))."""
         inp = self.upload_rows(rows)
         out = BatchStruct()
         st = self._lib.dbsp_truncate_below(self._h, ctypes.byref(inp), mode,
@@ -435,10 +463,10 @@ class Ctx:
         self.free_batch(out)
         return res
 
-    def rolling_create(self, before, after):
+    def rolling_create(self, before, after, agg="sum"):
         """Incremental partitioned rolling aggregate over
         [ts - before, ts + after] (see `Rolling`)."""
-        return Rolling(self, before, after)
+        return Rolling(self, before, after, agg=agg)
 
     def shard_partition(self, rows, nshards):
         inp = self.upload_rows(rows)
@@ -454,18 +482,39 @@ class Ctx:
         return res, offs
 
 
-class Rolling:
-    """Stateful incremental partitioned rolling aggregate (linear weight-sum;
-    mirror of Stream::partitioned_rolling_aggregate_linear).  Input rows are
-    (k = partition, v = ts, w) with partition, ts < 2^32; each step returns
-    the tick's consolidated output delta (partition<<32 | ts, sum, +-1)."""
+ROLL_AGGS = {"sum": ROLL_SUM, "max": ROLL_MAX, "min": ROLL_MIN}
 
-    def __init__(self, ctx: Ctx, before: int, after: int):
+
+def roll_agg_code(agg):
+    try:
+        return ROLL_AGGS[agg]
+    except KeyError:
+        raise ValueError(f"unknown rolling aggregator {agg!r}; "
+                         f"one of {sorted(ROLL_AGGS)}") from None
+
+
+class Rolling:
+    """Stateful incremental partitioned rolling aggregate.
+
+    agg="sum" (mirror of Stream::partitioned_rolling_aggregate_linear): input
+    rows are (k = partition, v = ts, w) with partition, ts < 2^32; each step
+    returns the tick's consolidated output delta (partition<<32 | ts, sum,
+    +-1).
+
+    agg="max" / "min" (Stream::partitioned_rolling_aggregate with Max / Min):
+    input rows are (k = partition, v = ts << 32 | val, w) with partition
+    < 2^32; one output (partition<<32 | ts, M, +-1) per time that holds a row
+    of positive weight, M the extreme val of any non-zero weight over the
+    range."""
+
+    def __init__(self, ctx: Ctx, before: int, after: int, agg="sum"):
         self._ctx = ctx
         self._lib = ctx._lib
+        self.agg = agg
         h = ctypes.c_void_p()
-        _check(self._lib.dbsp_rolling_create(ctx._h, before, after,
-                                             ctypes.byref(h)),
+        _check(self._lib.dbsp_rolling_create_agg(ctx._h, roll_agg_code(agg),
+                                                 before, after,
+                                                 ctypes.byref(h)),
                "rolling_create")
         self._h = h
 
@@ -567,19 +616,25 @@ class Engine:
                "c5_init")
 
     def rolling_init(self, before, after):
-        """Query 101: the rolling range [date_time - before, date_time +
+        """Query 101 / 102: the rolling range [date_time - before, date_time +
         after] in ms (defaults 10000 / 0); rejected after the first step."""
         _check(self._lib.dbsp_engine_rolling_init(self._h, before, after),
                "rolling_init")
 
+    def rolling_agg(self, agg):
+        """Query 102: "max" (the default) or "min"; rejected after the first
+        step."""
+        _check(self._lib.dbsp_engine_rolling_agg(self._h, roll_agg_code(agg)),
+               "rolling_agg")
+
     def rolling_lateness(self, ms):
-        """Query 101: bound the operator's state by the watermark
+        """Query 101 / 102: bound the operator's state by the watermark
         max(bid date_time so far) - ms; rejected after the first step."""
         _check(self._lib.dbsp_engine_rolling_lateness(self._h, ms),
                "rolling_lateness")
 
     def rolling_stats(self):
-        """Query 101: (in_rows, out_rows, late_rows, sweeps)."""
+        """Query 101 / 102: (in_rows, out_rows, late_rows, sweeps)."""
         vals = [ctypes.c_int64() for _ in range(4)]
         _check(self._lib.dbsp_engine_rolling_stats(
             self._h, *[ctypes.byref(x) for x in vals]), "rolling_stats")

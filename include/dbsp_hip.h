@@ -207,6 +207,43 @@ typedef struct dbsp_rolling dbsp_rolling;
  * input trace and the delayed output-trace feedback) */
 dbsp_status dbsp_rolling_create(dbsp_ctx *ctx, uint64_t before, uint64_t after,
                                 dbsp_rolling **out);
+/* The operator's aggregator (the Agg of partitioned_rolling_aggregate<TS, V,
+ * Agg>, rolling_aggregate.rs:235-321; its eval, :487-604, combines tree nodes
+ * with Agg::Semigroup).  DBSP_ROLL_SUM is the linear aggregator above.
+ * DBSP_ROLL_MAX / DBSP_ROLL_MIN are aggregate/max.rs:36-55 / min.rs:38-57:
+ * Input deltas are rows (k = partition, v = ts << 32 | val, w) with
+ * partition, ts, val < 2^32, so any 64-bit v is valid and (k, v) order is
+ * (partition, ts, val) order; partition >= 2^32 is DBSP_ERR_INVALID with the
+ * state unchanged.  range_of as above.
+ * A time (partition, ts) is output iff the input integral holds a row at it
+ * with w > 0 (the value loop breaks at the first !weight.le0(),
+ * rolling_aggregate.rs:572-592: once per time however many values it holds,
+ * never for a time of negative rows only).  Its value M is the max (min) of
+ * val over the partition's integral rows with time in range_of(ts) and ANY
+ * non-zero weight, negative included (Max::aggregate / Min::aggregate return
+ * the extreme value "with non-zero weight"; the tree's leaves are that
+ * aggregate per time, radix_tree/updater.rs:393).
+ * Output deltas are rows (k = partition<<32 | ts, v = M, w = +-1), the tick's
+ * change of that relation, consolidated.  Ranges that exclude the row's own
+ * time (an Option output) and arbitrary Fold aggregators are out of scope. */
+typedef enum { DBSP_ROLL_SUM = 0, DBSP_ROLL_MAX = 1, DBSP_ROLL_MIN = 2 } dbsp_roll_agg;
+/* rolling_aggregate.rs:286-359 with the aggregator chosen; fixed for the
+ * handle's life.  dbsp_rolling_step, _step_wm (time = v >> 32 for MAX / MIN:
+ * late rows, watermark and sweeps as for the sum), _stats, _compact,
+ * _wm_stats and _destroy take either kind of handle.  dbsp_rolling_create is
+ * this call with DBSP_ROLL_SUM. */
+dbsp_status dbsp_rolling_create_agg(dbsp_ctx *ctx, dbsp_roll_agg agg,
+                                    uint64_t before, uint64_t after,
+                                    dbsp_rolling **out);
+/* Radix-tree rolling Max / Min batch primitive (radix_tree/mod.rs:1-75 with
+ * Agg::Semigroup = max | min; leaves radix_tree/updater.rs:393): one output
+ * row per row (partition, ts << 32 | val, w) of a consolidated batch:
+ * (k, v, w = M as i64) with M over the partition's rows with time in
+ * [ts - before, ts + after], rows of either sign counting.  MAX or MIN only
+ * (DBSP_ERR_INVALID otherwise). */
+dbsp_status dbsp_rolling_minmax(dbsp_ctx *ctx, const dbsp_batch *in,
+                                dbsp_roll_agg agg, uint64_t before,
+                                uint64_t after, dbsp_batch *out);
 /* rolling_aggregate.rs:487-604 (eval).  k/v/w: n raw (unsorted,
  * unconsolidated) delta rows in device memory; out: the tick's consolidated
  * output delta (device arrays owned by the caller, null when empty; host
@@ -259,8 +296,9 @@ dbsp_status dbsp_rolling_wm_stats(dbsp_rolling *r, uint64_t *watermark,
  * :463-607): out = the rows of `in` whose time is >= bound, in order (so a
  * consolidated batch stays consolidated).  mode 0: time = v (rows
  * (partition, ts, w)); mode 1: time = k & 0xffffffff (rows
- * (partition<<32 | ts, sum, w)).  Device arrays in and out; out is owned by
- * the caller, null when empty. */
+ * (partition<<32 | ts, sum, w)); mode 2: time = v >> 32 (rows
+ * (partition, ts << 32 | val, w), the low half of v ignored).  Device arrays
+ * in and out; out is owned by the caller, null when empty. */
 dbsp_status dbsp_truncate_below(dbsp_ctx *ctx, const dbsp_batch *in, int mode,
                                 uint64_t bound, dbsp_batch *out);
 
@@ -370,11 +408,17 @@ typedef struct dbsp_engine dbsp_engine;
  *  bids.map_index(|b| (b.auction, (b.date_time, b.price)))
  *      .partitioned_rolling_aggregate_linear(...),
  *  operator/time_series/rolling_aggregate.rs:367-419 over the Nexmark bid
- *  stream; output rows (auction<<32 | date_time, sum of prices, +-1)). */
+ *  stream; output rows (auction<<32 | date_time, sum of prices, +-1)), or
+ * 102 (per-auction rolling highest bid: the same map_index into
+ *      .partitioned_rolling_aggregate(Max, range),
+ *  rolling_aggregate.rs:235-321; input rows (auction, date_time<<32 | price,
+ *  w), output rows (auction<<32 | date_time, highest price, +-1); a bid
+ *  whose date_time or price is >= 2^32 makes the step DBSP_ERR_INVALID with
+ *  the state unchanged). */
 dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
                                int rank, int world);
 
-/* Query 101 range: [date_time - before_ms, date_time + after_ms]
+/* Query 101 / 102 range: [date_time - before_ms, date_time + after_ms]
  * (RelRange, range.rs:93-104).  Defaults 10000 / 0.  DBSP_ERR_INVALID on
  * another query or after the engine's first step. */
 dbsp_status dbsp_engine_rolling_init(dbsp_engine *e, uint64_t before_ms,
@@ -383,11 +427,16 @@ dbsp_status dbsp_engine_rolling_init(dbsp_engine *e, uint64_t before_ms,
  * (watermark.rs:33-75) feeding partitioned_rolling_aggregate_with_watermark
  * (rolling_aggregate.rs:155-220): per tick the watermark is the largest bid
  * time seen so far, this tick's rows included, minus lateness_ms, and the
- * step is dbsp_rolling_step_wm.  Sharded ranks use their rank-local maximum
+ * step is dbsp_rolling_step_wm (query 102: the bid time is v >> 32).
+ * Sharded ranks use their rank-local maximum
  * (no collective).  Off by default; DBSP_ERR_INVALID on another query or
  * after the first step. */
 dbsp_status dbsp_engine_rolling_lateness(dbsp_engine *e, uint64_t lateness_ms);
-/* query 101 trace rows and watermark counters (Spine introspection,
+/* Query 102's aggregator (aggregate/max.rs:36-55, min.rs:38-57):
+ * DBSP_ROLL_MAX (the default) or DBSP_ROLL_MIN.  DBSP_ERR_INVALID on another
+ * query, another aggregator or after the first step. */
+dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e, dbsp_roll_agg agg);
+/* query 101 / 102 trace rows and watermark counters (Spine introspection,
  * trace/spine_fueled.rs:107-119); any out pointer may be null */
 dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e, int64_t *in_rows,
                                       int64_t *out_rows, int64_t *late_rows,

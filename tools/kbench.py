@@ -8,6 +8,7 @@ join kernels are HBM-bound, and reports achieved algorithmic GB/s against the
 Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
                        python tools/kbench.py --only rolling [--roll-rows N]
                        python tools/kbench.py --only rolling_wm
+                       python tools/kbench.py --only rolling_minmax [--roll-rows N]
 Prints one JSON line per primitive.
 """
 import argparse
@@ -341,8 +342,15 @@ def _rolling_deltas(n_per, parts, n_delta, late_frac, ticks, span, seed):
     return out
 
 
+def _with_values(ts, g, vmax=1 << 20):
+    """(partition, ts) rows -> v = ts << 32 | val, val uniform below vmax."""
+    val = torch.randint(0, vmax, ts.shape, generator=g, dtype=torch.int64,
+                        device="cuda")
+    return (ts << 32) | val
+
+
 def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
-                  ticks=12, warm=2, span=64):
+                  ticks=12, warm=2, span=64, agg="sum"):
     """Incremental partitioned rolling aggregate (dbsp_rolling_step) against
     the only route the batch primitive offers: merge the tick's delta into
     ONE consolidated integral and run dbsp_rolling_agg over all of it (the
@@ -351,8 +359,12 @@ def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
     consume the same raw deltas; `warm` leading ticks are excluded.  Times
     are host-clock around calls that end in a stream synchronise; with
     DBSP_PROFILE=1 the operator body's hipEvent time (kernel_stats class 3)
-    is reported too."""
-    from dbsp_amd.engine import Engine
+    is reported too.
+
+    agg "max" / "min": the same stream with a value column (rows
+    (partition, ts << 32 | val, w), val uniform below 2^20) through a Max /
+    Min operator, against merge + dbsp_rolling_minmax over the trace."""
+    from dbsp_amd.engine import Engine, roll_agg_code
     n_per = max(1, n_trace // parts)
     n_trace = n_per * parts
     g = torch.Generator(device="cuda").manual_seed(17)
@@ -363,10 +375,15 @@ def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
                        device="cuda")
     deltas = _rolling_deltas(n_per, parts, n_delta, late_frac, warm + ticks,
                              span, 23)
+    if agg != "sum":
+        gv = torch.Generator(device="cuda").manual_seed(29)
+        tv = _with_values(tv, gv)
+        deltas = [(k, _with_values(v, gv), w) for k, v, w in deltas]
+        torch.cuda.synchronize()
     probe = Engine(ctx, query=101)   # reads the context's hipEvent counters
 
     # ---- incremental operator ----
-    op = ctx.rolling_create(before, after)
+    op = ctx.rolling_create(before, after, agg=agg)
     out = BatchStruct()
     t0 = time.perf_counter()
     assert L.dbsp_rolling_step(op._h, tk.data_ptr(), tv.data_ptr(),
@@ -406,9 +423,14 @@ def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
         assert L.dbsp_merge(ctx._h, ctypes.byref(integral), ctypes.byref(d),
                             ctypes.byref(m)) == 0
         res = BatchStruct()
-        assert after == 0, "dbsp_rolling_agg covers [ts - width, ts] only"
-        assert L.dbsp_rolling_agg(ctx._h, ctypes.byref(m), before,
-                                  ctypes.byref(res)) == 0
+        if agg == "sum":
+            assert after == 0, "dbsp_rolling_agg covers [ts - width, ts] only"
+            assert L.dbsp_rolling_agg(ctx._h, ctypes.byref(m), before,
+                                      ctypes.byref(res)) == 0
+        else:
+            assert L.dbsp_rolling_minmax(ctx._h, ctypes.byref(m),
+                                         roll_agg_code(agg), before, after,
+                                         ctypes.byref(res)) == 0
         ctx.sync()
         dt = (time.perf_counter() - t0) * 1e3
         if i >= warm:
@@ -427,8 +449,11 @@ def bench_rolling(ctx, L, n_trace, parts, n_delta, late_frac, before, after,
         return s[len(s) // 2]
     return {
         "primitive": "dbsp_rolling_step (incremental partitioned rolling "
-                     "aggregate) vs merge + dbsp_rolling_agg over the trace",
-        "trace_rows": n_trace, "partitions": parts, "delta_rows": n_delta,
+                     "aggregate) vs merge + dbsp_rolling_agg over the trace"
+                     if agg == "sum" else
+                     f"dbsp_rolling_step on a {agg} operator vs merge + "
+                     "dbsp_rolling_minmax over the trace",
+        "agg": agg, "trace_rows": n_trace, "partitions": parts, "delta_rows": n_delta,
         "late_frac": late_frac, "before": before, "after": after,
         "ticks": ticks, "warmup_ticks": warm, "load_ms": round(load_ms, 2),
         "in_rows": stats[0], "in_batches": stats[1],
@@ -608,7 +633,7 @@ def main():
     ap.add_argument("--sort-rows", type=int, default=50_000_000)
     ap.add_argument("--only", default=None,
                     choices=["merge", "join", "sort", "incremental", "c5",
-                             "rolling", "rolling_wm"])
+                             "rolling", "rolling_wm", "rolling_minmax"])
     ap.add_argument("--wm-ticks", type=int, default=200,
                     help="rolling_wm leg: ticks of the frontier stream")
     ap.add_argument("--wm-lateness", type=int, default=1024)
@@ -644,6 +669,12 @@ def main():
         # the rolling leg runs on request only: a bare run keeps its legs
         if args.only == name or (args.only is None and name != "rolling"):
             print(json.dumps(leg()))
+    if args.only == "rolling_minmax":   # on request only: the rolling leg's
+        for agg in ("sum", "max"):      # stream through both operators
+            print(json.dumps(bench_rolling(
+                ctx, L, args.roll_rows, args.roll_parts, args.roll_delta,
+                args.roll_late, args.roll_before, args.roll_after,
+                args.roll_ticks, agg=agg)), flush=True)
     if args.only == "rolling_wm":       # on request only, as the rolling leg
         for res in bench_rolling_wm(ctx, L, args):
             print(json.dumps(res), flush=True)
