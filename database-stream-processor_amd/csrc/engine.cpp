@@ -314,6 +314,9 @@ extern "C" dbsp_status dbsp_ctx_create(dbsp_ctx **out, int device) {
     HIP_CHECK_ST(hipMalloc(&c->d_len, LEN_SLOTS * sizeof(int64_t)));
     HIP_CHECK_ST(hipMalloc(&c->d_mid, MERGE_BATCH_MAX * MERGE_MID_SCRATCH *
                                           sizeof(int64_t)));
+    // generation tags count up from 1: recycled memory must not look tagged
+    HIP_CHECK_ST(hipMemset(c->d_mid, 0, MERGE_BATCH_MAX * MERGE_MID_SCRATCH *
+                                            sizeof(int64_t)));
     c->arena_sz = (size_t)512 << 20;
     c->arena_half = c->arena_sz / 2;
     if (hipMalloc(&c->arena, c->arena_sz) != hipSuccess) {
@@ -1020,21 +1023,10 @@ extern "C" dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *c,
 
 extern "C" dbsp_status dbsp_merge_f64(dbsp_ctx *c, const dbsp_batch *a,
                                       const dbsp_batch *b, dbsp_batch *out) {
-    if (a->len + b->len <= 32768) {
-        DevBatch res;
-        TRY(alloc_batch(c, a->len + b->len, res));
-        MergeArgs ma{};
-        ma.np = 1;
-        merge_pair(ma, 0, as_batch(a), as_batch(b), res);
-        ma.d_len = c->d_len + LEN_OP;
-        TRY(dbspk::merge_small_batch(c->stream, ma, true));
-        TRY(read_len(c, LEN_OP, 1));
-        res.n = c->h_len[LEN_OP];
-        put_batch(out, res);
-        return DBSP_OK;
-    }
+    // the same three-band dispatch the C5 weighted-integral spine takes
     DevBatch res;
-    TRY(dbspk::merge_rows(c->stream, as_batch(a), as_batch(b), true, &res));
+    TRY(merge_batches(c, as_batch(a), as_batch(b), res, /*wf64=*/true));
+    TRY(dbsp_ctx_sync(c));
     put_batch(out, res);
     return DBSP_OK;
 }

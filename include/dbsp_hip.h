@@ -349,6 +349,8 @@ dbsp_status dbsp_shard_partition(dbsp_ctx *ctx, const dbsp_batch *in,
 dbsp_status dbsp_sort_consolidate_f64(dbsp_ctx *ctx, const uint64_t *k_in,
                                       const uint64_t *v_in, const double *w_in,
                                       int64_t n, dbsp_batch *out);
+/* dbsp_merge with f64 weights: the same three size bands and kernels as the
+ * C5 spine's merges; a poisoned length returns DBSP_ERR_INTERNAL. */
 dbsp_status dbsp_merge_f64(dbsp_ctx *ctx, const dbsp_batch *a,
                            const dbsp_batch *b, dbsp_batch *out);
 /* weigh (aggregate/mod.rs:297-323) with f(k, v) = f64_from_bits(v):

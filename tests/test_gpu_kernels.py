@@ -11,6 +11,7 @@ import pytest
 from dbsp_amd import ROW_DT
 from dbsp_amd import oracle
 from helpers import rows_of, zset
+from merge_patterns import dense_route
 
 pytestmark = pytest.mark.gpu
 
@@ -38,33 +39,41 @@ def _sorted_eq(a, b):
 
 def test_sort_consolidate_parity(ctx):
     rng = np.random.default_rng(1)
+    # routes (sort_consolidate_batch): n <= 8192 is the fused single-workgroup
+    # sort; above it a key box that passes merge_patterns.dense_route goes to
+    # the weight histogram; what is left takes the chunked medium path up to
+    # 65,536 rows and the radix sort beyond
     cases = [
-        _random_rows(rng, 0),
-        _random_rows(rng, 1),
-        _random_rows(rng, 40_000),
-        _random_rows(rng, 100_000, key_range=2**40, val_range=2**30),
-        _random_rows(rng, 2048),          # exactly one sort tile
-        _random_rows(rng, 2049),
-        _random_rows(rng, 65_536),        # dense-range path (small key box)
-        _random_rows(rng, 65_537),
-        _random_rows(rng, 20_000, key_range=5, val_range=200),  # q5 tick shape
-        _random_rows(rng, 40_000, key_range=2**40, val_range=2**30),  # chunked
+        _random_rows(rng, 0),             # empty: no kernel
+        _random_rows(rng, 1),             # fused
+        _random_rows(rng, 40_000),        # dense (1000 x 50 box)
+        _random_rows(rng, 100_000, key_range=2**40, val_range=2**30),  # radix
+        _random_rows(rng, 2048),          # fused: exactly one sort tile
+        _random_rows(rng, 2049),          # fused
+        _random_rows(rng, 65_536),        # dense (small key box)
+        _random_rows(rng, 65_537),        # dense
+        # q5 tick shape: dense
+        _random_rows(rng, 20_000, key_range=5, val_range=200),
+        # medium (chunked): the only case here that takes it
+        _random_rows(rng, 40_000, key_range=2**40, val_range=2**30),
     ]
-    # medium-path all-equal keys, zero-sum weights (single segment, nseg=1)
+    # all-equal keys above the fused size, zero-sum weights: a 1 x 1 box, so
+    # the dense route (one histogram cell), not the medium path
     z40 = np.zeros(40_000, dtype=ROW_DT)
     z40["k"] = 3
     z40["v"] = 4
     z40["w"] = np.where(np.arange(40_000) % 2 == 0, 1, -1)
     cases.append(z40)
-    # all-equal keys, zero-sum weights
+    # all-equal keys, zero-sum weights (fused: single segment, nseg=1)
     z = np.zeros(1000, dtype=ROW_DT)
     z["k"] = 7
     z["v"] = 9
     z["w"] = np.where(np.arange(1000) % 2 == 0, 1, -1)
     cases.append(z)
-    # bitonic fast-path band (n <= 2048): pow2 boundaries, duplicate-heavy
-    # (consolidation across thread ownership), cancel-heavy (zero-weight
-    # drop), and wide 64-bit keys (the bitonic compares full (k, v))
+    # bitonic fast-path band (n <= 2048, fused): pow2 boundaries,
+    # duplicate-heavy (consolidation across thread ownership), cancel-heavy
+    # (zero-weight drop), and wide 64-bit keys (the bitonic compares full
+    # (k, v))
     for n in (2, 3, 1023, 1024, 1025, 2047):
         cases.append(_random_rows(rng, n, key_range=2**63, val_range=2**63))
     dup = _random_rows(rng, 1500, key_range=40, val_range=3)
@@ -101,6 +110,104 @@ def test_sort_consolidate_big_path_all_cancel(ctx):
     got = ctx.sort_consolidate(rows1)
     assert np.array_equal(got, one)
     assert np.array_equal(got, oracle.consolidate(rows1))
+
+
+FAR_KEY = 1 << 44  # one such key makes the box too wide for the dense route
+
+
+def _distinct_rows(rng, n, far=True):
+    """n rows with distinct keys in random order, so every 8192-row chunk
+    keeps its length and the chunks interleave when merged."""
+    out = np.empty(n, dtype=ROW_DT)
+    out["k"] = 1000 + 3 * rng.permutation(n)
+    out["v"] = rng.integers(0, 50, n)
+    out["w"] = rng.choice([-3, -2, -1, 1, 2, 3], n)
+    if far:
+        out["k"][-1] = FAR_KEY
+    return out
+
+
+def _pool_chunk(rng, pool, signed):
+    """8192 rows over the 1000 distinct (k, v) of pool."""
+    out = pool[rng.integers(0, len(pool), 8192)]
+    out["w"] = (rng.choice([-2, -1, 1, 2], 8192) if signed
+                else rng.integers(1, 4, 8192))
+    return out
+
+
+def _self_cancelling_chunk(rng, lo):
+    """8192 rows: 4096 distinct pairs, each with +w and -w, shuffled."""
+    half = _distinct_rows(rng, 4096, far=False)
+    half["k"] += lo
+    neg = half.copy()
+    neg["w"] = -neg["w"]
+    return rng.permutation(np.concatenate([half, neg]))
+
+
+def _medium_cases():
+    """(name, rows, consolidated chunk lengths) for sort_medium: it sorts
+    consecutive 8192-row chunks on chip, then merges them pairwise in rounds,
+    pairs of at most 4096 rows in one k_merge_small launch and pairs of at
+    most 32768 in one k_merge_mid_fused launch (up to MERGE_BATCH_MAX = 4
+    pairs each), anything larger through the merge-path."""
+    rng = np.random.default_rng(12)
+    cases = [
+        # chunks 8192 + 1: one mid pair
+        ("8193", _distinct_rows(rng, 8193), [8192, 1]),
+        # three chunks: a mid pair and an odd carry, then (16384, 1)
+        ("16385", _distinct_rows(rng, 16385), [8192, 8192, 1]),
+        # eight chunks: four mid pairs in one launch, then two pairs of
+        # 32768 rows, then the merge-path
+        ("65536", _distinct_rows(rng, 65536), [8192] * 8),
+    ]
+    pool = _distinct_rows(rng, 16384, far=False)[:1000]
+    pool["k"] += 1  # no pair of the pool is a row of the distinct half
+    small = np.concatenate([_pool_chunk(rng, pool, False),
+                            _pool_chunk(rng, pool, True)])
+    dist = _distinct_rows(rng, 16384)
+    n0 = len(oracle.consolidate(small[:8192]))
+    n1 = len(oracle.consolidate(small[8192:]))
+    # one round with a small and a mid pair: slots [0, 1], and [1, 0] when
+    # the mid pair comes first
+    cases.append(("small+mid", np.concatenate([small, dist]),
+                  [n0, n1, 8192, 8192]))
+    cases.append(("mid+small", np.concatenate([dist, small]),
+                  [8192, 8192, n0, n1]))
+    # chunks 0 and 1 cancel inside themselves: a (0, 0) pair next to a mid one
+    gone = np.concatenate([_self_cancelling_chunk(rng, 0),
+                           _self_cancelling_chunk(rng, 1)])
+    cases.append(("cancelled chunks", np.concatenate([gone, dist]),
+                  [0, 0, 8192, 8192]))
+    # half of chunk 2 is cancelled by rows of chunk 3: in the mid merge, not
+    # in the sort
+    d = _distinct_rows(rng, 8192 + 4096)
+    neg = d[rng.permutation(8192)[:4096]].copy()
+    neg["w"] = -neg["w"]
+    c3 = rng.permutation(np.concatenate([neg, d[8192:]]))
+    cases.append(("cancelled in merge", np.concatenate([gone, d[:8192], c3]),
+                  [0, 0, 8192, 8192]))
+    return cases
+
+
+def test_sort_consolidate_medium_path(ctx):
+    """The chunked medium path at the shapes of its merge rounds: a lone
+    mid pair, an odd carry, a full launch of four pairs, a round that mixes
+    the two kernels in either slot order, empty chunks, and cancellation
+    left to the merge."""
+    for name, rows, lens in _medium_cases():
+        n = len(rows)
+        assert not dense_route(rows), name
+        assert 8192 < n <= 65536, name
+        chunks = [rows[i:i + 8192] for i in range(0, n, 8192)]
+        assert [len(oracle.consolidate(c)) for c in chunks] == lens, name
+        if name in ("small+mid", "mid+small"):
+            small = sorted(lens)[:2]
+            assert 0 < small[0] and sum(small) <= 4096, name
+        exp = oracle.consolidate(rows)
+        if name == "cancelled in merge":
+            assert len(exp) == 8192
+        got = ctx.sort_consolidate(rows)
+        assert np.array_equal(got, exp), f"{name}: {len(got)} vs {len(exp)}"
 
 
 def test_merge_parity(ctx):
