@@ -97,7 +97,7 @@ enum : int {
     L_EMIT_FLAG = 4,     // join tail: nonzero = capacity overflow
     L_DENSE = 5,         // q5: chained dense-sort length of the bid delta
     L_FINAL = 6,         // output (final) sort length
-    L_WIN = 7,           // single-spine window total (q5, window_vs_spine)
+    L_WIN = 7,           // single-spine window total (q5, dbsp_window)
     L_RAW = 8,           // 8/9: flatmap raw lengths of streams A/B: the
                          // flatmap's ticket counters.  A taking delta sort
                          // (q3's train) hands them back zeroed and leaves
@@ -951,20 +951,6 @@ extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
     DevBatch res;
     TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_MAX, delta_keys, nd,
                                as_batch(in_trace), as_batch(out_trace), &res));
-    put_batch(out, res);
-    return DBSP_OK;
-}
-
-extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
-                                   const dbsp_batch *batch, int have_prev,
-                                   uint64_t s0, uint64_t e0, uint64_t s1,
-                                   uint64_t e1, dbsp_batch *out) {
-    DevBatch res;
-    {
-        ScopedTimer t(c, 4, 0.0);
-        TRY(dbspk::window_rows(c->stream, as_batch(trace), as_batch(batch),
-                               have_prev, s0, e0, s1, e1, &res));
-    }
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -1995,81 +1981,91 @@ static dbsp_status finalize_raw(dbsp_ctx *c, std::vector<DevBatch> &outs,
     return sort_consolidate_batch(c, cat, out);
 }
 
-// last key of a consolidated batch (watermark: fast_forward_keys,
-// watermark.rs:38-45)
-static dbsp_status last_key(dbsp_ctx *c, const DevBatch &b, uint64_t *out,
-                            bool *has) {
-    if (b.n == 0) {
-        *has = false;
-        return DBSP_OK;
-    }
-    TRY(dbsp_d2h(c, out, b.k + (b.n - 1), 8));
-    *has = true;
-    return DBSP_OK;
-}
-
-// One spine's window launch plan: the spine (capped to MAX_TRACE_BATCHES) as
-// a kernel argument, and the region table the ranges kernel fills — three
-// regions per spine batch plus the tick batch, 5 int64 each — carved from
-// the arena (null when it is exhausted).
-struct WindowPlan {
-    TraceArgs ta;
+// ---- window stage (window.rs:144-220) ----
+// One leg: a spine windowed against the tick's consolidated delta.  The
+// ranges launch reads the bounds the device watermark published and fills
+// the region table — three regions per spine batch plus the tick batch, 5
+// int64 each — leaving the row total in a d_len slot; the emit copies the
+// rows once the caller's sync has brought that total to the host.
+struct WindowLeg {
+    Spine *trace;           // excludes this tick
+    const DevBatch *delta;  // sorted; its n is read only when n_dev is null
+    const int64_t *n_dev;   // the delta's device length, or null
+    int slot;               // d_len slot of tick base 0 that gets the total
+    // filled by window_launch
+    TraceArgs ta{};
     int nreg = 0;
     int64_t *table = nullptr;
+    bool table_cached = false;  // arena exhausted: freed after the emit
 };
-static dbsp_status window_plan(dbsp_ctx *c, Spine &sp, WindowPlan &wp) {
-    TRY(sp.cap_batches(c));
-    wp.ta = trace_args_of(sp);
-    wp.nreg = 3 * wp.ta.nb + 1;
-    wp.table = (int64_t *)arena_alloc(c, (size_t)wp.nreg * 5 * 8 + 8);
-    return DBSP_OK;
-}
-// emit a planned window's `total` rows (ranges already in the table) into a
-// transient batch appended to raw
-static dbsp_status window_emit(dbsp_ctx *c, const WindowPlan &wp,
-                               int64_t total, const DevBatch &batch,
-                               std::vector<DevBatch> &raw) {
-    if (total <= 0) return DBSP_OK;
-    DevBatch o;
-    TRY(alloc_batch(c, total, o, true));
-    TRY(dbspk::window_emit_multi(c->stream, wp.ta, batch, wp.table, wp.nreg,
-                                 total, o));
-    raw.push_back(o);
+
+// plan each leg (once: a second launch, after a re-sort, reuses the spine
+// arguments and the table) and launch its ranges behind the published bounds
+static dbsp_status window_launch(dbsp_engine *e, WindowLeg *legs, int n) {
+    dbsp_ctx *c = e->ctx;
+    for (WindowLeg *w = legs; w < legs + n; w++) {
+        if (w->table) continue;
+        TRY(w->trace->cap_batches(c));
+        w->ta = trace_args_of(*w->trace);
+        w->nreg = 3 * w->ta.nb + 1;
+        const size_t bytes = (size_t)w->nreg * 5 * 8 + 8;
+        w->table = (int64_t *)arena_alloc(c, bytes);
+        w->table_cached = !w->table;
+        if (w->table_cached)
+            HIP_CHECK_ST(dbspk::cache_malloc((void **)&w->table, bytes,
+                                             c->stream));
+    }
+    ScopedTimer t(c, 4, 0.0);
+    for (WindowLeg *w = legs; w < legs + n; w++)
+        TRY(dbspk::window_ranges_chain(c->stream, w->ta, w->delta->k,
+                                       w->delta->n, w->n_dev, e->d_bounds,
+                                       w->table, c->d_len + w->slot));
     return DBSP_OK;
 }
 
-// window over a spine: one ranges launch covers every spine batch's three
-// regions plus the tick-batch region, one emit launch copies them all
-static dbsp_status window_vs_spine(dbsp_ctx *c, Spine &trace,
-                                   const DevBatch &batch, bool have_prev,
-                                   uint64_t s0, uint64_t e0, uint64_t s1,
-                                   uint64_t e1, std::vector<DevBatch> &outs) {
-    ScopedTimer t(c, 4, 0.0);
-    WindowPlan wp;
-    TRY(window_plan(c, trace, wp));
-    DevBatch tmp_table;
-    if (!wp.table) {
-        // fallback scratch: the ranges kernel writes 5 int64 per region + 8
-        // bytes through .k, and alloc_batch's k column is n*8+8 bytes
-        TRY(alloc_batch(c, wp.nreg * 5, tmp_table));
-        wp.table = (int64_t *)tmp_table.k;
+// emit a launched leg's rows (none for a total of 0 or the -1 of a lost
+// speculation) into a batch appended to raw
+static dbsp_status window_emit(dbsp_ctx *c, WindowLeg &w,
+                               std::vector<DevBatch> &raw,
+                               bool transient = true) {
+    const int64_t total = c->h_len[w.slot];
+    if (total > 0) {
+        DevBatch o;
+        TRY(alloc_batch(c, total, o, transient));
+        TRY(dbspk::window_emit_multi(c->stream, w.ta, *w.delta, w.table,
+                                     w.nreg, total, o));
+        raw.push_back(o);
     }
-    TRY(dbspk::window_ranges_multi(c->stream, wp.ta, batch.k, batch.n,
-                                   have_prev ? 1 : 0, s0, e0, s1, e1, wp.table,
-                                   c->d_len + L_WIN));
-    TRY(read_len(c, L_WIN, 1));
-    TRY(window_emit(c, wp, c->h_len[L_WIN], batch, outs));
-    if (tmp_table.k) free_batch(c, tmp_table);
+    if (w.table_cached) HIP_CHECK_ST(dbspk::cache_free(w.table, c->stream));
+    w.table = nullptr;
     return DBSP_OK;
 }
-// the same with the bounds the device watermark published (the no-arena
-// fallback of the chained ticks; e->h_bounds was just read back)
-static dbsp_status window_vs_spine_bounds(dbsp_ctx *c, Spine &trace,
-                                          const DevBatch &batch,
-                                          const unsigned long long *hb,
-                                          std::vector<DevBatch> &outs) {
-    return window_vs_spine(c, trace, batch, hb[4] != 0, hb[0], hb[1], hb[2],
-                           hb[3], outs);
+
+// the operator on its own: the trace is one batch and the bounds come from
+// the caller, so the regions come out in the order retract, shrink, insert,
+// tick batch
+extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
+                                   const dbsp_batch *batch, int have_prev,
+                                   uint64_t s0, uint64_t e0, uint64_t s1,
+                                   uint64_t e1, dbsp_batch *out) {
+    const DevBatch b = as_batch(batch);
+    WindowLeg w{nullptr, &b, nullptr, L_WIN};
+    w.ta = trace_args_one(as_batch(trace));
+    w.nreg = 3 * w.ta.nb + 1;
+    w.table_cached = true;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&w.table,
+                                     (size_t)w.nreg * 5 * 8 + 8, c->stream));
+    std::vector<DevBatch> res;
+    {
+        ScopedTimer t(c, 4, 0.0);
+        TRY(dbspk::window_ranges_multi(c->stream, w.ta, b.k, b.n, have_prev,
+                                       s0, e0, s1, e1, w.table,
+                                       c->d_len + w.slot));
+        TRY(read_len(c, w.slot, 1));
+        TRY(window_emit(c, w, res, /*transient=*/false));
+    }
+    put_batch(out, res.empty() ? DevBatch{} : res[0]);
+    return DBSP_OK;
 }
 
 // map + sort/consolidate (copies; input retained)
@@ -3564,38 +3560,41 @@ static dbsp_status enqueue_front(dbsp_engine *e, Build build) {
     return st;
 }
 
-// readback of the bounds the device watermark published
+// readback (with sync) of the bounds the device watermark published
 // {s0, e0, s1, e1, have_prev, err}
-static dbsp_status read_bounds(dbsp_engine *e, bool sync) {
+static dbsp_status read_bounds(dbsp_engine *e) {
     HIP_CHECK_ST(hipMemcpyAsync(e->h_bounds, e->d_bounds, 6 * sizeof(uint64_t),
                                 hipMemcpyDeviceToHost, e->ctx->stream));
-    if (sync) HIP_CHECK_ST(hipStreamSynchronize(e->ctx->stream));
+    HIP_CHECK_ST(hipStreamSynchronize(e->ctx->stream));
     return DBSP_OK;
 }
 
-// Explicit-path watermark (sharded exchange / chain fallback): the tick's
-// local max event time — the last key of the time-keyed delta d — reduces
-// across ranks ON THE STREAM (q8.rs:63-65 as an RCCL allreduce feeding
-// k_wm_update_g) and the bounds are published device-side into the same
-// state words the chained path uses, so flipping between the modes never
-// desyncs the watermark.
-static dbsp_status wm_update_global(dbsp_engine *e, const DevBatch &d,
-                                    uint64_t width, uint64_t tumble,
-                                    uint64_t lag) {
+// The tick's one watermark update (q5.rs:85-90 / q8.rs:63-65): the max event
+// time is the last key of the time-keyed delta d, whose length is d.n or, when
+// n_dev is given, still on the device.  Sharded ranks (host lengths only)
+// reduce it across ranks ON THE STREAM first, an RCCL allreduce feeding the
+// same kernel, so every mode advances the same state words in e->d_wm and
+// flipping between them never desyncs the watermark.
+static dbsp_status wm_update(dbsp_engine *e, const DevBatch &d,
+                             const int64_t *n_dev, uint64_t width,
+                             uint64_t tumble, uint64_t lag) {
     dbsp_ctx *c = e->ctx;
-    unsigned long long *gslot = e->d_wm + 10;
-    if (d.n > 0) {
-        HIP_CHECK_ST(hipMemcpyAsync(gslot, d.k + d.n - 1, sizeof(uint64_t),
-                                    hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        HIP_CHECK_ST(hipMemsetAsync(gslot, 0, sizeof(uint64_t), c->stream));
+    WmSource src{d.k, d.n, n_dev, nullptr};
+    if (sharding_on(c)) {
+        unsigned long long *gslot = e->d_wm + 10;
+        if (d.n > 0) {
+            HIP_CHECK_ST(hipMemcpyAsync(gslot, d.k + d.n - 1, sizeof(uint64_t),
+                                        hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            HIP_CHECK_ST(hipMemsetAsync(gslot, 0, sizeof(uint64_t), c->stream));
+        }
+        if (ncclAllReduce(gslot, gslot, 1, ncclUint64, ncclMax, c->comm,
+                          c->stream) != ncclSuccess)
+            return DBSP_ERR_INTERNAL;
+        src.gmax_dev = gslot;
     }
-    if (sharding_on(c) &&
-        ncclAllReduce(gslot, gslot, 1, ncclUint64, ncclMax, c->comm,
-                      c->stream) != ncclSuccess)
-        return DBSP_ERR_INTERNAL;
-    return dbspk::wm_update_g(c->stream, gslot, width, tumble, lag, e->d_wm,
-                              e->d_bounds);
+    return dbspk::wm_update(c->stream, src, width, tumble, lag, e->d_wm,
+                            e->d_bounds);
 }
 
 // ---- q8 tick (queries/q8.rs:48-93) ----
@@ -3605,15 +3604,14 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     const int64_t *H = c->h_len + LEN_BASE0;
     // Single-rank ticks chain flatmap -> sorts -> device watermark -> window
     // ranges with ONE sync; the watermark lives in e->d_wm so the bounds
-    // never round-trip to the host on the fast path.  Sharded ranks keep the
-    // explicit path (the watermark allreduce and exchange need host values).
+    // never round-trip to the host.  Sharded ranks build their deltas
+    // explicitly (the exchange needs host lengths) and run the same stage.
     const bool use_front = take_front(e, d_ev, n);
-    const bool chain = use_front ||
-                       (!sharding_on(c) && e->d_wm && n <= 131072 &&
-                        e->spec_fail < 3);
+    const bool chain = use_front || (!sharding_on(c) && n <= 131072 &&
+                                     e->spec_fail < 3);
     DevBatch dPT, dAT, rawP, rawA;
-    std::vector<DevBatch> wp_raw, wa_raw;
-    WindowPlan wpP, wpA;
+    WindowLeg legs[2] = {{&e->pt_int, &dPT, nullptr, L_WIN2},
+                         {&e->at_int, &dAT, nullptr, L_WIN2 + 1}};
     if (chain) {
         if (use_front) {
             rawP = e->front.rawA;
@@ -3623,37 +3621,26 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         } else {
             TRY(build_deltas_chain(e, d_ev, n, rawP, rawA, dPT, dAT));
         }
-        TRY(dbspk::wm_update(c->stream, dAT.k, c->d_len + L_DELTA + 1,
-                             TUMBLE_MS, TUMBLE_MS, TUMBLE_MS, e->d_wm,
-                             e->d_bounds));
-        TRY(window_plan(c, e->pt_int, wpP));
-        TRY(window_plan(c, e->at_int, wpA));
-        const bool launched = wpP.table && wpA.table;
-        if (launched) {
-            ScopedTimer t(c, 4, 0.0);
-            TRY(dbspk::window_ranges_chain(c->stream, wpP.ta, dPT.k, 0,
-                                           c->d_len + L_DELTA, e->d_bounds,
-                                           wpP.table, c->d_len + L_WIN2));
-            TRY(dbspk::window_ranges_chain(c->stream, wpA.ta, dAT.k, 0,
-                                           c->d_len + L_DELTA + 1, e->d_bounds,
-                                           wpA.table, c->d_len + L_WIN2 + 1));
-        }
+        legs[0].n_dev = c->d_len + L_DELTA;
+        legs[1].n_dev = c->d_len + L_DELTA + 1;
+        TRY(wm_update(e, dAT, legs[1].n_dev, TUMBLE_MS, TUMBLE_MS, TUMBLE_MS));
+        TRY(window_launch(e, legs, 2));
         TRY(read_len(c, LEN_BASE0, LEN_TICK, /*sync=*/false));
-        TRY(read_bounds(e, /*sync=*/true));
-        const bool lost = !launched || e->h_bounds[5] != 0 ||
-                          H[L_DELTA] < 0 || H[L_DELTA + 1] < 0 ||
-                          H[L_WIN2] < 0 || H[L_WIN2 + 1] < 0;
+        TRY(read_bounds(e));
+        const bool lost = e->h_bounds[5] != 0 || H[L_DELTA] < 0 ||
+                          H[L_DELTA + 1] < 0 || H[L_WIN2] < 0 ||
+                          H[L_WIN2 + 1] < 0;
         if (!lost) {
             dPT.n = H[L_DELTA];
             dAT.n = H[L_DELTA + 1];
-            TRY(window_emit(c, wpP, H[L_WIN2], dPT, wp_raw));
-            TRY(window_emit(c, wpA, H[L_WIN2 + 1], dAT, wa_raw));
             e->spec_fail = 0;
         } else {
             e->spec_fail++;
-            // speculation lost (delta overflowed the fused sort, or no arena
-            // for the tables): re-sort with real lengths, pull the watermark
-            // state to the host, run the explicit window path, write back
+            // speculation lost (a delta overflowed the fused sort): re-sort
+            // with the real lengths and launch the ranges again.  The
+            // watermark stood still only if the auction delta was the one
+            // that overflowed (err); otherwise its update has happened and
+            // the published bounds are this tick's.
             rawP.n = H[L_RAW];
             rawA.n = H[L_RAW + 1];
             free_batch(c, dPT);
@@ -3662,56 +3649,22 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
             TRY(sort_consolidate_batch(c, rawA, dAT));
             rawP = DevBatch{};
             rawA = DevBatch{};
-            unsigned long long hw[4];
-            HIP_CHECK_ST(hipMemcpyAsync(hw, e->d_wm, sizeof(hw),
-                                        hipMemcpyDeviceToHost, c->stream));
-            HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-            uint64_t wm = hw[0];
-            uint64_t lk = 0;
-            bool has = false;
-            TRY(last_key(c, dAT, &lk, &has));
-            if (has && lk > 0) wm = std::max(wm, lk - TUMBLE_MS);
-            uint64_t rounded = wm - wm % TUMBLE_MS;
-            uint64_t s1 = rounded >= TUMBLE_MS ? rounded - TUMBLE_MS : 0;
-            uint64_t e1 = rounded;
-            TRY(window_vs_spine(c, e->pt_int, dPT, hw[3] != 0, hw[1], hw[2],
-                                s1, e1, wp_raw));
-            TRY(window_vs_spine(c, e->at_int, dAT, hw[3] != 0, hw[1], hw[2],
-                                s1, e1, wa_raw));
-            hw[0] = wm;
-            hw[1] = s1;
-            hw[2] = e1;
-            hw[3] = 1;
-            HIP_CHECK_ST(hipMemcpyAsync(e->d_wm, hw, sizeof(hw),
-                                        hipMemcpyHostToDevice, c->stream));
+            legs[0].n_dev = legs[1].n_dev = nullptr;
+            if (e->h_bounds[5] != 0)
+                TRY(wm_update(e, dAT, nullptr, TUMBLE_MS, TUMBLE_MS,
+                              TUMBLE_MS));
+            TRY(window_launch(e, legs, 2));
+            TRY(read_len(c, L_WIN2, 2));
         }
     } else {
-        // explicit deltas, but the watermark and windows stay device-side
-        // and the ranges chain behind the watermark
         TRY(build_deltas(e, d_ev, n, dPT, dAT, true));
-        TRY(wm_update_global(e, dAT, TUMBLE_MS, TUMBLE_MS, TUMBLE_MS));
-        TRY(window_plan(c, e->pt_int, wpP));
-        TRY(window_plan(c, e->at_int, wpA));
-        if (wpP.table && wpA.table) {
-            {
-                ScopedTimer t(c, 4, 0.0);
-                TRY(dbspk::window_ranges_chain(c->stream, wpP.ta, dPT.k, dPT.n,
-                                               nullptr, e->d_bounds, wpP.table,
-                                               c->d_len + L_WIN2));
-                TRY(dbspk::window_ranges_chain(c->stream, wpA.ta, dAT.k, dAT.n,
-                                               nullptr, e->d_bounds, wpA.table,
-                                               c->d_len + L_WIN2 + 1));
-            }
-            TRY(read_len(c, LEN_BASE0, LEN_TICK));
-            TRY(window_emit(c, wpP, H[L_WIN2], dPT, wp_raw));
-            TRY(window_emit(c, wpA, H[L_WIN2 + 1], dAT, wa_raw));
-        } else {
-            // no arena: read the published bounds and run the generic path
-            TRY(read_bounds(e, /*sync=*/true));
-            TRY(window_vs_spine_bounds(c, e->pt_int, dPT, e->h_bounds, wp_raw));
-            TRY(window_vs_spine_bounds(c, e->at_int, dAT, e->h_bounds, wa_raw));
-        }
+        TRY(wm_update(e, dAT, nullptr, TUMBLE_MS, TUMBLE_MS, TUMBLE_MS));
+        TRY(window_launch(e, legs, 2));
+        TRY(read_len(c, LEN_BASE0, LEN_TICK));
     }
+    std::vector<DevBatch> wp_raw, wa_raw;
+    TRY(window_emit(c, legs[0], wp_raw));
+    TRY(window_emit(c, legs[1], wa_raw));
     if (sharding_on(c)) {
         TRY(spines_insert_pair(c, e->pt_int, dPT, e->at_int, dAT));
     }  // single-rank: deferred into the tail multi-insert (the traces are
@@ -3745,7 +3698,7 @@ static dbsp_status q8_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     if (!sharding_on(c)) {
         std::function<dbsp_status()> hook = [&]() -> dbsp_status {
             if (!e->next_ev || e->next_n < 0 || e->next_n > 131072 ||
-                e->spec_fail >= 3 || !e->d_wm)
+                e->spec_fail >= 3)
                 return DBSP_OK;
             return enqueue_front(e, [&] {
                 return build_deltas_chain(e, e->next_ev, e->next_n,
@@ -3774,6 +3727,16 @@ static dbsp_status q5_front(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
         (unsigned long long *)(c->d_len + L_MINMAX));
 }
 
+// merge a delta (retained) into a consolidated single-batch integral
+static dbsp_status integral_add(dbsp_ctx *c, DevBatch &integral,
+                                const DevBatch &delta) {
+    DevBatch m;
+    TRY(merge_batches(c, integral, delta, m));
+    free_batch(c, integral);
+    integral = m;
+    return DBSP_OK;
+}
+
 // ---- q5 tick (queries/q5.rs:77-121) ----
 static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
@@ -3782,10 +3745,9 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     // Single-rank ticks: flatmap and the dense-range min/max probe chain into
     // ONE sync, the bid delta sorts through the dense path, and the
     // watermark/window-ranges run device-side as in q8.
-    const bool chain = !sharding_on(c) && e->d_wm;
+    const bool chain = !sharding_on(c);
     DevBatch dBT;
-    std::vector<DevBatch> wb_raw;
-    WindowPlan wpB;
+    bool n_pending = false;  // dBT.n still on the device (L_DENSE)
     const bool use_front = take_front(e, d_ev, n);
     if (chain) {
         DevBatch raw0, raw1;
@@ -3799,7 +3761,6 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         free_batch(c, raw1);
         const int64_t n0 = H[L_RAW];
         raw0.n = n0;
-        bool n_pending = false;  // dBT.n still on the device (L_DENSE)
         if (n0 == 0) {
             dBT = DevBatch{};
             free_batch(c, raw0);
@@ -3826,57 +3787,20 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
                 TRY(sort_consolidate_batch(c, raw0, dBT));
             }
         }
-        // device watermark + chained window ranges (q5.rs:85-90)
-        if (n_pending) {
-            TRY(dbspk::wm_update(c->stream, dBT.k, c->d_len + L_DENSE,
-                                 WIDTH_MS, TUMBLE_MS, WM_LAG_MS, e->d_wm,
-                                 e->d_bounds));
-        } else {
-            TRY(dbspk::wm_update_n(c->stream, dBT.k, dBT.n, WIDTH_MS,
-                                   TUMBLE_MS, WM_LAG_MS, e->d_wm,
-                                   e->d_bounds));
-        }
-        TRY(window_plan(c, e->bt_int, wpB));
-        if (wpB.table) {
-            {
-                ScopedTimer t(c, 4, 0.0);
-                TRY(dbspk::window_ranges_chain(
-                    c->stream, wpB.ta, dBT.k, dBT.n,
-                    n_pending ? c->d_len + L_DENSE : nullptr, e->d_bounds,
-                    wpB.table, c->d_len + L_WIN));
-            }
-            TRY(read_len(c, LEN_BASE0, LEN_TICK));
-            if (n_pending) dBT.n = H[L_DENSE];
-            TRY(window_emit(c, wpB, H[L_WIN], dBT, wb_raw));
-        } else {
-            // no arena for the table: wm_update already advanced the device
-            // state and published the bounds — read them (and the pending
-            // dense length) and run the explicit window path
-            TRY(read_bounds(e, /*sync=*/false));
-            TRY(read_len(c, LEN_BASE0, LEN_TICK));
-            if (n_pending) dBT.n = H[L_DENSE];
-            TRY(window_vs_spine_bounds(c, e->bt_int, dBT, e->h_bounds, wb_raw));
-        }
     } else {
-        // explicit deltas (sharded exchange), device watermark
+        // explicit deltas (sharded exchange)
         DevBatch dummy;
         TRY(build_deltas(e, d_ev, n, dBT, dummy, false));
-        TRY(wm_update_global(e, dBT, WIDTH_MS, TUMBLE_MS, WM_LAG_MS));
-        TRY(window_plan(c, e->bt_int, wpB));
-        if (wpB.table) {
-            {
-                ScopedTimer t(c, 4, 0.0);
-                TRY(dbspk::window_ranges_chain(c->stream, wpB.ta, dBT.k, dBT.n,
-                                               nullptr, e->d_bounds, wpB.table,
-                                               c->d_len + L_WIN));
-            }
-            TRY(read_len(c, L_WIN, 1));
-            TRY(window_emit(c, wpB, H[L_WIN], dBT, wb_raw));
-        } else {
-            TRY(read_bounds(e, /*sync=*/true));
-            TRY(window_vs_spine_bounds(c, e->bt_int, dBT, e->h_bounds, wb_raw));
-        }
     }
+    // device watermark + chained window ranges (q5.rs:85-90)
+    WindowLeg leg{&e->bt_int, &dBT, n_pending ? c->d_len + L_DENSE : nullptr,
+                  L_WIN};
+    TRY(wm_update(e, dBT, leg.n_dev, WIDTH_MS, TUMBLE_MS, WM_LAG_MS));
+    TRY(window_launch(e, &leg, 1));
+    TRY(read_len(c, LEN_BASE0, LEN_TICK));
+    if (n_pending) dBT.n = H[L_DENSE];
+    std::vector<DevBatch> wb_raw;
+    TRY(window_emit(c, leg, wb_raw));
     if (sharding_on(c)) TRY(e->bt_int.insert(c, dBT));
     // single-rank: bt_int is only read next tick — inserted in the tail
     // multi-insert
@@ -3906,11 +3830,8 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     }
     DevBatch dMaxOut;
     if (dMaxIn.n > 0) {
-        DevBatch m;
-        TRY(merge_batches(c, e->maxin_int, dMaxIn, m));
-        free_batch(c, e->maxin_int);
+        TRY(integral_add(c, e->maxin_int, dMaxIn));
         free_batch(c, dMaxIn);
-        e->maxin_int = m;
         // delta key is the unit key ()
         uint64_t *d_unit;
         HIP_CHECK_ST(dbspk::cache_malloc((void **)&d_unit, 8, c->stream));
@@ -3920,10 +3841,7 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
                                    e->maxin_int, e->maxout_int, &raw));
         HIP_CHECK_ST(dbspk::cache_free(d_unit, c->stream));
         TRY(sort_consolidate_batch(c, raw, dMaxOut));
-        DevBatch m2;
-        TRY(merge_batches(c, e->maxout_int, dMaxOut, m2));
-        free_batch(c, e->maxout_int);
-        e->maxout_int = m2;
+        TRY(integral_add(c, e->maxout_int, dMaxOut));
     } else {
         free_batch(c, dMaxIn);
     }
@@ -3940,13 +3858,8 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     // final incremental join (q5.rs:118-120)
     std::vector<DevBatch> outs;
     TRY(join_vs_spine(c, dMaxZ, e->bc_int, DBSP_PROJ_HI_V2_LO_K, 0, outs));
-    {
-        DevBatch m;
-        TRY(merge_batches(c, e->maxz_int, dMaxZ, m));
-        free_batch(c, e->maxz_int);
-        free_batch(c, dMaxZ);
-        e->maxz_int = m;
-    }
+    TRY(integral_add(c, e->maxz_int, dMaxZ));
+    free_batch(c, dMaxZ);
     if (dBC.n > 0 && e->maxz_int.n > 0) {
         DevBatch o;
         TRY(dbspk::join_rows(c->stream, dBC, e->maxz_int, DBSP_PROJ_HI_V1_LO_K,
@@ -3959,7 +3872,7 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     TRY(final_begin(e, outs, !sharding_on(c), async_final));
     if (!sharding_on(c)) {
         std::function<dbsp_status()> hook = [&]() -> dbsp_status {
-            if (!e->next_ev || e->next_n < 0 || !e->d_wm) return DBSP_OK;
+            if (!e->next_ev || e->next_n < 0) return DBSP_OK;
             return enqueue_front(e, [&] {
                 e->front.oA = e->front.oB = DevBatch{};
                 return q5_front(e, e->next_ev, e->next_n, e->front.rawA,

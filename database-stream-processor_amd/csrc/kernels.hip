@@ -2730,91 +2730,18 @@ __global__ void k_emit_nonzero(const uint64_t *keys, const W *acc, int64_t nd,
 }
 
 // ---------------------------------------------------------------------------
-// window ranges (window.rs:144-220): 4 slice copies with sign
+// device-resident watermark (q5.rs:85-90 / q8.rs:63-65 waterline): a single
+// thread advances the persistent watermark state by the tick's max event
+// time and publishes the window bounds for the chained ranges launch.
+// state = {wm, s0, e0, have_prev}; bounds = {s0, e0, s1, e1, have_prev, err}.
 // ---------------------------------------------------------------------------
 
-// compute the 4 region ranges on device: [r0lo,r0hi) retract, [r1lo,r1hi)
-// retract-shrink, [r2lo,r2hi) insert (trace), [r3lo,r3hi) insert (batch)
-__global__ void k_window_ranges(const uint64_t *tk, int64_t nt,
-                                const uint64_t *bk, int64_t nb, int have_prev,
-                                uint64_t s0, uint64_t e0, uint64_t s1,
-                                uint64_t e1, int64_t *ranges /* [8] */) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int64_t r0lo = 0, r0hi = 0, r1lo = 0, r1hi = 0, r2lo = 0, r2hi = 0;
-    if (have_prev) {
-        uint64_t r0end = min(s1, e0);
-        r0lo = lower_bound_k(tk, nt, s0);
-        r0hi = max(r0lo, (int64_t)lower_bound_k(tk, nt, r0end));
-        if (e1 < e0) {
-            r1lo = lower_bound_k(tk, nt, e1);
-            r1hi = max(r1lo, (int64_t)lower_bound_k(tk, nt, e0));
-        }
-        uint64_t r2start = max(e0, s1);
-        r2lo = lower_bound_k(tk, nt, r2start);
-        r2hi = max(r2lo, (int64_t)lower_bound_k(tk, nt, e1));
-    }
-    int64_t r3lo = lower_bound_k(bk, nb, s1);
-    int64_t r3hi = max(r3lo, (int64_t)lower_bound_k(bk, nb, e1));
-    ranges[0] = r0lo; ranges[1] = r0hi; ranges[2] = r1lo; ranges[3] = r1hi;
-    ranges[4] = r2lo; ranges[5] = r2hi; ranges[6] = r3lo; ranges[7] = r3hi;
-}
-
-__global__ void k_window_emit(const uint64_t *tk, const uint64_t *tv,
-                              const int64_t *tw, const uint64_t *bk,
-                              const uint64_t *bv, const int64_t *bw,
-                              const int64_t *ranges, uint64_t *ok, uint64_t *ov,
-                              int64_t *ow) {
-    int64_t len0 = ranges[1] - ranges[0];
-    int64_t len1 = ranges[3] - ranges[2];
-    int64_t len2 = ranges[5] - ranges[4];
-    int64_t len3 = ranges[7] - ranges[6];
-    int64_t total = len0 + len1 + len2 + len3;
-    for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < total;
-         o += (int64_t)gridDim.x * blockDim.x) {
-        int64_t src;
-        int64_t sign;
-        const uint64_t *k;
-        const uint64_t *v;
-        const int64_t *w;
-        if (o < len0) { src = ranges[0] + o; sign = -1; k = tk; v = tv; w = tw; }
-        else if (o < len0 + len1) { src = ranges[2] + (o - len0); sign = -1; k = tk; v = tv; w = tw; }
-        else if (o < len0 + len1 + len2) { src = ranges[4] + (o - len0 - len1); sign = 1; k = tk; v = tv; w = tw; }
-        else { src = ranges[6] + (o - len0 - len1 - len2); sign = 1; k = bk; v = bv; w = bw; }
-        ok[o] = k[src];
-        ov[o] = v[src];
-        ow[o] = sign * w[src];
-    }
-}
-
-// multi-batch window: all three regions of every spine batch plus the tick's
-// batch region in one ranges launch + one emit launch (window.rs:144-220
-// evaluated per spine batch; the trace excludes the current tick).
-// Region table rows: [src_batch(-1 = tick batch), lo, len, sign, goff]
-
-// ---------------------------------------------------------------------------
-// device-resident watermark (q5.rs:85-90 / q8.rs:63-65 waterline): single
-// thread reads the sorted delta's last key (the tick's max event-time),
-// advances the persistent watermark state and publishes the window bounds
-// for the chained ranges launch.  state = {wm, s0, e0, have_prev};
-// bounds = {s0, e0, s1, e1, have_prev, err}.  err=1 when the delta length is
-// the speculative-sort overflow sentinel — the host then recomputes on its
-// explicit path (the state is left untouched).
-// ---------------------------------------------------------------------------
-__device__ void wm_update_body(const uint64_t *ak, int64_t n, uint64_t width,
-                               uint64_t tumble, uint64_t lag,
-                               unsigned long long *state,
-                               unsigned long long *bounds);
-
-// sharded variant: the tick's global max event-time arrives REDUCED in
-// *gmax_dev (local last key -> ncclAllReduce(max) on the stream), so the
-// whole watermark/window-bounds update stays device-side across ranks
-__global__ void k_wm_update_g(const unsigned long long *gmax_dev,
-                              uint64_t width, uint64_t tumble, uint64_t lag,
-                              unsigned long long *state,
-                              unsigned long long *bounds) {
-    const uint64_t g = *gmax_dev;
+// gmax: the tick's max event time, 0 when it has none
+__device__ void wm_advance(uint64_t gmax, uint64_t width, uint64_t tumble,
+                           uint64_t lag, unsigned long long *state,
+                           unsigned long long *bounds) {
     uint64_t wm = state[0];
-    if (g > 0) wm = max(wm, (uint64_t)(g - lag));
+    if (gmax > 0) wm = max(wm, gmax - lag);
     uint64_t rounded = wm - wm % tumble;
     uint64_t s1 = rounded >= width ? rounded - width : 0;
     uint64_t e1 = rounded;
@@ -2830,47 +2757,32 @@ __global__ void k_wm_update_g(const unsigned long long *gmax_dev,
     state[3] = 1;
 }
 
-__global__ void k_wm_update_n(const uint64_t *ak, int64_t n, uint64_t width,
-                              uint64_t tumble, uint64_t lag,
-                              unsigned long long *state,
-                              unsigned long long *bounds) {
-    wm_update_body(ak, n, width, tumble, lag, state, bounds);
-}
-
-__global__ void k_wm_update(const uint64_t *ak, const int64_t *n_dev,
-                            uint64_t width, uint64_t tumble, uint64_t lag,
-                            unsigned long long *state,
+// err=1 when the delta length is the speculative-sort overflow sentinel: the
+// state is left untouched and the host runs the update again with the real
+// length once it has re-sorted
+__global__ void k_wm_update(WmSource src, uint64_t width, uint64_t tumble,
+                            uint64_t lag, unsigned long long *state,
                             unsigned long long *bounds) {
-    wm_update_body(ak, *n_dev, width, tumble, lag, state, bounds);
+    uint64_t gmax = 0;
+    if (src.gmax_dev) {
+        gmax = *src.gmax_dev;
+    } else {
+        const int64_t n = src.n_dev ? *src.n_dev : src.n;
+        if (n < 0) {
+            bounds[5] = 1;
+            return;
+        }
+        if (n > 0) gmax = src.ak[n - 1];
+    }
+    wm_advance(gmax, width, tumble, lag, state, bounds);
 }
 
-__device__ void wm_update_body(const uint64_t *ak, int64_t n, uint64_t width,
-                               uint64_t tumble, uint64_t lag,
-                               unsigned long long *state,
-                               unsigned long long *bounds) {
-    if (n < 0) {
-        bounds[5] = 1;
-        return;
-    }
-    uint64_t wm = state[0];
-    if (n > 0) {
-        uint64_t gmax = ak[n - 1];
-        if (gmax > 0) wm = max(wm, gmax - lag);
-    }
-    uint64_t rounded = wm - wm % tumble;
-    uint64_t s1 = rounded >= width ? rounded - width : 0;
-    uint64_t e1 = rounded;
-    bounds[0] = state[1];
-    bounds[1] = state[2];
-    bounds[2] = s1;
-    bounds[3] = e1;
-    bounds[4] = state[3];
-    bounds[5] = 0;
-    state[0] = wm;
-    state[1] = s1;
-    state[2] = e1;
-    state[3] = 1;
-}
+// ---------------------------------------------------------------------------
+// window (window.rs:144-220): all three regions of every spine batch plus the
+// tick's batch region in one ranges launch + one emit launch (evaluated per
+// spine batch; the trace excludes the current tick).
+// Region table rows: [src_batch(-1 = tick batch), lo, len, sign, goff]
+// ---------------------------------------------------------------------------
 
 __global__ void k_window_ranges_multi(TraceArgs t, const uint64_t *bk,
                                       int64_t bn, int have_prev, uint64_t s0,
@@ -3883,29 +3795,6 @@ dbsp_status distinct_inc_rows(hipStream_t s, const Rows &delta,
     return give_rows(sc, r, out);
 }
 
-dbsp_status window_rows(hipStream_t s, const Rows &trace, const Rows &batch,
-                        int have_prev, uint64_t s0, uint64_t e0, uint64_t s1,
-                        uint64_t e1, Rows *out) {
-    Scratch sc(s);
-    int64_t *d_ranges;
-    HIP_CHECK(sc.get(&d_ranges, 8 * sizeof(int64_t)));
-    k_window_ranges<<<1, 1, 0, s>>>(trace.k, trace.n, batch.k, batch.n,
-                                    have_prev, s0, e0, s1, e1, d_ranges);
-    int64_t h_ranges[8];
-    HIP_CHECK(hipMemcpyAsync(h_ranges, d_ranges, sizeof(h_ranges),
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    int64_t total = (h_ranges[1] - h_ranges[0]) + (h_ranges[3] - h_ranges[2]) +
-                    (h_ranges[5] - h_ranges[4]) + (h_ranges[7] - h_ranges[6]);
-    Rows r;
-    TRY_K(alloc_rows(sc, total, &r));
-    if (total > 0)
-        k_window_emit<<<grid_for(total), BLK, 0, s>>>(
-            trace.k, trace.v, trace.w, batch.k, batch.v, batch.w, d_ranges,
-            r.k, r.v, r.w);
-    return give_rows(sc, r, out);
-}
-
 dbsp_status window_ranges_multi(hipStream_t s, const TraceArgs &t,
                                 const uint64_t *bk, int64_t bn, int have_prev,
                                 uint64_t s0, uint64_t e0, uint64_t s1,
@@ -3916,27 +3805,10 @@ dbsp_status window_ranges_multi(hipStream_t s, const TraceArgs &t,
     return DBSP_OK;
 }
 
-dbsp_status wm_update(hipStream_t s, const uint64_t *ak, const int64_t *n_dev,
-                      uint64_t width, uint64_t tumble, uint64_t lag,
-                      unsigned long long *state, unsigned long long *bounds) {
-    k_wm_update<<<1, 1, 0, s>>>(ak, n_dev, width, tumble, lag, state, bounds);
-    return DBSP_OK;
-}
-
-dbsp_status wm_update_n(hipStream_t s, const uint64_t *ak, int64_t n,
-                        uint64_t width, uint64_t tumble, uint64_t lag,
-                        unsigned long long *state,
-                        unsigned long long *bounds) {
-    k_wm_update_n<<<1, 1, 0, s>>>(ak, n, width, tumble, lag, state, bounds);
-    return DBSP_OK;
-}
-
-dbsp_status wm_update_g(hipStream_t s, const unsigned long long *gmax_dev,
-                        uint64_t width, uint64_t tumble, uint64_t lag,
-                        unsigned long long *state,
-                        unsigned long long *bounds) {
-    k_wm_update_g<<<1, 1, 0, s>>>(gmax_dev, width, tumble, lag, state,
-                                  bounds);
+dbsp_status wm_update(hipStream_t s, const WmSource &src, uint64_t width,
+                      uint64_t tumble, uint64_t lag, unsigned long long *state,
+                      unsigned long long *bounds) {
+    k_wm_update<<<1, 1, 0, s>>>(src, width, tumble, lag, state, bounds);
     return DBSP_OK;
 }
 

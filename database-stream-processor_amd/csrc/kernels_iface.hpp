@@ -116,6 +116,15 @@ struct JoinCountArgs {
     int64_t *starts[3];
 };
 
+// where the device watermark takes the tick's max event time from
+struct WmSource {
+    const uint64_t *ak;  // sorted time keys of the tick's delta: the last one
+    int64_t n;           // ... of n rows,
+    const int64_t *n_dev;  // or of *n_dev if set (negative: bounds err = 1,
+                           // state untouched)
+    const unsigned long long *gmax_dev;  // if set, overrides all the above: an
+                                         // already reduced maximum (0 = none)
+};
 
 namespace dbspk {
 // big-buffer free-list over hipMallocAsync (see kernels.hip): same signature
@@ -159,15 +168,14 @@ dbsp_status consolidate_sorted(hipStream_t s, const Rows &in, bool wf64,
 dbsp_status merge_rows(hipStream_t s, const Rows &a, const Rows &b, bool wf64,
                        Rows *out);
 
-dbsp_status wm_update(hipStream_t s, const uint64_t *ak, const int64_t *n_dev,
-                      uint64_t width, uint64_t tumble, uint64_t lag,
-                      unsigned long long *state, unsigned long long *bounds);
-dbsp_status wm_update_n(hipStream_t s, const uint64_t *ak, int64_t n,
-                        uint64_t width, uint64_t tumble, uint64_t lag,
-                        unsigned long long *state, unsigned long long *bounds);
-dbsp_status wm_update_g(hipStream_t s, const unsigned long long *gmax_dev,
-                        uint64_t width, uint64_t tumble, uint64_t lag,
-                        unsigned long long *state, unsigned long long *bounds);
+// device watermark: advance state = {wm, s0, e0, have_prev} by the tick's max
+// event time and publish bounds = {s0, e0, s1, e1, have_prev, err} (no sync)
+dbsp_status wm_update(hipStream_t s, const WmSource &src, uint64_t width,
+                      uint64_t tumble, uint64_t lag, unsigned long long *state,
+                      unsigned long long *bounds);
+// ranges launch behind wm_update: the bounds are read from the device, and the
+// tick batch's length from *bn_dev when it is given (else bn).  err bounds or
+// a negative device length leave *d_total = -1.
 dbsp_status window_ranges_chain(hipStream_t s, const TraceArgs &t,
                                 const uint64_t *bk, int64_t bn,
                                 const int64_t *bn_dev,
@@ -328,10 +336,6 @@ dbsp_status agg_sum_batch(hipStream_t s, const uint64_t *keys, int64_t nd,
 // f64: v holds the sum's bit pattern.
 dbsp_status emit_nonzero(hipStream_t s, const uint64_t *keys,
                          const int64_t *acc, int64_t nd, bool wf64, Rows *out);
-
-dbsp_status window_rows(hipStream_t s, const Rows &trace, const Rows &batch,
-                        int have_prev, uint64_t s0, uint64_t e0, uint64_t s1,
-                        uint64_t e1, Rows *out);
 
 // multi-batch window: ranges for all spine batches + tick batch in one launch
 // (region table rows [src,lo,len,sign,goff]; total left in *d_total), then one
