@@ -197,14 +197,19 @@ struct dbsp_ctx {
     hipEvent_t ev_sync2 = nullptr;  // early-wake event (post-count readback)
     hipEvent_t ev_tick[2] = {nullptr, nullptr};  // pipelined-train events
     hipEvent_t ev_tail[2] = {nullptr, nullptr};  // train tail (post 2nd readback)
-    // q3 train fork: the accumulator merge and the head readback run on a
-    // side stream behind ev_fork (recorded on the main stream after the delta
-    // sorts); ev_tick, recorded on the side stream, is what the main stream
-    // joins on before the tail readback.  q3_fork is off under DBSP_PROFILE
-    // (ScopedTimer's events assume one stream) and with DBSP_Q3_FORK=0.
+    // q3 train fork: `stream` is the LOOP stream (flatmap, delta sorts, fold,
+    // head readback, ev_tick: what the host waits for each tick); the probe,
+    // the join tail and the tail readback run on the BACK stream `side`
+    // behind ev_fork (recorded on the loop stream after the delta sorts) and
+    // end in ev_tail.  q3_fork is off under DBSP_PROFILE (ScopedTimer's
+    // events assume one stream) and with DBSP_Q3_FORK=0.
     hipStream_t side = nullptr;
     hipEvent_t ev_fork[2] = {nullptr, nullptr};
     bool q3_fork = false;
+    // index of the last ev_tail recorded on the back stream that the loop
+    // stream has not been ordered behind (neither by a stream wait nor by a
+    // host sync); -1: no back-stream work can be live.  See q3_join_back.
+    int back_live = -1;
     // deferred spine-insert round (train path): the last small-merge round's
     // length readback is resolved at the NEXT insert/step on a near-empty
     // stream instead of blocking behind the next tick's freshly enqueued
@@ -259,6 +264,23 @@ static inline void arena_other_half(dbsp_ctx *c, size_t base) {
 
 static inline bool in_arena(dbsp_ctx *c, const void *p) {
     return c->arena && p >= c->arena && p < c->arena + c->arena_sz;
+}
+
+// Join on demand (q3 trains; the ordering argument above the q3 tick): put
+// the loop stream behind everything enqueued on the back stream so far.  The
+// back stream runs in order, so its last ev_tail covers all of it.  Called
+// before anything on the loop stream frees, recycles or overwrites what a
+// probe or join tail in flight may still use; free when nothing is in flight.
+static inline void q3_join_back(dbsp_ctx *c) {
+    if (c->back_live < 0) return;
+    (void)hipStreamWaitEvent(c->stream, c->ev_tail[c->back_live], 0);
+    c->back_live = -1;
+}
+// the same where the host itself must be behind the back stream
+static inline void q3_sync_back(dbsp_ctx *c) {
+    if (c->back_live < 0) return;
+    (void)hipEventSynchronize(c->ev_tail[c->back_live]);
+    c->back_live = -1;
 }
 
 extern "C" dbsp_status dbsp_ctx_create(dbsp_ctx **out, int device) {
@@ -332,6 +354,7 @@ static void drop_pending_insert(dbsp_ctx *c);
 
 extern "C" dbsp_status dbsp_ctx_destroy(dbsp_ctx *c) {
     if (!c) return DBSP_OK;
+    q3_sync_back(c);
     drop_pending_insert(c);
     if (c->ev_insert) (void)hipEventDestroy(c->ev_insert);
     if (c->ev_tail[0]) (void)hipEventDestroy(c->ev_tail[0]);
@@ -363,6 +386,7 @@ extern "C" dbsp_status dbsp_ctx_destroy(dbsp_ctx *c) {
 
 extern "C" dbsp_status dbsp_ctx_sync(dbsp_ctx *c) {
     HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    q3_sync_back(c);
     return DBSP_OK;
 }
 
@@ -746,8 +770,11 @@ struct Spine {
         return DBSP_OK;
     }
 
-    // the two topmost batches give way to their merge (dropped when empty)
+    // the two topmost batches give way to their merge (dropped when empty).
+    // A q3 probe in flight on the back stream may still read them: whatever
+    // recycles their blocks runs behind the join (free when none is).
     void replace_top2(dbsp_ctx *c, DevBatch merged) {
+        q3_join_back(c);
         free_batch(c, batches.back());
         batches.pop_back();
         free_batch(c, batches.back());
@@ -1403,6 +1430,9 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
     if (e && e->d_wm) (void)hipFree(e->d_wm);
     if (!e) return DBSP_OK;
     dbsp_ctx *c = e->ctx;
+    // a pending q3 train's probe and join tail read the spines, the deltas
+    // and out_store on the back stream: nothing is freed under them
+    if (c) q3_sync_back(c);
     // discard any deferred insert round before the spines it references go
     // away (the merged pair is still in its spine's list, so dropping the
     // result is safe for ANY engine's pending round — at worst re-merged)
@@ -1427,7 +1457,7 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
         free_batch(c, e->front.oB);
     }
     if (e->train.pending) {
-        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->stream);  // back stream: synced above
         q3_train_drop(c, e->train);
     }
     if (e->out_store.k) free_batch(c, e->out_store);
@@ -1696,12 +1726,12 @@ enum : int {
     HK_FLATMAP,  // raw-stream arena bumps, counter fill (if any), flatmap
     HK_SORT,     // sort scratch + delta allocations, delta sorts
     HK_ALLOC,    // accumulator-result allocations
-    HK_FORK,     // fork event record + side-stream wait
+    HK_FORK,     // fork event record
     HK_MERGE,    // accumulator fold / merge launch
     HK_HEAD,     // head copy + ev_tick record
-    HK_PROBE,    // plan build + probe launch
+    HK_PROBE,    // back-stream wait on the fork event, plan build, probe
     HK_TAIL,     // join tail buffers + launch
-    HK_JOIN,     // join wait + tail copy + ev_tail record
+    HK_JOIN,     // tail copy + ev_tail record
     HK_N
 };
 static const bool g_hook_prof = []() {
@@ -2815,31 +2845,72 @@ extern "C" dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e,
 // (LEN_BASE0 / LEN_BASE1), the events and the arena halves; the
 // spine-insert rounds use the LEN_ROUND slots.
 //
-// Inside a train the accumulator merge (this tick's deltas folded into the
-// per-spine memtable) is off the critical path: nothing in the tick reads
-// its result — the probes read the pre-insert spines — so it FORKS to a side
-// stream:
-//   main: flatmap (no fill) -> delta sorts (take) -> record ev_fork
-//   side: wait ev_fork -> accumulator fold -> head readback -> record ev_tick
-//   main: probe -> join tail -> wait ev_tick -> tail readback -> record ev_tail
-// Ordering argument (what buffer recycling and slot reuse rest on):
-//  1. The main stream joins the side stream (wait ev_tick, the side
-//     stream's last event of the train) before the train's last main-stream
-//     operation.  So everything train t launched, on either stream, is
-//     complete before anything enqueued on the main stream after train t:
-//     commit-side frees and allocations, spill rounds, replays, train t+1.
-//     A train that bails after forking joins before it unwinds.
-//  2. The side stream runs train work only, and train t+1's side work waits
-//     ev_fork(t+1), which the main stream records after train t's join.  So
-//     side work of t+1 follows all of train t and everything the commit of
-//     tick t enqueued on the main stream before the enqueue of train t+1.
-//  3. Hence any two users of a recycled buffer, of a length slot or of the
-//     merge scratch d_mid are ordered exactly as they were on one stream.
-//     The accumulator fold uses no d_mid; rule 2 still carries the recycled
-//     buffers and length slots, and d_mid under DBSP_Q3_FOLD=0: the spill
-//     rounds of commit t are main-stream work enqueued before ev_fork(t+1)
-//     (rule 2) and after the join of train t (rule 1), so they never
-//     overlap a side merge.
+// The train forks.  The host's loop is: wake on ev_tick(t), verdict + swap,
+// enqueue train t+1, whose ev_tick it wakes on next.  What that loop waits
+// for — flatmap, delta sorts, the accumulator fold, the head readback — is
+// one stream with nothing else in it; what nobody waits for until the
+// commit's end — probe, join tail, tail readback — runs beside it:
+//   loop (c->stream): flatmap (no fill) -> delta sorts (take) -> record
+//                     ev_fork -> fold -> head readback -> record ev_tick
+//   back (c->side):   wait ev_fork -> probe -> join tail -> tail readback
+//                     -> record ev_tail
+// The hook enqueues all loop-stream work first, through ev_tick, then the
+// back-stream work.  Nothing flatmap(t+1) or sort(t+1) touches is produced
+// by probe(t) or tail(t), so on the common path the loop stream never waits
+// for the back stream.
+// Ordering argument (what buffer recycling and slot reuse rest on).  The
+// free list hands a freed block to the next allocation at once, so reuse is
+// safe only where stream order, or a completion the host has observed,
+// separates the users.
+//  1. Back-stream work of train t+1 waits ev_fork(t+1).  So it follows
+//     everything enqueued on the loop stream before it: fold(t), every
+//     kernel of commit t (spill rounds, replays of an earlier tick), and
+//     flatmap and sorts of t+1.  The back stream runs in order, so it also
+//     follows all of back(t).
+//  2. The loop stream follows back-stream work only through a JOIN ON DEMAND
+//     (q3_join_back: the loop stream waits the last ev_tail recorded, which
+//     covers the whole back stream; q3_sync_back where the host must be
+//     behind it) or through the commit's own hipEventSynchronize(ev_tail(t)).
+//     What back(t) uses: reads the deltas oA/oP(t), every spine batch listed
+//     at the enqueue of train t, and d_len[sb + L_DELTA]; reads and writes
+//     its arena buffers (cnts, starts, offsets, comb_chain, scr); writes
+//     out_store and d_len[sb + L_PLAN .. L_FINAL] — at base 0 those are the
+//     LEN_OP slots every sized op borrows — and h_len[sb + LH_*].  Every
+//     loop-stream path that frees, recycles or overwrites one of these while
+//     a train may be in flight joins first:
+//       - Spine::replace_top2, the one place spine batches are freed: the
+//         deferred round's resolve at the top of the commit (with its
+//         cascade rounds), the immediate merges of a spill round, the
+//         consolidate_all calls of the enqueue and of the unpipelined body,
+//         the rounds an unpipelined insert runs after its hook.  The first
+//         three also join explicitly, ahead of their sized merges' LEN_OP
+//         use;
+//       - the lost-speculation branch of the commit, before it drops the
+//         deltas and replays (sized sorts, possibly a new out_store);
+//       - both overflow replays of q3_publish_chained: tail(t) is complete
+//         there, but train t+1 is enqueued and its tail writes base 0's
+//         first slots when t+1 runs at base 0;
+//       - a train that bails after forking (records ev_tail, joins);
+//       - a stale train, and engine and context teardown (host syncs).
+//     Safe without a join: the frees after q3_publish_chained (the host has
+//     synced ev_tail(t); train t+1 reads none of them), free_batch of an
+//     empty fold result (loop-stream order), the batched merges of a spill
+//     round (they read what the back stream reads, write fresh blocks and
+//     use the LEN_ROUND slots and d_mid, which the back stream never
+//     touches), and engine_free_output (a replay's output, loop-stream work).
+//  3. Length slots: train t+2 reuses the base and the events of train t, and
+//     is enqueued by commit t+1, after commit t synced ev_tail(t).
+//  4. ARENA RULE: consecutive trains bump from offset 0 of opposite halves,
+//     and commit t continues behind train t's transients in t's half.  So a
+//     loop-stream write of train t+1 (raw streams, sort scratch) is in the
+//     half back(t) does not use, commit-side transients of t lie above
+//     everything train t allocated, and train t+2 — same half as t — is
+//     enqueued after the host synced ev_tail(t), behind commit t's
+//     transients in loop-stream order.  This also keeps plans[].cnts and
+//     plans[].offsets of tick t intact for an emit-overflow replay at its
+//     publish: with both trains bumping from offset 0 of one half, as
+//     before, probe(t+1) overwrote them ahead of the replay whenever the two
+//     ticks had the same size.
 //
 // Counter hand-back: a train's delta sorts TAKE the flatmap's two ticket
 // counters (L_RAW of the train's base): each sort block reads its counter,
@@ -2847,11 +2918,11 @@ extern "C" dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e,
 // next flatmap on that base is launched without a counter fill
 // (dbsp_ctx::raw_zero says when that holds; every path that runs a plain
 // sort behind its flatmap keeps the fill and leaves the flag clear).
-// Ordering: flatmap(t) and the taking sort(t) are consecutive main-stream
+// Ordering: flatmap(t) and the taking sort(t) are consecutive loop-stream
 // launches.  Between that sort and the next flatmap on the same base — a
-// later train's, or a single step's on base 0, main-stream work behind it
-// either way — nothing reads or writes the two counters: the side stream's
-// head readback copies the base's head range, where it finds the lengths at
+// later train's, or a single step's on base 0, loop-stream work behind it
+// either way — nothing reads or writes the two counters: the back stream
+// touches neither, the head readback copies the base's head range, where it finds the lengths at
 // L_RAWN (the L_RAW words it also copies are dead), a lost speculation
 // replays from H[L_RAWN], and no op scratch slot aliases L_RAW
 // (static_assert above).  If the invariant broke anyway, the counters would
@@ -2859,11 +2930,12 @@ extern "C" dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e,
 // sort poisons a count above the capacity, and the replay refuses a raw
 // count above the tick's event count.
 // Under DBSP_PROFILE (ScopedTimer's events assume one stream) and with
-// DBSP_Q3_FORK=0 the side work stays on the main stream, in the same order.
+// DBSP_Q3_FORK=0 the back-stream work stays on the loop stream, in the order
+// of the layout above, and no join is ever needed.
 //
 // Per-tick stepping (no next_ev), sharded ranks, oversized ticks and lost
 // speculations all run the unpipelined body below: the same probe and join
-// tail in order on the main stream when chained, the explicit path otherwise.
+// tail in order on the loop stream when chained, the explicit path otherwise.
 
 static constexpr int64_t Q3_EMIT_CAP = 32768;
 
@@ -2871,11 +2943,11 @@ static constexpr int64_t Q3_EMIT_CAP = 32768;
 // guarantee the spine state is the one tick t's probes must read) and
 // enqueue the probe (spec: delta lengths still on device, L_DELTA of sb; the
 // probe keeps the start positions for the join tail) or count+scan (host
-// lengths).
-static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
-                                 bool spec, int sb, int64_t n_cap,
-                                 Q3Plan plans[3], int &np, int &jca_np,
-                                 bool &arena_ok) {
+// lengths) on stream s.
+static dbsp_status q3_plan_count(dbsp_engine *e, hipStream_t s, DevBatch &dA,
+                                 DevBatch &dP, bool spec, int sb,
+                                 int64_t n_cap, Q3Plan plans[3], int &np,
+                                 int &jca_np, bool &arena_ok) {
     dbsp_ctx *c = e->ctx;
     np = 0;
     arena_ok = true;
@@ -2928,20 +3000,18 @@ static dbsp_status q3_plan_count(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     if (arena_ok) {
         jca.d_total = c->d_len + sb + L_PLAN;
         // a chained tick only probes here: its join tail scans the counts
-        if (jca.np > 0 && spec) TRY(dbspk::join_probe_batch(c->stream, jca));
-        if (jca.np > 0 && !spec)
-            TRY(dbspk::join_count_scan_batch(c->stream, jca));
+        if (jca.np > 0 && spec) TRY(dbspk::join_probe_batch(s, jca));
+        if (jca.np > 0 && !spec) TRY(dbspk::join_count_scan_batch(s, jca));
     }
     return DBSP_OK;
 }
 
 // the join tail behind a chained probe: scan + emit into a capacity buffer +
-// output consolidate into the reused store, one launch.  Kernel only — the
-// caller queues the tail readback (q3_read_tail) once whatever else that
-// readback must follow is in the stream.  ok=false: arena exhausted, nothing
-// was launched.
-static dbsp_status q3_chain_tail(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
-                                 Q3Plan plans[3], int np, int sb,
+// output consolidate into the reused store, one launch on stream s.  Kernel
+// only — the caller queues the tail readback (q3_read_tail) behind it.
+// ok=false: arena exhausted, nothing was launched.
+static dbsp_status q3_chain_tail(dbsp_engine *e, hipStream_t s, DevBatch &dA,
+                                 DevBatch &dP, Q3Plan plans[3], int np, int sb,
                                  DevBatch &comb_chain, bool &ok) {
     dbsp_ctx *c = e->ctx;
     ok = false;
@@ -2985,14 +3055,15 @@ static dbsp_status q3_chain_tail(dbsp_engine *e, DevBatch &dA, DevBatch &dP,
     ta.ok = e->out_store.k;
     ta.ov = e->out_store.v;
     ta.ow = e->out_store.w;
-    TRY(dbspk::join_tail_small(c->stream, ta));
+    TRY(dbspk::join_tail_small(s, ta));
     ok = true;
     return DBSP_OK;
 }
-// the tail readback: device L_PLAN..L_FINAL of base sb -> host LH_*
-static inline dbsp_status q3_read_tail(dbsp_ctx *c, int sb) {
+// the tail readback on stream s: device L_PLAN..L_FINAL of base sb -> host
+// LH_*
+static inline dbsp_status q3_read_tail(dbsp_ctx *c, hipStream_t s, int sb) {
     return read_len_to(c, sb + LH_PLAN, sb + L_PLAN, LH_TAIL_N,
-                       /*sync=*/false);
+                       /*sync=*/false, s);
 }
 
 // explicit emits from prepared counts/offsets (the non-chained path and the
@@ -3100,6 +3171,11 @@ static dbsp_status q3_publish_chained(dbsp_engine *e, int sb, DevBatch &dA,
     dbsp_ctx *c = e->ctx;
     int64_t H[LEN_BASE_N];  // the replay's sized ops reuse h_len
     memcpy(H, c->h_len + sb, sizeof(H));
+    // Both replays below run sized ops, which borrow the LEN_OP slots: the
+    // first offsets of base 0, where the join tail of a NEXT train already
+    // enqueued at that base leaves its totals.  Join it first (overflow
+    // ticks only).
+    if (H[LH_EMIT_FLAG] != 0 || H[LH_FINAL] < 0) q3_join_back(c);
     if (H[LH_EMIT_FLAG] != 0) {
         // combined emits exceeded the capacity buffer: replay explicitly
         // from the tail kernel's counts/offsets/totals.  A plan whose total
@@ -3146,8 +3222,8 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
         for (;;) {
             int jca_np = 0;
             bool arena_ok = true;
-            TRY(q3_plan_count(e, dA, dP, spec, LEN_BASE0, n, plans, np, jca_np,
-                              arena_ok));
+            TRY(q3_plan_count(e, c->stream, dA, dP, spec, LEN_BASE0, n, plans,
+                              np, jca_np, arena_ok));
             // chained: the head readback carries the delta lengths; the
             // host wakes at an event recorded right after the copy, with
             // the join tail and its own readback queued behind it.
@@ -3156,9 +3232,9 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
             if (emits) {
                 TRY(read_len(c, LEN_BASE0 + L_HEAD, L_HEAD_N, /*sync=*/false));
                 (void)hipEventRecord(c->ev_sync2, c->stream);
-                TRY(q3_chain_tail(e, dA, dP, plans, np, LEN_BASE0, comb_chain,
-                                  chain_emits));
-                if (chain_emits) TRY(q3_read_tail(c, LEN_BASE0));
+                TRY(q3_chain_tail(e, c->stream, dA, dP, plans, np, LEN_BASE0,
+                                  comb_chain, chain_emits));
+                if (chain_emits) TRY(q3_read_tail(c, c->stream, LEN_BASE0));
                 (void)hipEventSynchronize(c->ev_sync2);
             } else {
                 TRY(read_len(c, LEN_BASE0, LEN_TICK));
@@ -3207,9 +3283,9 @@ static dbsp_status q3_body(dbsp_engine *e, const dbsp_event *d_ev, int64_t n,
     engine_free_output(e);
     // The hook enqueues the NEXT tick's train mid-insert (after this tick's
     // merge launches, before their wait): probing the pre-cascade batch
-    // list is Z-set-identical to the merged state, and the train's
-    // fork/join ordering (comment above the q3 tick) keeps any recycled
-    // buffers safe.  The insert's event sync
+    // list is Z-set-identical to the merged state, and the round's
+    // replace_top2 joins the back stream before it frees that list (rule 2
+    // above the q3 tick).  The insert's event sync
     // (recorded pre-hook) covers this tick's readbacks, so the length reads
     // after it are complete.  Sharded ranks run no trains.
     std::function<dbsp_status()> hook = [&]() -> dbsp_status {
@@ -3266,11 +3342,16 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         bail();
         return st;
     }
+    // consolidating frees every batch of the spine, which the previous
+    // train's probe may still read, and its sized merges borrow the LEN_OP
+    // slots that a join tail at base 0 writes: join the back stream first
     if ((int)e->p_int.batches.size() > MAX_TRACE_BATCHES) {
+        q3_join_back(c);
         TRY(e->p_int.consolidate_all(c));
         e->q3_acc[1] = DevBatch{};
     }
     if ((int)e->a_int.batches.size() > MAX_TRACE_BATCHES) {
+        q3_join_back(c);
         TRY(e->a_int.consolidate_all(c));
         e->q3_acc[0] = DevBatch{};
     }
@@ -3278,12 +3359,12 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
     // memtable (one 2-pair launch; delta lengths read from the d_len slots
     // the chain just wrote, so nothing here waits).  The commit swaps the
     // spine top for the result — or, past the spill threshold, seals it as a
-    // ladder batch.  Nothing in this tick reads the result (the probes read
-    // the pre-insert spines), so with the fork on it runs on the side stream
-    // beside the probe and the join tail, followed there by the head
-    // readback the host wakes on.
+    // ladder batch.  The host waits for its lengths, so it stays on the loop
+    // stream, followed there by the head readback the host wakes on; the
+    // probe and the join tail, which nobody waits for until the commit's
+    // end, fork to the back stream behind the sorts.
     const bool fork = c->q3_fork;
-    hipStream_t ss = fork ? c->side : c->stream;
+    hipStream_t back = fork ? c->side : c->stream;
     {
         MergeArgs ma{};
         for (int s = 0; s < 2; s++) {
@@ -3303,34 +3384,38 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         ma.d_len = c->d_len + sb + L_XCHG;
         ScopedTimer timer(c, 1, (double)(e->q3_acc[0].n + e->q3_acc[1].n +
                                          2 * n) * 48.0);
-        if (fork) {
-            HIP_CHECK_ST(hipEventRecord(c->ev_fork[evi], c->stream));
-            HIP_CHECK_ST(hipStreamWaitEvent(ss, c->ev_fork[evi], 0));
-        }
+        // the fork point: behind the sorts, in front of the fold
+        if (fork) HIP_CHECK_ST(hipEventRecord(c->ev_fork[evi], c->stream));
         hook_mark(HK_FORK);
         // the fold needs no scratch and no barrier between workgroups;
         // DBSP_Q3_FOLD=0 keeps the general merge here for comparison
         if (c->q3_fold)
-            TRY(dbspk::acc_fold_batch(ss, ma, false));
+            TRY(dbspk::acc_fold_batch(c->stream, ma, false));
         else
-            TRY(dbspk::merge_mid_batch(ss, ma, c->d_mid, false));
+            TRY(dbspk::merge_mid_batch(c->stream, ma, c->d_mid, false));
         hook_mark(HK_MERGE);
     }
-    TRY(read_len_to(c, sb + L_HEAD, sb + L_HEAD, L_HEAD_N, /*sync=*/false, ss));
-    HIP_CHECK_ST(hipEventRecord(c->ev_tick[evi], ss));
+    TRY(read_len_to(c, sb + L_HEAD, sb + L_HEAD, L_HEAD_N, /*sync=*/false));
+    HIP_CHECK_ST(hipEventRecord(c->ev_tick[evi], c->stream));
     hook_mark(HK_HEAD);
-    // from here on a bail must rejoin the side stream first: whatever the
-    // main stream runs next may recycle the buffers the merge is writing
+    // The loop stream's part ends here; the rest goes to the back stream.
+    // A bail from here on puts the loop stream behind what the back stream
+    // got: the next step's unpipelined body recycles the train's buffers.
+    if (fork) HIP_CHECK_ST(hipStreamWaitEvent(back, c->ev_fork[evi], 0));
     auto bail_joined = [&](void) {
-        if (fork) (void)hipStreamWaitEvent(c->stream, c->ev_tick[evi], 0);
+        if (fork) {
+            (void)hipEventRecord(c->ev_tail[evi], back);
+            c->back_live = evi;
+            q3_join_back(c);
+        }
         bail();
     };
     int jca_np = 0;
     bool arena_ok = true;
     {
         ScopedTimer timer(c, 2, (double)n * 24.0);
-        TRY(q3_plan_count(e, T.oA, T.oP, true, sb, n, T.plans, T.np, jca_np,
-                          arena_ok));
+        TRY(q3_plan_count(e, back, T.oA, T.oP, true, sb, n, T.plans, T.np,
+                          jca_np, arena_ok));
     }
     hook_mark(HK_PROBE);
     if (!arena_ok || jca_np == 0) {
@@ -3338,21 +3423,19 @@ static dbsp_status q3_enqueue_train(dbsp_engine *e, const dbsp_event *d_ev,
         return DBSP_OK;  // fall back: next step runs the unpipelined body
     }
     bool tail_ok = false;
-    TRY(q3_chain_tail(e, T.oA, T.oP, T.plans, T.np, sb, T.comb_chain,
+    TRY(q3_chain_tail(e, back, T.oA, T.oP, T.plans, T.np, sb, T.comb_chain,
                       tail_ok));
     if (!tail_ok) {
         bail_joined();
         return DBSP_OK;
     }
     hook_mark(HK_TAIL);
-    // join: the tail readback and ev_tail follow BOTH streams' work, so
-    // ev_tail — and anything enqueued on the main stream after this train —
-    // is behind everything the train launched on either stream
-    if (fork) HIP_CHECK_ST(hipStreamWaitEvent(c->stream, c->ev_tick[evi], 0));
-    TRY(q3_read_tail(c, sb));
+    TRY(q3_read_tail(c, back, sb));
     // tail barrier: the commit's output-length and plan-total reads (host
-    // LH_* slots) wait this event just before consuming them
-    (void)hipEventRecord(c->ev_tail[evi], c->stream);
+    // LH_* slots) wait this event just before consuming them, and it is
+    // what a join on demand (q3_join_back) waits for
+    (void)hipEventRecord(c->ev_tail[evi], back);
+    if (fork) c->back_live = evi;
     hook_mark(HK_JOIN);
     T.arena_base = c->arena_base;
     T.arena_off = c->arena_off;
@@ -3390,18 +3473,24 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     e->train.pending = false;  // T owns the batches now
     e->train.oA = e->train.oP = DevBatch{};
     e->train.res[0] = e->train.res[1] = DevBatch{};
-    // commit-side transients go to the half the train is NOT using
-    arena_other_half(c, T.arena_base);
+    // arena rule: commit-side transients continue behind the train's own in
+    // the train's half; the next train (hook below) takes the other half
+    c->arena_base = T.arena_base;
+    c->arena_off = T.arena_off;
     (void)hipEventSynchronize(c->ev_tick[T.evi]);
     double t1 = prof ? host_us() : 0;
     int64_t H[LEN_TICK];  // the train's head readback (later ones reuse h_len)
     memcpy(H, c->h_len + T.sb, sizeof(H));
     if (q3_spec_lost(H)) {
         e->spec_fail++;
+        // the probe and the tail of this train bailed on the sentinel but
+        // may not have run yet: they read the deltas dropped here and write
+        // out_store and base-0 length slots that the replay reuses
+        q3_join_back(c);
         q3_train_drop(c, T);
         // re-materialize the deltas from the raw flatmap outputs (arena of
-        // the train's half — untouched until the next enqueue) and replay
-        // the tick explicitly
+        // the train's half, below what this commit bumps) and replay the
+        // tick explicitly
         // The train's sorts took the counters, so the raw lengths are at
         // L_RAWN (L_RAW with DBSP_Q3_TAKE=0).  A count above the tick's
         // event count cannot come from a flatmap that started at zero (the
@@ -3432,6 +3521,9 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     // past the spill threshold seal it into the ladder.  No kernel launch
     // on the common path, so the next train (hook below) starts within a
     // few microseconds of the wake.
+    // a deferred round's resolve frees the pre-cascade batches this train's
+    // probe reads, and its cascade rounds borrow LEN_OP slots: join first
+    if (c->pend_n) q3_join_back(c);
     TRY(resolve_pending_insert(c));
     constexpr int64_t Q3_ACC_SPILL = 32768;
     Spine *spill[2];
@@ -3470,7 +3562,10 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     };
     if (nspill > 0) {
         // sealed batches re-level through the classic rounds; the readback
-        // is deferred (stash) so nothing blocks behind the new train
+        // is deferred (stash) so nothing blocks behind the new train.  A
+        // pair past the batched merges' size is merged and freed at once,
+        // under this train's probe: join first (spill ticks only)
+        q3_join_back(c);
         TRY(spine_rounds(c, spill, nspill, &hook, &fired, /*defer=*/true));
     }
     if (!fired) TRY(hook());
@@ -3487,6 +3582,7 @@ static dbsp_status q3_commit_train(dbsp_engine *e) {
     // this tick's plan totals and output lengths land with the tail
     // readback, past ev_tick — wait the tail before consuming them
     (void)hipEventSynchronize(c->ev_tail[T.evi]);
+    if (c->back_live == T.evi) c->back_live = -1;  // no train behind it
     TRY(q3_publish_chained(e, T.sb, dA, dP, T.plans, T.np, T.comb_chain));
     free_batch(c, consumed[0]);
     free_batch(c, consumed[1]);
@@ -3501,8 +3597,10 @@ static dbsp_status q3_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
     if (e->train.pending) {
         if (e->train.ev == d_ev && e->train.n == n) return q3_commit_train(e);
-        // stale train (out-of-band step): drain its enqueued work, discard
+        // stale train (out-of-band step): drain its enqueued work on both
+        // streams, discard
         (void)hipStreamSynchronize(c->stream);
+        q3_sync_back(c);
         q3_train_drop(c, e->train);
         e->train.pending = false;
     }

@@ -10,7 +10,9 @@ The second form prints the launches / total ms / avg us table of the
 <ticks> ticks (timed + warmup).  The third prints the *_timeline.txt files:
 every dispatch of one q3 tick period with begin / end relative to the tick's
 flatmap, and the medians over the steady-state periods of the distances that
-tell which chain bounds the step.
+tell which chain bounds the step: tail(t) end -> flatmap(t+1) begin (the
+stream the tail runs on), sort end -> head copy end (the device's part of
+the host loop) and head copy end -> flatmap(t+1) begin (the host's part).
 """
 import sqlite3
 import sys
@@ -82,7 +84,7 @@ def timeline(path, tick_no, title=""):
     """One steady-state q3 tick period from the per-dispatch timestamps: every
     dispatch from the tick_no-th k_flatmap's begin to the next one's, in us
     relative to that begin, with the queue it ran on; then, over all full
-    periods from tick 10 on, the medians of the two distances that say which
+    periods from tick 10 on, the medians of the three distances that say which
     chain bounds the step."""
     db = sqlite3.connect(path)
     cur = db.cursor()
@@ -115,7 +117,7 @@ def timeline(path, tick_no, title=""):
         xs = sorted(xs)
         return xs[len(xs) // 2] if xs else float("nan")
 
-    per, next_fm, head_after_sort, merge_len = [], [], [], []
+    per, next_fm, head_after_sort, merge_len, host_part = [], [], [], [], []
     for t in range(10, len(starts) - 1):
         p = period(t)
         names = [r[0] for r in p[:-1]]
@@ -129,21 +131,28 @@ def timeline(path, tick_no, title=""):
         copies = [r for r in p[:-1] if r[0] == "rocclr:copyBuffer"]
         if not merge or not copies:
             continue
-        head = [r for r in copies if r[1] >= merge[0][2]]
+        # the head copy follows the fold on the fold's own queue
+        head = [r for r in copies
+                if r[1] >= merge[0][2] and r[3] == merge[0][3]]
         if not head:
             continue
         per.append((p[-1][1] - p[0][1]) / 1e3)
         next_fm.append((p[-1][1] - tail[2]) / 1e3)
         head_after_sort.append((head[0][2] - sort[2]) / 1e3)
         merge_len.append((merge[0][2] - merge[0][1]) / 1e3)
+        host_part.append((p[-1][1] - head[0][2]) / 1e3)
     lines.append("")
     lines.append(f"medians over {len(per)} periods (tick 10 on):")
     lines.append(f"  period, flatmap(t) begin -> flatmap(t+1) begin  "
                  f"{med(per):7.2f} us")
     lines.append(f"  tail(t) end -> flatmap(t+1) begin               "
                  f"{med(next_fm):7.2f} us")
+    lines.append(f"    (flatmap(t+1) began before tail(t) ended in "
+                 f"{sum(x < 0 for x in next_fm)} of {len(next_fm)} periods)")
     lines.append(f"  sort end -> head copy end (fold/merge + copy)   "
                  f"{med(head_after_sort):7.2f} us")
+    lines.append(f"  head copy end -> flatmap(t+1) begin (host part) "
+                 f"{med(host_part):7.2f} us")
     lines.append(f"  accumulator fold / merge kernel                 "
                  f"{med(merge_len):7.2f} us")
     return "\n".join(lines)
