@@ -936,6 +936,193 @@ extern "C" dbsp_status dbsp_join(dbsp_ctx *c, const dbsp_batch *delta,
     return DBSP_OK;
 }
 
+// the spine of a test-facing join: every batch keeps its slot, empty or not
+static dbsp_status trace_verbatim(const dbsp_batch *batches, int n,
+                                  TraceArgs &t) {
+    if (n < 0 || n > MAX_TRACE_BATCHES || (n > 0 && !batches))
+        return DBSP_ERR_INVALID;
+    t = TraceArgs{};
+    for (int i = 0; i < n; i++) {
+        if (batches[i].len < 0) return DBSP_ERR_INVALID;
+        trace_push(t, as_batch(&batches[i]));
+    }
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_join_spine(dbsp_ctx *c, const dbsp_batch *delta,
+                                       const dbsp_batch *trace_batches,
+                                       int n_batches, dbsp_proj proj,
+                                       uint64_t param, int path,
+                                       dbsp_batch *out) {
+    const DevBatch d = as_batch(delta);
+    TraceArgs t;
+    TRY(trace_verbatim(trace_batches, n_batches, t));
+    if (d.n < 0 || (path != 1 && path != 2)) return DBSP_ERR_INVALID;
+    if (path == 2 && d.n > 8192) return DBSP_ERR_INVALID;
+    DevBatch res;
+    if (path == 1 || t.nb == 0) {
+        TRY(dbspk::join_spine_rows(c->stream, d, t, proj, param, &res));
+        TRY(dbsp_ctx_sync(c));
+        put_batch(out, res);
+        return DBSP_OK;
+    }
+    // the small route, chained as agg_linear_spine chains it
+    uint32_t *cnts = nullptr;
+    uint64_t *offsets = nullptr;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&cnts,
+                                     (size_t)d.n * t.nb * 4 + 8, c->stream));
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&offsets, (size_t)(d.n + 1) * 8,
+                                     c->stream));
+    JoinCountArgs jca{};
+    jca.np = 1;
+    jca.dk[0] = d.k;
+    jca.nd[0] = d.n;
+    jca.t[0] = t;
+    jca.cnts[0] = cnts;
+    jca.offsets[0] = offsets;
+    jca.d_total = c->d_len + LEN_OP;
+    dbsp_status st = dbspk::join_count_scan_batch(c->stream, jca);
+    if (st == DBSP_OK) st = read_len(c, LEN_OP, 1);
+    int64_t total = 0;
+    if (st == DBSP_OK) st = checked_len(c, LEN_OP, total);
+    if (st == DBSP_OK && total > 0) {
+        st = alloc_batch(c, total, res);
+        if (st == DBSP_OK)
+            st = dbspk::join_emit_prepared(c->stream, d, t, cnts, offsets,
+                                           total, proj, param, res);
+    }
+    (void)dbspk::cache_free(cnts, c->stream);
+    (void)dbspk::cache_free(offsets, c->stream);
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    if (st != DBSP_OK) {
+        free_batch(c, res);
+        return st;
+    }
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_join_tail(dbsp_ctx *c, const dbsp_join_plan *plans,
+                                      int np, int64_t cap, int64_t *verdict,
+                                      uint64_t *const *offsets_host,
+                                      dbsp_batch *out) {
+    if (np < 1 || np > 3 || cap < 8192 || !plans || !verdict || !offsets_host)
+        return DBSP_ERR_INVALID;
+    // device length slots: [0..2] nd, [3..5] tn, [6..8] totals, [9] d_total,
+    // [10] d_flag, [11] d_final
+    enum { S_ND = 0, S_TN = 3, S_TOT = 6, S_TOTAL = 9, S_FLAG = 10,
+           S_FINAL = 11, S_N = 12 };
+    int64_t h[S_N] = {};
+    JoinCountArgs jca{};
+    JoinTailArgs ta{};
+    jca.np = ta.np = np;
+    for (int p = 0; p < np; p++) {
+        const dbsp_join_plan &pl = plans[p];
+        if (pl.delta.len < 0 || pl.n_batches < 1) return DBSP_ERR_INVALID;
+        TRY(trace_verbatim(pl.trace_batches, pl.n_batches, jca.t[p]));
+        // a length the kernels accept must lie inside the columns
+        if (pl.nd >= 0 && pl.nd <= 8192 && pl.nd > pl.delta.len)
+            return DBSP_ERR_INVALID;
+        if (pl.fresh) {
+            if (pl.n_batches != 1 || pl.tn > pl.trace_batches[0].len)
+                return DBSP_ERR_INVALID;
+            jca.t[p].n[0] = 0;  // read from the device, as a chained tick's
+        }
+        h[S_ND + p] = pl.nd;
+        h[S_TN + p] = pl.fresh ? pl.tn : 0;
+    }
+    int64_t *slots = nullptr;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&slots, S_N * 8, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(slots, h, S_N * 8, hipMemcpyHostToDevice,
+                                c->stream));
+    std::vector<void *> bufs{slots};
+    auto release = [&]() {
+        for (void *b : bufs) (void)dbspk::cache_free(b, c->stream);
+    };
+    dbsp_status st = DBSP_OK;
+    for (int p = 0; p < np && st == DBSP_OK; p++) {
+        const dbsp_join_plan &pl = plans[p];
+        const size_t n_cap = (size_t)pl.delta.len, nb = (size_t)pl.n_batches;
+        void *cn = nullptr, *of = nullptr, *sp = nullptr;
+        if (dbspk::cache_malloc(&cn, n_cap * nb * 4 + 8, c->stream) !=
+                hipSuccess ||
+            dbspk::cache_malloc(&of, (n_cap + 1) * 8, c->stream) !=
+                hipSuccess ||
+            dbspk::cache_malloc(&sp, n_cap * nb * 8 + 8, c->stream) !=
+                hipSuccess)
+            st = DBSP_ERR_OOM;
+        for (void *b : {cn, of, sp})
+            if (b) bufs.push_back(b);
+        jca.dk[p] = ta.dk[p] = pl.delta.k;
+        ta.dv[p] = pl.delta.v;
+        ta.dw[p] = pl.delta.w;
+        jca.nd[p] = 0;
+        jca.nd_dev[p] = ta.nd_dev[p] = slots + S_ND + p;
+        jca.tn_dev[p] = ta.tn_dev[p] = pl.fresh ? slots + S_TN + p : nullptr;
+        ta.t[p] = jca.t[p];
+        jca.cnts[p] = (uint32_t *)cn;
+        ta.cnts[p] = (const uint32_t *)cn;
+        jca.starts[p] = (int64_t *)sp;
+        ta.starts[p] = (const int64_t *)sp;
+        jca.offsets[p] = ta.offsets[p] = (uint64_t *)of;
+        ta.proj[p] = pl.proj;
+    }
+    DevBatch comb, scr, store;
+    if (st == DBSP_OK) st = alloc_batch(c, cap, comb);
+    if (st == DBSP_OK) st = alloc_batch(c, 8192, scr);
+    if (st == DBSP_OK) st = alloc_batch(c, 8192, store);
+    jca.d_total = slots + S_TOT;
+    ta.totals = slots + S_TOT;
+    ta.cap = cap;
+    ta.d_total = slots + S_TOTAL;
+    ta.d_flag = slots + S_FLAG;
+    ta.d_final = slots + S_FINAL;
+    ta.ek = comb.k; ta.ev = comb.v; ta.ew = comb.w;
+    ta.tk = scr.k; ta.tv = scr.v; ta.tw = scr.w;
+    ta.ok = store.k; ta.ov = store.v; ta.ow = store.w;
+    if (st == DBSP_OK) st = dbspk::join_probe_batch(c->stream, jca);
+    if (st == DBSP_OK) st = dbspk::join_tail_small(c->stream, ta);
+    if (st == DBSP_OK &&
+        hipMemcpyAsync(h, slots, S_N * 8, hipMemcpyDeviceToHost, c->stream) !=
+            hipSuccess)
+        st = DBSP_ERR_INTERNAL;
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    for (int p = 0; p < np && st == DBSP_OK; p++) {
+        if (h[S_TOT + p] < 0 || plans[p].nd <= 0) continue;
+        if (!offsets_host[p]) {
+            st = DBSP_ERR_INVALID;
+        } else if (hipMemcpyAsync(offsets_host[p], ta.offsets[p],
+                                  (size_t)plans[p].nd * 8,
+                                  hipMemcpyDeviceToHost,
+                                  c->stream) != hipSuccess) {
+            st = DBSP_ERR_INTERNAL;
+        }
+    }
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    free_batch(c, scr);
+    release();
+    DevBatch res;
+    if (st == DBSP_OK) {
+        for (int i = 0; i < 3; i++) verdict[i] = i < np ? h[S_TOT + i] : 0;
+        verdict[3] = h[S_TOTAL];
+        verdict[4] = h[S_FLAG];
+        verdict[5] = h[S_FINAL];
+        if (h[S_FINAL] >= 0 && h[S_FINAL] <= 8192) {
+            std::swap(res, store);
+            res.n = h[S_FINAL];
+        } else if (h[S_FINAL] < 0 && h[S_FLAG] == 0 && h[S_TOTAL] >= 0 &&
+                   h[S_TOTAL] <= cap) {
+            std::swap(res, comb);
+            res.n = h[S_TOTAL];
+        }
+    }
+    free_batch(c, comb);
+    free_batch(c, store);
+    if (st != DBSP_OK) return st;
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
 // Radix-tree rolling aggregate primitive (operator/time_series/radix_tree/
 // + rolling_aggregate.rs:235-280): per input row
 // (partition, ts, w) of a consolidated (partition, time)-sorted batch, the

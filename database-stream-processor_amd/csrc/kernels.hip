@@ -1472,7 +1472,7 @@ __device__ inline bool proj_out(int proj, uint64_t param, uint64_t k,
                                 uint64_t &lo) {
     switch (proj) {
         case DBSP_PROJ_Q4_BID_X_AUC: {
-            // delta = bid (v1 = bid_dt<<20 | price), trace = auction
+            // delta = bid (v1 = bid_dt<<27 | price), trace = auction
             // (v2 = a_dt<<28 | (expires-a_dt)<<4 | category-10); emit
             // ((auction<<4)|cat, price) when the bid falls in the auction's
             // validity window (q4.rs:58-68)
@@ -1484,7 +1484,7 @@ __device__ inline bool proj_out(int proj, uint64_t param, uint64_t k,
         }
         case DBSP_PROJ_Q6_BID_X_AUC: {
             // q6.rs:60-80: delta = bid (v1 = bid_dt<<27|price), trace =
-            // auction (v2 = a_dt<<34 | (expires-a_dt)<<20 | seller); emit
+            // auction (v2 = a_dt<<36 | (expires-a_dt)<<20 | seller); emit
             // ((auction<<20)|seller, price) in the validity window
             const uint64_t bid_dt = v1 >> 27, price = v1 & 0x7FFFFFFull;
             const uint64_t a_dt = v2 >> 36, dur = (v2 >> 20) & 0xFFFFull;

@@ -290,6 +290,8 @@ __host__ __device__ static inline int acc_fold_wgs(int64_t na) {
 }
 dbsp_status acc_fold_batch(hipStream_t s, const MergeArgs &args, bool wf64);
 
+// The small-join scan and the tail sum matches in 32 bits, so a plan set's
+// combined matches must stay below 2^32.
 // the probe phase of a join over up to 3 plans (nd <= 8192 each): per-plan
 // per-row/per-batch cnts and, if asked, start positions; no scan
 dbsp_status join_probe_batch(hipStream_t s, const JoinCountArgs &args);

@@ -20,6 +20,13 @@ class BatchStruct(ctypes.Structure):
                 ("w", ctypes.c_void_p), ("len", ctypes.c_int64)]
 
 
+class JoinPlanStruct(ctypes.Structure):
+    _fields_ = [("delta", BatchStruct), ("nd", ctypes.c_int64),
+                ("trace_batches", ctypes.POINTER(BatchStruct)),
+                ("n_batches", ctypes.c_int), ("proj", ctypes.c_int),
+                ("fresh", ctypes.c_int), ("tn", ctypes.c_int64)]
+
+
 def _L():
     global _lib
     if _lib is None:
@@ -51,6 +58,17 @@ def _L():
         L.dbsp_join.argtypes = [vp, ctypes.POINTER(BatchStruct),
                                 ctypes.POINTER(BatchStruct), ctypes.c_int, u64,
                                 ctypes.POINTER(BatchStruct)]
+        L.dbsp_join_spine.restype = i32
+        L.dbsp_join_spine.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                      ctypes.POINTER(BatchStruct),
+                                      ctypes.c_int, ctypes.c_int, u64,
+                                      ctypes.c_int,
+                                      ctypes.POINTER(BatchStruct)]
+        L.dbsp_join_tail.restype = i32
+        L.dbsp_join_tail.argtypes = [vp, ctypes.POINTER(JoinPlanStruct),
+                                     ctypes.c_int, i64, ctypes.POINTER(i64),
+                                     ctypes.POINTER(vp),
+                                     ctypes.POINTER(BatchStruct)]
         L.dbsp_agg_linear_upsert.restype = i32
         L.dbsp_agg_linear_upsert.argtypes = [vp, vp, i64,
                                              ctypes.POINTER(BatchStruct),
@@ -294,6 +312,81 @@ class Ctx:
         for x in (d, t, out):
             self.free_batch(x)
         return res
+
+    def join_spine(self, delta_rows, batches, proj, param=0,
+                   path=1) -> np.ndarray:
+        """delta x spine, the raw rows in the order the kernel wrote them.
+        `batches` (at most 24, each sorted by (k, v)) reach the kernels
+        verbatim, empty ones included.  path 1: the sized count / scan / emit
+        route; path 2: the small route (probe, one-workgroup scan, emit over
+        prepared counts), at most 8192 delta rows."""
+        d = self.upload_rows(delta_rows)
+        ups = [self.upload_rows(b) for b in batches]
+        arr = (BatchStruct * max(len(ups), 1))(*ups)
+        out = BatchStruct()
+        try:
+            _check(self._lib.dbsp_join_spine(self._h, ctypes.byref(d), arr,
+                                             len(ups), proj, param, path,
+                                             ctypes.byref(out)), "join_spine")
+            res = self.download_rows(out)
+        finally:
+            for x in [d, out] + ups:
+                self.free_batch(x)
+        return res
+
+    def join_tail(self, plans, cap=32768) -> dict:
+        """The chained tick's probe + join tail over 1..3 plans.  A plan is a
+        dict: "delta" (rows), "batches" (list of rows), "proj", and optionally
+        "nd" (the delta length handed to the kernels in place of
+        len(delta); negative and oversized ones are passed on), "fresh"
+        (the one-batch trace is a tick-fresh delta) and "tn" (its length as
+        the kernels see it).  Returns the verdicts "totals", "d_total",
+        "d_flag", "d_final", "offsets" (per plan: the plan-local exclusive
+        offsets, None where the total is negative), "store" (the output
+        store's rows when d_final >= 0, else None) and "capbuf" (the capacity
+        buffer's rows when only they are valid, else None)."""
+        np_ = len(plans)
+        arr = (JoinPlanStruct * max(np_, 1))()
+        keep, offs = [], []
+        for p, pl in enumerate(plans):
+            d = self.upload_rows(pl["delta"])
+            ups = [self.upload_rows(b) for b in pl["batches"]]
+            tb = (BatchStruct * max(len(ups), 1))(*ups)
+            keep.append((d, ups, tb))
+            nd = pl.get("nd")
+            arr[p].delta = d
+            arr[p].nd = d.len if nd is None else nd
+            arr[p].trace_batches = tb
+            arr[p].n_batches = len(ups)
+            arr[p].proj = pl["proj"]
+            arr[p].fresh = 1 if pl.get("fresh") else 0
+            tn = pl.get("tn")
+            arr[p].tn = (ups[0].len if ups else 0) if tn is None else tn
+            offs.append(np.zeros(max(d.len, 1), dtype=np.uint64))
+        optr = (ctypes.c_void_p * max(np_, 1))(*[_p(o) for o in offs])
+        verdict = (ctypes.c_int64 * 6)()
+        out = BatchStruct()
+        try:
+            _check(self._lib.dbsp_join_tail(self._h, arr, np_, cap, verdict,
+                                            optr, ctypes.byref(out)),
+                   "join_tail")
+            rows = self.download_rows(out)
+        finally:
+            for d, ups, _ in keep:
+                for x in [d] + ups:
+                    self.free_batch(x)
+            self.free_batch(out)
+        totals = [int(verdict[p]) for p in range(np_)]
+        d_total, d_flag, d_final = (int(verdict[i]) for i in (3, 4, 5))
+        return {
+            "totals": totals, "d_total": d_total, "d_flag": d_flag,
+            "d_final": d_final,
+            "offsets": [offs[p][:max(int(arr[p].nd), 0)].copy()
+                        if totals[p] >= 0 else None for p in range(np_)],
+            "store": rows if d_final >= 0 else None,
+            "capbuf": rows if d_final < 0 and d_flag == 0 and d_total >= 0
+            else None,
+        }
 
     def agg_linear_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
         keys = np.ascontiguousarray(keys, dtype=np.uint64)

@@ -83,25 +83,31 @@ typedef struct {
 typedef enum {
     DBSP_PROJ_HI_V2_LO_V1    = 0, /* q3: delta=auction_by_seller, trace=person_by_id */
     DBSP_PROJ_HI_V1_LO_V2    = 1, /* q3 swapped side */
-    DBSP_PROJ_HI_K_LO_V1V2   = 2, /* generic pair join (reference join.rs:886 tests): lo=v1<<32|v2 */
+    DBSP_PROJ_HI_K_LO_V1V2   = 2, /* generic pair join (reference join.rs:886 tests):
+                                     lo = v1<<32 | (v2 & lo32); vals are 32-bit */
     DBSP_PROJ_HI_K_LO_V1RND  = 3, /* q8: lo = (v1 & hi32) | round_down(v1 & lo32, param) */
     DBSP_PROJ_HI_K_LO_V2RND  = 4, /* q8 swapped side */
     DBSP_PROJ_HI_V2_LO_K     = 5, /* q5 final join */
     DBSP_PROJ_HI_V1_LO_K     = 6, /* q5 final join swapped side */
-    DBSP_PROJ_HI_K_LO_V2V1   = 7, /* generic pair join, swapped side: lo=v2<<32|v1 */
+    DBSP_PROJ_HI_K_LO_V2V1   = 7, /* generic pair join, swapped side:
+                                     lo = v2<<32 | (v1 & lo32) */
     DBSP_PROJ_HI_K_LO_V2     = 8, /* (k, v2): keeps the join key, takes the trace val
                                      (full 64-bit; the C5 join -> f64-sum pipeline) */
     DBSP_PROJ_Q4_BID_X_AUC   = 9, /* q4.rs:58-68 join_func: delta=bid
-                                     (v=bid_dt<<20|price), trace=auction
+                                     (v=bid_dt<<27|price), trace=auction
                                      (v=a_dt<<28|(expires-a_dt)<<4|(cat&0xF)):
                                      emit ((auction<<4)|cat, price) iff
                                      a_dt <= bid_dt <= expires, else weight 0
-                                     (dropped by the consolidate) */
+                                     (dropped by the consolidate).  Fields:
+                                     price 27 bits, expires-a_dt 24, cat 4;
+                                     auction<<4 keeps its low 64 bits */
     DBSP_PROJ_Q4_AUC_X_BID   = 10, /* q4 swapped side */
     DBSP_PROJ_Q6_BID_X_AUC   = 11, /* q6.rs:60-80: delta=bid, trace=auction
                                       (v=a_dt<<36|(expires-a_dt)<<20|seller):
                                       emit ((auction<<20)|seller, price) in
-                                      the validity window, else weight 0 */
+                                      the validity window, else weight 0.
+                                      Fields: expires-a_dt 16 bits, seller 20;
+                                      the bid packs as for q4 */
     DBSP_PROJ_Q6_AUC_X_BID   = 12, /* q6 swapped side */
 } dbsp_proj;
 
@@ -167,6 +173,52 @@ dbsp_status dbsp_acc_fold(dbsp_ctx *ctx, const dbsp_batch *acc,
 dbsp_status dbsp_join(dbsp_ctx *ctx, const dbsp_batch *delta,
                       const dbsp_batch *trace, dbsp_proj proj, uint64_t param,
                       dbsp_batch *out_raw);
+
+/* dbsp_join against a whole spine, by the kernels the engine's ticks run.
+ * trace_batches: n_batches (0..24) batches, each sorted by (k, v); they reach
+ * the kernels verbatim, an empty batch keeping its slot.  path 1: the sized
+ * count / scan / emit route (any delta length).  path 2: the small route, a
+ * block probe, a one-workgroup scan and the emit over prepared counts, as the
+ * linear aggregate's retractions chain them; a delta above 8192 rows is
+ * DBSP_ERR_INVALID.  out_raw holds the raw rows in the order the emit wrote
+ * them: delta row major, then batch, then trace position; an invalid q4 / q6
+ * pair keeps its slot with weight 0.  Synchronous. */
+dbsp_status dbsp_join_spine(dbsp_ctx *ctx, const dbsp_batch *delta,
+                            const dbsp_batch *trace_batches, int n_batches,
+                            dbsp_proj proj, uint64_t param, int path,
+                            dbsp_batch *out_raw);
+
+/* One plan of the chained join tail: delta x trace under proj (param 0).
+ * delta.len is the rows its columns hold (the capacity); nd is the length
+ * handed to the kernels through a device length slot, verbatim, so a negative
+ * one or one above 8192 is passed on (a length in 0..8192 above delta.len is
+ * DBSP_ERR_INVALID: it would be read).  fresh != 0 marks a one-batch trace
+ * that is itself a tick-fresh delta: its length tn then travels through a
+ * device slot too (tn above trace_batches[0].len is DBSP_ERR_INVALID). */
+typedef struct {
+    dbsp_batch delta;
+    int64_t nd;
+    const dbsp_batch *trace_batches;
+    int n_batches;  /* 1..24 */
+    dbsp_proj proj;
+    int fresh;
+    int64_t tn;
+} dbsp_join_plan;
+
+/* The chained tick's join tail over 1..3 plans: the probe that keeps the run
+ * starts, then the one-workgroup tail (scan, capacity check, emit into a
+ * capacity buffer of cap >= 8192 rows, sort + consolidate through an
+ * 8192-row scratch into an 8192-row output store).  Synchronous.
+ * verdict (host, 6 words): totals[0..2] (-1: that plan read a poisoned
+ * length; unused plans 0), then d_total, d_flag, d_final as the kernel left
+ * them.  offsets_host[p] (host, plans[p].nd words) receives plan p's
+ * plan-local exclusive offsets when totals[p] >= 0.  out (device, caller
+ * frees): the output store's first d_final rows when d_final >= 0; else the
+ * capacity buffer's first d_total rows when d_flag == 0 and d_total >= 0;
+ * else empty. */
+dbsp_status dbsp_join_tail(dbsp_ctx *ctx, const dbsp_join_plan *plans, int np,
+                           int64_t cap, int64_t *verdict,
+                           uint64_t *const *offsets_host, dbsp_batch *out);
 
 /* Linear aggregate + upsert for the aggregate_linear path.
  * Replaces AggregateIncremental::eval_key with the WeightedCount aggregator
