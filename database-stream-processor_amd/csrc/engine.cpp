@@ -1169,6 +1169,61 @@ extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
     return DBSP_OK;
 }
 
+extern "C" dbsp_status dbsp_agg_last10_upsert(dbsp_ctx *c,
+                                              const uint64_t *delta_keys,
+                                              int64_t nd,
+                                              const dbsp_batch *in_trace,
+                                              const dbsp_batch *out_trace,
+                                              dbsp_batch *out) {
+    DevBatch res;
+    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LAST10, delta_keys, nd,
+                               as_batch(in_trace), as_batch(out_trace), &res));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+// the insert half of agg_linear_spine on its own: unique keys, one
+// accumulator summed batch by batch, the ticket-ordered emit
+extern "C" dbsp_status dbsp_agg_sum_spine(dbsp_ctx *c, const dbsp_batch *delta,
+                                          const dbsp_batch *in_batches,
+                                          int n_batches, uint64_t **out_keys,
+                                          int64_t *n_keys, dbsp_batch *out) {
+    TraceArgs t;
+    TRY(trace_verbatim(in_batches, n_batches, t));
+    if (delta->len < 0 || !out_keys || !n_keys) return DBSP_ERR_INVALID;
+    uint64_t *keys = nullptr;
+    int64_t nk = 0;
+    TRY(dbspk::unique_keys(c->stream, delta->k, delta->len, &keys, &nk));
+    *out_keys = keys;
+    *n_keys = nk;
+    if (nk == 0) {
+        put_batch(out, DevBatch{});
+        return dbsp_ctx_sync(c);
+    }
+    int64_t *acc = nullptr;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
+    HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
+    DevBatch ins;
+    dbsp_status st = DBSP_OK;
+    for (int b = 0; b < t.nb && st == DBSP_OK; b++)
+        st = dbspk::agg_sum_batch(c->stream, keys, nk,
+                                  as_batch(&in_batches[b]), acc, false);
+    if (st == DBSP_OK) st = alloc_batch(c, nk, ins);
+    if (st == DBSP_OK)
+        st = dbspk::emit_nonzero(c->stream, keys, acc, nk, false, &ins);
+    (void)dbspk::cache_free(acc, c->stream);
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    if (st != DBSP_OK) {
+        free_batch(c, ins);
+        (void)dbspk::cache_free(keys, c->stream);
+        *out_keys = nullptr;
+        *n_keys = 0;
+        return st;
+    }
+    put_batch(out, ins);
+    return DBSP_OK;
+}
+
 extern "C" dbsp_status dbsp_shard_partition(dbsp_ctx *c, const dbsp_batch *in,
                                             int nshards, dbsp_batch *out,
                                             int64_t *offsets_host) {
@@ -2282,6 +2337,163 @@ extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
         TRY(window_emit(c, w, res, /*transient=*/false));
     }
     put_batch(out, res.empty() ? DevBatch{} : res[0]);
+    return DBSP_OK;
+}
+
+// ---- test-facing: the watermark kernel and the window pair over a spine ----
+
+// scratch device words of one watermark update: the state, the bounds, the
+// device length and the reduced maximum
+enum { WM_STATE = 0, WM_BOUNDS = 4, WM_N = 10, WM_GMAX = 11, WM_WORDS = 12 };
+
+// upload state / bounds / length / maximum, run k_wm_update from `source`,
+// leave everything in dev (no sync, nothing read back)
+static dbsp_status wm_update_scratch(dbsp_ctx *c, unsigned long long *dev,
+                                     uint64_t *h, const uint64_t state[4],
+                                     const uint64_t bounds[6], int source,
+                                     const uint64_t *ak, int64_t n,
+                                     uint64_t gmax, uint64_t width,
+                                     uint64_t tumble, uint64_t lag) {
+    for (int i = 0; i < 4; i++) h[WM_STATE + i] = state[i];
+    for (int i = 0; i < 6; i++) h[WM_BOUNDS + i] = bounds[i];
+    h[WM_N] = (uint64_t)n;
+    h[WM_GMAX] = gmax;
+    HIP_CHECK_ST(hipMemcpyAsync(dev, h, WM_WORDS * 8, hipMemcpyHostToDevice,
+                                c->stream));
+    WmSource src{ak, 0, nullptr, nullptr};
+    if (source == DBSP_WM_HOST_N) src.n = n;
+    else src.n_dev = (const int64_t *)(dev + WM_N);
+    if (source == DBSP_WM_GMAX) src.gmax_dev = dev + WM_GMAX;
+    return dbspk::wm_update(c->stream, src, width, tumble, lag,
+                            dev + WM_STATE, dev + WM_BOUNDS);
+}
+
+extern "C" dbsp_status dbsp_wm_update(dbsp_ctx *c, uint64_t *state,
+                                      uint64_t *bounds, int source,
+                                      const uint64_t *ak, int64_t ak_len,
+                                      int64_t n, uint64_t gmax, uint64_t width,
+                                      uint64_t tumble, uint64_t lag) {
+    if (!state || !bounds || tumble == 0 || ak_len < 0 || n > ak_len ||
+        (ak_len > 0 && !ak) || source < DBSP_WM_HOST_N ||
+        source > DBSP_WM_GMAX)
+        return DBSP_ERR_INVALID;
+    unsigned long long *dev = nullptr;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&dev, WM_WORDS * 8, c->stream));
+    uint64_t h[WM_WORDS];
+    dbsp_status st = wm_update_scratch(c, dev, h, state, bounds, source, ak, n,
+                                       gmax, width, tumble, lag);
+    if (st == DBSP_OK &&
+        hipMemcpyAsync(h, dev, WM_WORDS * 8, hipMemcpyDeviceToHost,
+                       c->stream) != hipSuccess)
+        st = DBSP_ERR_INTERNAL;
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    (void)dbspk::cache_free(dev, c->stream);
+    if (st != DBSP_OK) return st;
+    for (int i = 0; i < 4; i++) state[i] = h[WM_STATE + i];
+    for (int i = 0; i < 6; i++) bounds[i] = h[WM_BOUNDS + i];
+    return DBSP_OK;
+}
+
+// a region table the emit may follow: every region inside its source, the
+// offsets the running sum of the lengths, the total their sum
+static bool window_table_ok(const int64_t *tb, int nreg, const TraceArgs &t,
+                            int64_t bcap, int64_t total) {
+    int64_t acc = 0;
+    for (int r = 0; r < nreg; r++) {
+        const int64_t src = tb[r * 5], lo = tb[r * 5 + 1], len = tb[r * 5 + 2];
+        if (src != (r < 3 * t.nb ? r / 3 : -1)) return false;
+        const int64_t n = src < 0 ? bcap : t.n[src];
+        if (lo < 0 || len < 0 || lo > n || len > n - lo) return false;
+        if (tb[r * 5 + 3] != 1 && tb[r * 5 + 3] != -1) return false;
+        if (tb[r * 5 + 4] != acc) return false;
+        acc += len;
+    }
+    return acc == total;
+}
+
+extern "C" dbsp_status dbsp_window_spine(dbsp_ctx *c,
+                                         const dbsp_batch *trace_batches,
+                                         int n_batches, const dbsp_batch *batch,
+                                         int route, uint64_t *bounds,
+                                         dbsp_window_chain *chain,
+                                         int64_t *total, int64_t *table_host,
+                                         dbsp_batch *out) {
+    TraceArgs t;
+    TRY(trace_verbatim(trace_batches, n_batches, t));
+    const DevBatch b = as_batch(batch);
+    if (b.n < 0 || !bounds || !total || !table_host ||
+        (route != 1 && route != 2))
+        return DBSP_ERR_INVALID;
+    if (route == 2 &&
+        (!chain || chain->tumble == 0 || chain->wm_n > b.n || chain->bn > b.n))
+        return DBSP_ERR_INVALID;
+    const int nreg = 3 * t.nb + 1;
+    int64_t *table = nullptr;
+    unsigned long long *dev = nullptr;
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&table,
+                                     (size_t)nreg * 5 * 8 + 8, c->stream));
+    HIP_CHECK_ST(dbspk::cache_malloc((void **)&dev, (WM_WORDS + 1) * 8,
+                                     c->stream));
+    int64_t *d_bn = (int64_t *)(dev + WM_WORDS);
+    uint64_t h[WM_WORDS];
+    dbsp_status st = DBSP_OK;
+    if (route == 1) {
+        st = dbspk::window_ranges_multi(c->stream, t, b.k, b.n,
+                                        bounds[4] != 0, bounds[0], bounds[1],
+                                        bounds[2], bounds[3], table,
+                                        c->d_len + L_WIN);
+    } else {
+        const uint64_t none[6] = {};
+        if (hipMemcpyAsync(d_bn, &chain->bn, 8, hipMemcpyHostToDevice,
+                           c->stream) != hipSuccess)
+            st = DBSP_ERR_INTERNAL;
+        if (st == DBSP_OK)
+            st = wm_update_scratch(c, dev, h, chain->state, none,
+                                   DBSP_WM_DEV_N, b.k, chain->wm_n, 0,
+                                   chain->width, chain->tumble, chain->lag);
+        // the host length stays 0, as in a chained tick
+        if (st == DBSP_OK)
+            st = dbspk::window_ranges_chain(c->stream, t, b.k, 0, d_bn,
+                                            dev + WM_BOUNDS, table,
+                                            c->d_len + L_WIN);
+        if (st == DBSP_OK &&
+            hipMemcpyAsync(h, dev, WM_WORDS * 8, hipMemcpyDeviceToHost,
+                           c->stream) != hipSuccess)
+            st = DBSP_ERR_INTERNAL;
+    }
+    if (st == DBSP_OK) st = read_len(c, L_WIN, 1);
+    DevBatch res;
+    if (st == DBSP_OK) {
+        *total = c->h_len[L_WIN];
+        if (route == 2) {
+            for (int i = 0; i < 4; i++) chain->state[i] = h[WM_STATE + i];
+            for (int i = 0; i < 6; i++) bounds[i] = h[WM_BOUNDS + i];
+        }
+    }
+    if (st == DBSP_OK && *total >= 0) {
+        if (hipMemcpyAsync(table_host, table, (size_t)nreg * 5 * 8,
+                           hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            st = DBSP_ERR_INTERNAL;
+        if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+        // the emit reads where the table points: follow it only when it
+        // stays inside the batches
+        if (st == DBSP_OK && !window_table_ok(table_host, nreg, t, b.n, *total))
+            st = DBSP_ERR_INTERNAL;
+        if (st == DBSP_OK && *total > 0) {
+            st = alloc_batch(c, *total, res);
+            if (st == DBSP_OK)
+                st = dbspk::window_emit_multi(c->stream, t, b, table, nreg,
+                                              *total, res);
+        }
+    }
+    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
+    (void)dbspk::cache_free(table, c->stream);
+    (void)dbspk::cache_free(dev, c->stream);
+    if (st != DBSP_OK) {
+        free_batch(c, res);
+        return st;
+    }
+    put_batch(out, res);
     return DBSP_OK;
 }
 

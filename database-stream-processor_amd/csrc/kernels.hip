@@ -2618,8 +2618,9 @@ __global__ void k_distinct_count(const uint64_t *dk, const uint64_t *dv,
 
 // MODE: 0 = linear weight-sum (WeightedCount, aggregate/mod.rs:129-156),
 // 1 = Max (max.rs:36-55), 2 = q6's fold: average of the last <= 10 vals in
-// the key's run (queries/q6.rs:96-110 VecDeque fold in cursor order; the
-// price lives in the low 20 bits of the val)
+// the key's run (queries/q6.rs:96-110 VecDeque fold in cursor order, every
+// val of non-zero weight counting whatever its sign, fold.rs:87; the price
+// lives in the low 27 bits of the val)
 template <int MODE>
 __global__ void k_agg_count(const uint64_t *keys, int64_t nd,
                             const uint64_t *ik, const int64_t *iw, int64_t ni,

@@ -27,6 +27,15 @@ class JoinPlanStruct(ctypes.Structure):
                 ("fresh", ctypes.c_int), ("tn", ctypes.c_int64)]
 
 
+class WindowChainStruct(ctypes.Structure):
+    _fields_ = [("state", ctypes.c_uint64 * 4), ("wm_n", ctypes.c_int64),
+                ("bn", ctypes.c_int64), ("width", ctypes.c_uint64),
+                ("tumble", ctypes.c_uint64), ("lag", ctypes.c_uint64)]
+
+
+WM_SOURCES = {"host_n": 0, "dev_n": 1, "gmax": 2}  # dbsp_wm_source
+
+
 def _L():
     global _lib
     if _lib is None:
@@ -76,6 +85,27 @@ def _L():
                                              ctypes.POINTER(BatchStruct)]
         L.dbsp_agg_max_upsert.restype = i32
         L.dbsp_agg_max_upsert.argtypes = L.dbsp_agg_linear_upsert.argtypes
+        L.dbsp_agg_last10_upsert.restype = i32
+        L.dbsp_agg_last10_upsert.argtypes = L.dbsp_agg_linear_upsert.argtypes
+        L.dbsp_agg_sum_spine.restype = i32
+        L.dbsp_agg_sum_spine.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                         ctypes.POINTER(BatchStruct),
+                                         ctypes.c_int, ctypes.POINTER(vp),
+                                         ctypes.POINTER(i64),
+                                         ctypes.POINTER(BatchStruct)]
+        L.dbsp_wm_update.restype = i32
+        L.dbsp_wm_update.argtypes = [vp, ctypes.POINTER(u64),
+                                     ctypes.POINTER(u64), ctypes.c_int, vp,
+                                     i64, i64, u64, u64, u64, u64]
+        L.dbsp_window_spine.restype = i32
+        L.dbsp_window_spine.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                        ctypes.c_int,
+                                        ctypes.POINTER(BatchStruct),
+                                        ctypes.c_int, ctypes.POINTER(u64),
+                                        ctypes.POINTER(WindowChainStruct),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(BatchStruct)]
         L.dbsp_window.restype = i32
         L.dbsp_window.argtypes = [vp, ctypes.POINTER(BatchStruct),
                                   ctypes.POINTER(BatchStruct), ctypes.c_int,
@@ -427,6 +457,134 @@ class Ctx:
         self._lib.dbsp_dev_free(self._h, dk)
         for x in (it, ot, out):
             self.free_batch(x)
+        return res
+
+    def agg_last10_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
+        """q6's fold + upsert: per key the floor average of the last <= 10
+        prices (low 27 bits of v) of its run in in_rows, then the key's
+        out_rows negated; raw rows in kernel order."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        dk = ctypes.c_void_p()
+        _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
+                                        ctypes.byref(dk)), "alloc")
+        if len(keys):
+            _check(self._lib.dbsp_h2d(self._h, dk, _p(keys), len(keys) * 8), "h2d")
+        it = self.upload_rows(in_rows)
+        ot = self.upload_rows(out_rows)
+        out = BatchStruct()
+        try:
+            _check(self._lib.dbsp_agg_last10_upsert(self._h, dk, len(keys),
+                                                    ctypes.byref(it),
+                                                    ctypes.byref(ot),
+                                                    ctypes.byref(out)),
+                   "agglast10")
+            self.sync()
+            res = self.download_rows(out)
+        finally:
+            self._lib.dbsp_dev_free(self._h, dk)
+            for x in (it, ot, out):
+                self.free_batch(x)
+        return res
+
+    def agg_sum_spine(self, delta_rows, batches):
+        """(unique keys of the consolidated delta, emitted rows): per-key
+        weight sums over `batches` (at most 24, passed verbatim), one row
+        (key, sum, +1) per non-zero sum, in ticket order."""
+        d = self.upload_rows(delta_rows)
+        ups = [self.upload_rows(b) for b in batches]
+        arr = (BatchStruct * max(len(ups), 1))(*ups)
+        out = BatchStruct()
+        dk = ctypes.c_void_p()
+        nk = ctypes.c_int64()
+        try:
+            _check(self._lib.dbsp_agg_sum_spine(self._h, ctypes.byref(d), arr,
+                                                len(ups), ctypes.byref(dk),
+                                                ctypes.byref(nk),
+                                                ctypes.byref(out)),
+                   "agg_sum_spine")
+            keys = np.empty(nk.value, dtype=np.uint64)
+            if nk.value:
+                _check(self._lib.dbsp_d2h(self._h, _p(keys), dk,
+                                          nk.value * 8), "d2h")
+            res = self.download_rows(out)
+        finally:
+            if dk:
+                self._lib.dbsp_dev_free(self._h, dk)
+            for x in [d, out] + ups:
+                self.free_batch(x)
+        return keys, res
+
+    def wm_update(self, state, source, keys=(), n=None, gmax=0, width=1,
+                  tumble=1, lag=0, bounds=None):
+        """One k_wm_update step on scratch words.  state: {wm, s0, e0,
+        have_prev}; source: "host_n", "dev_n" or "gmax"; keys: the sorted time
+        keys uploaded, n the length the kernel sees (default len(keys));
+        bounds: the 6 words the kernel finds (default zeros).  Returns
+        (state after, bounds after) as lists of ints."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        st = (ctypes.c_uint64 * 4)(*[int(x) for x in state])
+        bd = (ctypes.c_uint64 * 6)(*[int(x) for x in (bounds or [0] * 6)])
+        dk = ctypes.c_void_p()
+        _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
+                                        ctypes.byref(dk)), "alloc")
+        try:
+            if len(keys):
+                _check(self._lib.dbsp_h2d(self._h, dk, _p(keys),
+                                          len(keys) * 8), "h2d")
+            _check(self._lib.dbsp_wm_update(
+                self._h, st, bd, WM_SOURCES[source], dk, len(keys),
+                len(keys) if n is None else n, gmax, width, tumble, lag),
+                "wm_update")
+        finally:
+            self._lib.dbsp_dev_free(self._h, dk)
+        return [int(x) for x in st], [int(x) for x in bd]
+
+    def window_spine(self, batches, tick_rows, bounds=None, chain=None):
+        """The window stage over a spine (at most 24 batches, passed
+        verbatim).  Route 1: bounds = (s0, e0, s1, e1, have_prev), handed to
+        the ranges kernel by value.  Route 2: chain = dict(state, width,
+        tumble, lag, and optionally wm_n / bn: the tick batch's length as the
+        watermark / the ranges kernel reads it from the device, default
+        len(tick_rows)); the bounds come from k_wm_update on the device.
+        Returns dict(total, table (nreg x 5 int64, None for a -1 total), rows
+        (kernel order), bounds (6 words) and, on route 2, state)."""
+        ups = [self.upload_rows(b) for b in batches]
+        tick = self.upload_rows(tick_rows)
+        arr = (BatchStruct * max(len(ups), 1))(*ups)
+        nreg = 3 * len(ups) + 1
+        table = np.zeros((nreg, 5), dtype=np.int64)
+        bd = (ctypes.c_uint64 * 6)()
+        total = ctypes.c_int64()
+        out = BatchStruct()
+        ch = None
+        if chain is None:
+            for i, x in enumerate(bounds):
+                bd[i] = int(x)
+        else:
+            ch = WindowChainStruct()
+            for i, x in enumerate(chain["state"]):
+                ch.state[i] = int(x)
+            ch.wm_n = chain.get("wm_n", tick.len)
+            ch.bn = chain.get("bn", tick.len)
+            ch.width, ch.tumble, ch.lag = (chain["width"], chain["tumble"],
+                                           chain["lag"])
+        try:
+            _check(self._lib.dbsp_window_spine(
+                self._h, arr, len(ups), ctypes.byref(tick),
+                1 if chain is None else 2, bd,
+                None if ch is None else ctypes.byref(ch),
+                ctypes.byref(total),
+                table.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                ctypes.byref(out)), "window_spine")
+            rows = self.download_rows(out)
+        finally:
+            for x in [tick, out] + ups:
+                self.free_batch(x)
+        res = {"total": total.value,
+               "table": table if total.value >= 0 else None,
+               "rows": rows, "bounds": [int(x) for x in bd]}
+        if ch is not None:
+            res["state"] = [int(x) for x in ch.state]
         return res
 
     def window(self, trace_rows, batch_rows, have_prev, s0, e0, s1, e1):

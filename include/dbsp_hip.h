@@ -369,6 +369,84 @@ dbsp_status dbsp_agg_max_upsert(dbsp_ctx *ctx,
                                 const dbsp_batch *out_trace,
                                 dbsp_batch *out_raw);
 
+/* q6's fold + upsert (queries/q6.rs:97-110 over aggregate/fold.rs:76-96).
+ * Same contract as above; in_trace rows are (seller, auction<<27 | price).
+ * The new per-key value is the floor average of the prices (low 27 bits of
+ * the val) of the last <= 10 rows of the key's run; every row of a
+ * consolidated trace counts, whatever the sign of its weight. */
+dbsp_status dbsp_agg_last10_upsert(dbsp_ctx *ctx,
+                                   const uint64_t *delta_keys, int64_t nd,
+                                   const dbsp_batch *in_trace,
+                                   const dbsp_batch *out_trace,
+                                   dbsp_batch *out_raw);
+
+/* The insert half of the linear aggregate over a spine, as the q5 tick runs
+ * it: the distinct keys of the consolidated delta, per-key weight sums of
+ * in_batches (0..24, sorted by k, passed verbatim) added batch by batch into
+ * one zeroed accumulator, then (key, sum, +1) for every non-zero sum.
+ * out_keys (device, caller frees; null when the delta is empty) and n_keys
+ * receive the distinct keys; out_raw the emitted rows, in the order their
+ * tickets were drawn (undefined: compare as a set).  Synchronous. */
+dbsp_status dbsp_agg_sum_spine(dbsp_ctx *ctx, const dbsp_batch *delta,
+                               const dbsp_batch *in_batches, int n_batches,
+                               uint64_t **out_keys, int64_t *n_keys,
+                               dbsp_batch *out_raw);
+
+/* Where dbsp_wm_update's kernel takes the tick's max event time from: the
+ * last of the first n sorted keys with n passed by value, the same with n
+ * read from a device word, or an already reduced maximum (0 = none). */
+typedef enum {
+    DBSP_WM_HOST_N = 0,
+    DBSP_WM_DEV_N  = 1,
+    DBSP_WM_GMAX   = 2,
+} dbsp_wm_source;
+
+/* One step of the device watermark (queries/q5.rs:85-96, q8.rs:62-71) on
+ * scratch device words.  state (host, in/out): {wm, s0, e0, have_prev}.
+ * bounds (host, in/out): {s0, e0, s1, e1, have_prev, err}; what the caller
+ * puts in is what the kernel finds there.  ak: ak_len sorted device keys; n is
+ * the length the kernel sees (n > ak_len is DBSP_ERR_INVALID; a negative n
+ * sets err = 1 and leaves every other word as it was).  DBSP_WM_GMAX ignores
+ * ak and n and takes gmax.  wm = max(wm, max - lag) when the tick has a
+ * maximum (precondition max >= lag), rounded = wm - wm % tumble, the new
+ * window [rounded - width saturating at 0, rounded).  Synchronous. */
+dbsp_status dbsp_wm_update(dbsp_ctx *ctx, uint64_t *state, uint64_t *bounds,
+                           int source, const uint64_t *ak, int64_t ak_len,
+                           int64_t n, uint64_t gmax, uint64_t width,
+                           uint64_t tumble, uint64_t lag);
+
+/* Route 2 of dbsp_window_spine: the watermark step the window bounds come
+ * from.  state is in/out; wm_n is the tick batch's length as the watermark
+ * kernel sees it and bn as the ranges kernel sees it, both through device
+ * words (either above batch->len is DBSP_ERR_INVALID; negative ones are
+ * passed on). */
+typedef struct {
+    uint64_t state[4];
+    int64_t wm_n;
+    int64_t bn;
+    uint64_t width, tumble, lag;
+} dbsp_window_chain;
+
+/* The window stage over a whole spine, by the kernels the q5 / q8 ticks run.
+ * trace_batches: n_batches (0..24) batches sorted by k, passed verbatim, an
+ * empty batch keeping its three regions; batch: this tick's delta.
+ * route 1: k_window_ranges_multi with the host bounds {s0, e0, s1, e1,
+ * have_prev, -} (read).  route 2: k_wm_update on chain->state with the tick
+ * batch's keys as its source, then the ranges launch reading the bounds and
+ * the batch length from the device; bounds (written) receives what the
+ * watermark published.  total: the row total, or the -1 verdict of an err
+ * watermark or a negative bn (no table, no rows).  table_host receives the
+ * (3 * n_batches + 1) * 5 region words [src, lo, len, sign, goff], regions per
+ * batch in the order retract [s0, min(s1,e0)), shrink [e1, e0), insert
+ * [max(e0,s1), e1), the tick batch's [s1, e1) last.  out_raw: the emitted
+ * rows in table order.  A table that points outside its batches is
+ * DBSP_ERR_INTERNAL and nothing is emitted.  Synchronous. */
+dbsp_status dbsp_window_spine(dbsp_ctx *ctx, const dbsp_batch *trace_batches,
+                              int n_batches, const dbsp_batch *batch,
+                              int route, uint64_t *bounds,
+                              dbsp_window_chain *chain, int64_t *total,
+                              int64_t *table_host, dbsp_batch *out_raw);
+
 /* Window operator: 3-region retract/insert range scan over a time-keyed trace.
  * Replaces Window::eval (operator/time_series/window.rs:144-220).
  * trace = integral of the stream up to but NOT including this tick;

@@ -510,10 +510,12 @@ std::vector<Row> q6_step(Oracle &o, const std::vector<dbsp_event> &ev) {
         // per affected seller: avg of the last <= 10 vals' prices; then the
         // upsert against the output integral
         for (uint64_t key : keys) {
-            // gather the seller's current run
+            // gather the seller's current run: Fold::aggregate steps on
+            // every val whose weight is non-zero, whatever its sign
+            // (aggregate/fold.rs:83-93)
             std::vector<uint64_t> vals;
             for (auto &r : o.q6_fold_in)
-                if (r.k == key && r.w > 0) vals.push_back(r.v);
+                if (r.k == key && r.w != 0) vals.push_back(r.v);
             if (!vals.empty()) {
                 size_t n10 = vals.size() < 10 ? vals.size() : 10;
                 uint64_t sum = 0;
