@@ -266,6 +266,44 @@ static inline bool in_arena(dbsp_ctx *c, const void *p) {
     return c->arena && p >= c->arena && p < c->arena + c->arena_sz;
 }
 
+// Scratch owned for a scope: a stream-cache block goes back to the cache on
+// the ctx stream when the scope ends, whichever return ends it, so TRY is
+// safe around it; a block of the tick arena needs no free.
+struct ScratchBuf {
+    dbsp_ctx *c = nullptr;
+    void *p = nullptr;
+    bool cached = false;  // p is a cache_malloc block: ours to free
+    ScratchBuf() = default;
+    // adopt a block some kernel-interface call cache_malloc'd
+    ScratchBuf(dbsp_ctx *c_, void *block) : c(c_), p(block), cached(true) {}
+    ScratchBuf(const ScratchBuf &) = delete;
+    ScratchBuf &operator=(const ScratchBuf &) = delete;
+    ~ScratchBuf() { reset(); }
+    // arena_first: the tick arena, the stream cache only when that is full
+    dbsp_status alloc(dbsp_ctx *c_, size_t bytes, bool arena_first = false) {
+        reset();
+        c = c_;
+        if (arena_first) p = arena_alloc(c, bytes);
+        if (!p) {
+            HIP_CHECK_ST(dbspk::cache_malloc(&p, bytes, c->stream));
+            cached = true;
+        }
+        return DBSP_OK;
+    }
+    void reset() {
+        if (cached) (void)dbspk::cache_free(p, c->stream);
+        release();
+    }
+    // ownership passes out: the caller frees
+    void *release() {
+        void *r = p;
+        p = nullptr;
+        cached = false;
+        return r;
+    }
+    template <class T> T *as() const { return (T *)p; }
+};
+
 // Join on demand (q3 trains; the ordering argument above the q3 tick): put
 // the loop stream behind everything enqueued on the back stream so far.  The
 // back stream runs in order, so its last ev_tail covers all of it.  Called
@@ -493,6 +531,13 @@ static dbsp_status concat_batches(dbsp_ctx *c, const std::vector<DevBatch> &in,
     }
     out.n = total;
     return DBSP_OK;
+}
+
+// copy a batch (for inserting a delta into a spine while retaining it)
+static dbsp_status copy_batch(dbsp_ctx *c, const DevBatch &in, DevBatch &out) {
+    TRY(alloc_batch(c, in.n > 0 ? in.n : 1, out));
+    out.n = in.n;
+    return copy_cols(c, out, 0, in.k, in.v, in.w, in.n);
 }
 
 static inline void put_batch(dbsp_batch *out, const DevBatch &b) {
@@ -760,6 +805,13 @@ struct Spine {
         return DBSP_OK;
     }
 
+    // insert a copy: the caller retains b
+    dbsp_status insert_copy(dbsp_ctx *c, const DevBatch &b) {
+        DevBatch cpy;
+        TRY(copy_batch(c, b, cpy));
+        return insert(c, cpy);
+    }
+
     // exhaustive merge to a single batch (consolidate.rs:33-47 semantics)
     dbsp_status consolidate_all(dbsp_ctx *c) {
         while (batches.size() >= 2) {
@@ -865,6 +917,58 @@ struct RollingOp {
     }
 };
 
+// ---- pieces of the keyed-aggregate stage, shared with their test probes ----
+
+// The small join route (delta.n <= 8192): probe and single-workgroup scan,
+// the match total read back, then the emit over the prepared counts.  out
+// stays empty when nothing matches.
+static dbsp_status join_small(dbsp_ctx *c, const DevBatch &delta,
+                              const TraceArgs &t, int proj, uint64_t param,
+                              bool transient, DevBatch &out) {
+    ScratchBuf cnts, offsets;
+    TRY(cnts.alloc(c, (size_t)delta.n * t.nb * 4 + 8, transient));
+    TRY(offsets.alloc(c, (size_t)(delta.n + 1) * 8, transient));
+    JoinCountArgs jca{};
+    jca.np = 1;
+    jca.dk[0] = delta.k;
+    jca.nd[0] = delta.n;
+    jca.t[0] = t;
+    jca.cnts[0] = cnts.as<uint32_t>();
+    jca.offsets[0] = offsets.as<uint64_t>();
+    jca.d_total = c->d_len + LEN_OP;
+    TRY(dbspk::join_count_scan_batch(c->stream, jca));
+    TRY(read_len(c, LEN_OP, 1));
+    int64_t total = 0;
+    TRY(checked_len(c, LEN_OP, total));  // fused-barrier poison
+    if (total == 0) return DBSP_OK;
+    TRY(alloc_batch(c, total, out, transient));
+    dbsp_status st = dbspk::join_emit_prepared(
+        c->stream, delta, t, cnts.as<uint32_t>(), offsets.as<uint64_t>(),
+        total, proj, param, out);
+    if (st != DBSP_OK) free_batch(c, out);
+    return st;
+}
+
+// Per-key weight sums of keys[nk] across the nb batches, one accumulator
+// summed batch by batch (an empty batch keeps its turn), then the
+// ticket-ordered emit of (key, sum, +1) for the non-zero sums into ins.
+// wf64: f64 weights, the sums travel as bit patterns.
+static dbsp_status agg_sum_emit(dbsp_ctx *c, const uint64_t *keys, int64_t nk,
+                                const DevBatch *batches, int nb, bool wf64,
+                                bool transient, DevBatch &ins) {
+    ScratchBuf acc;
+    TRY(acc.alloc(c, nk * 8 + 8));
+    HIP_CHECK_ST(hipMemsetAsync(acc.p, 0, nk * 8, c->stream));
+    for (int b = 0; b < nb; b++)
+        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, batches[b],
+                                 acc.as<int64_t>(), wf64));
+    TRY(alloc_batch(c, nk, ins, transient));
+    dbsp_status st = dbspk::emit_nonzero(c->stream, keys, acc.as<int64_t>(),
+                                         nk, wf64, &ins);
+    if (st != DBSP_OK) free_batch(c, ins);
+    return st;
+}
+
 // ---------------------------------------------------------------------------
 // kernel-level C ABI (device-pointer primitives; used by GPU parity tests)
 // ---------------------------------------------------------------------------
@@ -960,44 +1064,11 @@ extern "C" dbsp_status dbsp_join_spine(dbsp_ctx *c, const dbsp_batch *delta,
     if (d.n < 0 || (path != 1 && path != 2)) return DBSP_ERR_INVALID;
     if (path == 2 && d.n > 8192) return DBSP_ERR_INVALID;
     DevBatch res;
-    if (path == 1 || t.nb == 0) {
+    if (path == 1 || t.nb == 0)
         TRY(dbspk::join_spine_rows(c->stream, d, t, proj, param, &res));
-        TRY(dbsp_ctx_sync(c));
-        put_batch(out, res);
-        return DBSP_OK;
-    }
-    // the small route, chained as agg_linear_spine chains it
-    uint32_t *cnts = nullptr;
-    uint64_t *offsets = nullptr;
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&cnts,
-                                     (size_t)d.n * t.nb * 4 + 8, c->stream));
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&offsets, (size_t)(d.n + 1) * 8,
-                                     c->stream));
-    JoinCountArgs jca{};
-    jca.np = 1;
-    jca.dk[0] = d.k;
-    jca.nd[0] = d.n;
-    jca.t[0] = t;
-    jca.cnts[0] = cnts;
-    jca.offsets[0] = offsets;
-    jca.d_total = c->d_len + LEN_OP;
-    dbsp_status st = dbspk::join_count_scan_batch(c->stream, jca);
-    if (st == DBSP_OK) st = read_len(c, LEN_OP, 1);
-    int64_t total = 0;
-    if (st == DBSP_OK) st = checked_len(c, LEN_OP, total);
-    if (st == DBSP_OK && total > 0) {
-        st = alloc_batch(c, total, res);
-        if (st == DBSP_OK)
-            st = dbspk::join_emit_prepared(c->stream, d, t, cnts, offsets,
-                                           total, proj, param, res);
-    }
-    (void)dbspk::cache_free(cnts, c->stream);
-    (void)dbspk::cache_free(offsets, c->stream);
-    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
-    if (st != DBSP_OK) {
-        free_batch(c, res);
-        return st;
-    }
+    else
+        TRY(join_small(c, d, t, proj, param, /*transient=*/false, res));
+    TRY(dbsp_ctx_sync(c));
     put_batch(out, res);
     return DBSP_OK;
 }
@@ -1143,17 +1214,25 @@ extern "C" dbsp_status dbsp_rolling_agg(dbsp_ctx *c, const dbsp_batch *in,
     return DBSP_OK;
 }
 
+static dbsp_status agg_upsert(dbsp_ctx *c, dbspk::AggMode mode,
+                              const uint64_t *delta_keys, int64_t nd,
+                              const dbsp_batch *in_trace,
+                              const dbsp_batch *out_trace, dbsp_batch *out) {
+    DevBatch res;
+    TRY(dbspk::agg_upsert_rows(c->stream, mode, delta_keys, nd,
+                               as_batch(in_trace), as_batch(out_trace), &res));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
 extern "C" dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *c,
                                               const uint64_t *delta_keys,
                                               int64_t nd,
                                               const dbsp_batch *in_trace,
                                               const dbsp_batch *out_trace,
                                               dbsp_batch *out) {
-    DevBatch res;
-    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LINEAR, delta_keys, nd,
-                               as_batch(in_trace), as_batch(out_trace), &res));
-    put_batch(out, res);
-    return DBSP_OK;
+    return agg_upsert(c, dbspk::AGG_LINEAR, delta_keys, nd, in_trace,
+                      out_trace, out);
 }
 
 extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
@@ -1162,11 +1241,8 @@ extern "C" dbsp_status dbsp_agg_max_upsert(dbsp_ctx *c,
                                            const dbsp_batch *in_trace,
                                            const dbsp_batch *out_trace,
                                            dbsp_batch *out) {
-    DevBatch res;
-    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_MAX, delta_keys, nd,
-                               as_batch(in_trace), as_batch(out_trace), &res));
-    put_batch(out, res);
-    return DBSP_OK;
+    return agg_upsert(c, dbspk::AGG_MAX, delta_keys, nd, in_trace, out_trace,
+                      out);
 }
 
 extern "C" dbsp_status dbsp_agg_last10_upsert(dbsp_ctx *c,
@@ -1175,15 +1251,12 @@ extern "C" dbsp_status dbsp_agg_last10_upsert(dbsp_ctx *c,
                                               const dbsp_batch *in_trace,
                                               const dbsp_batch *out_trace,
                                               dbsp_batch *out) {
-    DevBatch res;
-    TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LAST10, delta_keys, nd,
-                               as_batch(in_trace), as_batch(out_trace), &res));
-    put_batch(out, res);
-    return DBSP_OK;
+    return agg_upsert(c, dbspk::AGG_LAST10, delta_keys, nd, in_trace,
+                      out_trace, out);
 }
 
-// the insert half of agg_linear_spine on its own: unique keys, one
-// accumulator summed batch by batch, the ticket-ordered emit
+// the insert half of agg_linear_spine on its own; the unique keys go to the
+// caller, who frees them
 extern "C" dbsp_status dbsp_agg_sum_spine(dbsp_ctx *c, const dbsp_batch *delta,
                                           const dbsp_batch *in_batches,
                                           int n_batches, uint64_t **out_keys,
@@ -1191,35 +1264,23 @@ extern "C" dbsp_status dbsp_agg_sum_spine(dbsp_ctx *c, const dbsp_batch *delta,
     TraceArgs t;
     TRY(trace_verbatim(in_batches, n_batches, t));
     if (delta->len < 0 || !out_keys || !n_keys) return DBSP_ERR_INVALID;
-    uint64_t *keys = nullptr;
+    *out_keys = nullptr;
+    *n_keys = 0;
+    uint64_t *k = nullptr;
     int64_t nk = 0;
-    TRY(dbspk::unique_keys(c->stream, delta->k, delta->len, &keys, &nk));
-    *out_keys = keys;
-    *n_keys = nk;
-    if (nk == 0) {
-        put_batch(out, DevBatch{});
-        return dbsp_ctx_sync(c);
-    }
-    int64_t *acc = nullptr;
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
-    HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
+    TRY(dbspk::unique_keys(c->stream, delta->k, delta->len, &k, &nk));
+    ScratchBuf keys(c, k);
     DevBatch ins;
-    dbsp_status st = DBSP_OK;
-    for (int b = 0; b < t.nb && st == DBSP_OK; b++)
-        st = dbspk::agg_sum_batch(c->stream, keys, nk,
-                                  as_batch(&in_batches[b]), acc, false);
-    if (st == DBSP_OK) st = alloc_batch(c, nk, ins);
-    if (st == DBSP_OK)
-        st = dbspk::emit_nonzero(c->stream, keys, acc, nk, false, &ins);
-    (void)dbspk::cache_free(acc, c->stream);
-    if (st == DBSP_OK) st = dbsp_ctx_sync(c);
-    if (st != DBSP_OK) {
-        free_batch(c, ins);
-        (void)dbspk::cache_free(keys, c->stream);
-        *out_keys = nullptr;
-        *n_keys = 0;
-        return st;
+    if (nk > 0) {
+        std::vector<DevBatch> batches;
+        for (int b = 0; b < n_batches; b++)
+            batches.push_back(as_batch(&in_batches[b]));
+        TRY(agg_sum_emit(c, k, nk, batches.data(), n_batches, false,
+                         /*transient=*/false, ins));
     }
+    TRY(dbsp_ctx_sync(c));
+    *out_keys = (uint64_t *)keys.release();
+    *n_keys = nk;
     put_batch(out, ins);
     return DBSP_OK;
 }
@@ -1306,15 +1367,10 @@ extern "C" dbsp_status dbsp_agg_linear_upsert_f64(dbsp_ctx *c,
         put_batch(out, DevBatch{});
         return DBSP_OK;
     }
-    int64_t *acc;  // f64 sums as bit patterns
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nd * 8 + 8, c->stream));
-    HIP_CHECK_ST(hipMemsetAsync(acc, 0, nd * 8, c->stream));
-    TRY(dbspk::agg_sum_batch(c->stream, delta_keys, nd, as_batch(in_trace), acc,
-                             true));
+    const DevBatch in = as_batch(in_trace);
     DevBatch ins;
-    TRY(alloc_batch(c, nd, ins, true));
-    TRY(dbspk::emit_nonzero(c->stream, delta_keys, acc, nd, true, &ins));
-    HIP_CHECK_ST(dbspk::cache_free(acc, c->stream));
+    TRY(agg_sum_emit(c, delta_keys, nd, &in, 1, /*wf64=*/true,
+                     /*transient=*/true, ins));
     // retractions against the (i64-weighted) output trace
     DevBatch retr;
     TRY(dbspk::agg_upsert_rows(c->stream, dbspk::AGG_LINEAR, delta_keys, nd,
@@ -1551,6 +1607,13 @@ static void q3_train_drop(dbsp_ctx *c, Q3Train &T) {
     free_batch(c, T.res[1]);
 }
 
+// the winning-bid front q4 and q6 share: auctions ⋈ bids, Max per auction
+struct WinningBids {
+    Spine a_int, b_int;  // auction / bid traces (keyed by auction)
+    Spine maxin_sp;      // max input integral (affected-key gather)
+    DevBatch maxout;     // consolidated max output integral
+};
+
 struct dbsp_engine {
     dbsp_ctx *ctx = nullptr;
     int query = 0;
@@ -1578,15 +1641,13 @@ struct dbsp_engine {
     // q5 state
     Spine bt_int, wb_int, counts_int, bc_int;
     DevBatch maxin_int, maxout_int, maxz_int;
-    // q4 state (queries/q4.rs: join + per-auction Max + per-category Average)
-    Spine q4_a_int, q4_b_int;      // auction / bid traces (keyed by auction)
-    Spine q4_maxin_sp;             // max input integral (affected-key gather)
-    DevBatch q4_maxout;            // consolidated max output integral
+    // q4 and q6 state: the winning bids (an engine runs one query), then
+    // q4's per-category Average (queries/q4.rs) ...
+    WinningBids win;
     Spine q4_avg_int, q4_avgout;   // packed (sum<<20|count) integral + output
-    // q6 state (queries/q6.rs: join + per-(auction,seller) Max + per-seller
-    // last-10 average fold)
-    Spine q6_a_int, q6_b_int, q6_maxin_sp, q6_fold_sp;
-    DevBatch q6_maxout, q6_foldout;
+    // ... and q6's per-seller last-10 average fold (queries/q6.rs)
+    Spine q6_fold_sp;
+    DevBatch q6_foldout;
     // C5 state (query 100; BASELINE configs[4]: 1B-row indexed trace x
     // 10M-row delta incremental join + f64 sum aggregate)
     Spine c5_trace;   // (k, f64-bits val, +1 i64) join-side trace
@@ -1682,13 +1743,11 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
     for (Spine *s : {&e->a_int, &e->p_int, &e->pt_int, &e->at_int, &e->wp_int,
                      &e->wa_int, &e->bt_int, &e->wb_int, &e->counts_int,
                      &e->bc_int, &e->c5_trace, &e->c5_wint, &e->c5_out,
-                     &e->q4_a_int, &e->q4_b_int, &e->q4_avg_int,
-                     &e->q4_avgout, &e->q4_maxin_sp, &e->q6_a_int,
-                     &e->q6_b_int, &e->q6_maxin_sp, &e->q6_fold_sp})
+                     &e->win.a_int, &e->win.b_int, &e->win.maxin_sp,
+                     &e->q4_avg_int, &e->q4_avgout, &e->q6_fold_sp})
         s->clear(c);
     e->roll.clear(c);
-    free_batch(c, e->q4_maxout);
-    free_batch(c, e->q6_maxout);
+    free_batch(c, e->win.maxout);
     free_batch(c, e->q6_foldout);
     free_batch(c, e->maxin_int);
     free_batch(c, e->maxout_int);
@@ -2267,8 +2326,7 @@ struct WindowLeg {
     // filled by window_launch
     TraceArgs ta{};
     int nreg = 0;
-    int64_t *table = nullptr;
-    bool table_cached = false;  // arena exhausted: freed after the emit
+    ScratchBuf table;  // let go after the emit
 };
 
 // plan each leg (once: a second launch, after a re-sort, reuses the spine
@@ -2276,22 +2334,19 @@ struct WindowLeg {
 static dbsp_status window_launch(dbsp_engine *e, WindowLeg *legs, int n) {
     dbsp_ctx *c = e->ctx;
     for (WindowLeg *w = legs; w < legs + n; w++) {
-        if (w->table) continue;
+        if (w->table.p) continue;
         TRY(w->trace->cap_batches(c));
         w->ta = trace_args_of(*w->trace);
         w->nreg = 3 * w->ta.nb + 1;
-        const size_t bytes = (size_t)w->nreg * 5 * 8 + 8;
-        w->table = (int64_t *)arena_alloc(c, bytes);
-        w->table_cached = !w->table;
-        if (w->table_cached)
-            HIP_CHECK_ST(dbspk::cache_malloc((void **)&w->table, bytes,
-                                             c->stream));
+        TRY(w->table.alloc(c, (size_t)w->nreg * 5 * 8 + 8,
+                           /*arena_first=*/true));
     }
     ScopedTimer t(c, 4, 0.0);
     for (WindowLeg *w = legs; w < legs + n; w++)
         TRY(dbspk::window_ranges_chain(c->stream, w->ta, w->delta->k,
                                        w->delta->n, w->n_dev, e->d_bounds,
-                                       w->table, c->d_len + w->slot));
+                                       w->table.as<int64_t>(),
+                                       c->d_len + w->slot));
     return DBSP_OK;
 }
 
@@ -2304,12 +2359,11 @@ static dbsp_status window_emit(dbsp_ctx *c, WindowLeg &w,
     if (total > 0) {
         DevBatch o;
         TRY(alloc_batch(c, total, o, transient));
-        TRY(dbspk::window_emit_multi(c->stream, w.ta, *w.delta, w.table,
-                                     w.nreg, total, o));
+        TRY(dbspk::window_emit_multi(c->stream, w.ta, *w.delta,
+                                     w.table.as<int64_t>(), w.nreg, total, o));
         raw.push_back(o);
     }
-    if (w.table_cached) HIP_CHECK_ST(dbspk::cache_free(w.table, c->stream));
-    w.table = nullptr;
+    w.table.reset();
     return DBSP_OK;
 }
 
@@ -2324,14 +2378,12 @@ extern "C" dbsp_status dbsp_window(dbsp_ctx *c, const dbsp_batch *trace,
     WindowLeg w{nullptr, &b, nullptr, L_WIN};
     w.ta = trace_args_one(as_batch(trace));
     w.nreg = 3 * w.ta.nb + 1;
-    w.table_cached = true;
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&w.table,
-                                     (size_t)w.nreg * 5 * 8 + 8, c->stream));
+    TRY(w.table.alloc(c, (size_t)w.nreg * 5 * 8 + 8));
     std::vector<DevBatch> res;
     {
         ScopedTimer t(c, 4, 0.0);
         TRY(dbspk::window_ranges_multi(c->stream, w.ta, b.k, b.n, have_prev,
-                                       s0, e0, s1, e1, w.table,
+                                       s0, e0, s1, e1, w.table.as<int64_t>(),
                                        c->d_len + w.slot));
         TRY(read_len(c, w.slot, 1));
         TRY(window_emit(c, w, res, /*transient=*/false));
@@ -2511,15 +2563,12 @@ static dbsp_status map_sorted(dbsp_ctx *c, const DevBatch &in, int mode,
     return DBSP_OK;
 }
 
-// copy a batch (for inserting a delta into a spine while retaining it)
-static dbsp_status copy_batch(dbsp_ctx *c, const DevBatch &in, DevBatch &out) {
-    TRY(alloc_batch(c, in.n > 0 ? in.n : 1, out));
-    out.n = in.n;
-    return copy_cols(c, out, 0, in.k, in.v, in.w, in.n);
-}
-
 // linear aggregate + upsert over spines (aggregate/mod.rs:479-547 +
-// upsert.rs:161-208; linear in both traces, so evaluated per spine batch)
+// upsert.rs:161-208; linear in both traces, so evaluated per spine batch).
+// in_trace's weight type is the sums': f64 sums (aggregate_linear's sum over
+// C5's weighted integral, aggregate/mod.rs:297-323) accumulate in batch
+// order, tolerance 2 ulp * depth.  The output trace is i64-weighted either
+// way.
 static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
                                     const Spine &in_trace, Spine &out_trace,
                                     DevBatch &out) {
@@ -2528,139 +2577,46 @@ static dbsp_status agg_linear_spine(dbsp_ctx *c, const DevBatch &delta,
         return DBSP_OK;
     }
     ScopedTimer timer(c, 3, 0.0);
-    uint64_t *keys = nullptr;
-    int64_t nk = 0;
-    TRY(dbspk::unique_keys(c->stream, delta.k, delta.n, &keys, &nk));
-    // per-key weight sums across in_trace batches
-    int64_t *acc;
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
-    HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
-    for (auto &b : in_trace.batches)
-        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, b, acc, false));
     std::vector<DevBatch> outs;
-    // inserts
-    DevBatch ins;
-    TRY(alloc_batch(c, nk, ins, true));
-    TRY(dbspk::emit_nonzero(c->stream, keys, acc, nk, false, &ins));
-    if (ins.n > 0) outs.push_back(ins);
-    // retractions ARE a join: probing the output trace with (key, _, -1) rows
-    // under proj (k, v2) emits exactly (key, old_val, -old_w) — the upsert
-    // contract (upsert.rs:180-195) — in one count/emit pair over the whole
-    // spine instead of a scan pipeline per batch.
-    if (!out_trace.batches.empty()) {
+    {
+        uint64_t *k = nullptr;
+        int64_t nk = 0;
+        TRY(dbspk::unique_keys(c->stream, delta.k, delta.n, &k, &nk));
+        ScratchBuf keys(c, k);
+        // inserts
+        DevBatch ins;
+        TRY(agg_sum_emit(c, k, nk, in_trace.batches.data(),
+                         (int)in_trace.batches.size(), in_trace.wf64,
+                         /*transient=*/true, ins));
+        if (ins.n > 0) outs.push_back(ins);
+        else free_batch(c, ins);
+        // retractions ARE a join: probing the output trace with (key, _, -1)
+        // rows under proj (k, v2) emits exactly (key, old_val, -old_w) — the
+        // upsert contract (upsert.rs:180-195) — in one count/emit pair over
+        // the whole spine instead of a scan pipeline per batch.
         TRY(out_trace.cap_batches(c));
         const TraceArgs t = trace_args_of(out_trace);
         if (t.nb > 0) {
             // synthetic delta columns: v = 0, w = -1
-            uint64_t *dv = (uint64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
-            int64_t *dw = (int64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
-            DevBatch tmp;
-            if (!dv || !dw) {
-                TRY(alloc_batch(c, nk, tmp));
-                dv = tmp.k;
-                dw = (int64_t *)tmp.v;
-            }
-            HIP_CHECK_ST(hipMemsetAsync(dv, 0, nk * 8, c->stream));
-            HIP_CHECK_ST(hipMemsetAsync(dw, 0xFF, nk * 8, c->stream));  // -1
-            if (nk <= 8192) {
-                uint32_t *cnts = (uint32_t *)arena_alloc(c, (size_t)nk * t.nb * 4 + 8);
-                uint64_t *offsets = (uint64_t *)arena_alloc(c, (size_t)(nk + 1) * 8);
-                DevBatch tmp2;
-                if (!cnts || !offsets) {
-                    TRY(alloc_batch(c, nk * (t.nb + 2), tmp2));
-                    cnts = (uint32_t *)tmp2.k;
-                    offsets = (uint64_t *)tmp2.v;
-                }
-                JoinCountArgs jca{};
-                jca.np = 1;
-                jca.dk[0] = keys;
-                jca.nd[0] = nk;
-                jca.t[0] = t;
-                jca.cnts[0] = cnts;
-                jca.offsets[0] = offsets;
-                jca.d_total = c->d_len + LEN_OP;
-                TRY(dbspk::join_count_scan_batch(c->stream, jca));
-                TRY(read_len(c, LEN_OP, 1));
-                int64_t total = c->h_len[LEN_OP];
-                if (total > 0) {
-                    DevBatch o;
-                    TRY(alloc_batch(c, total, o, true));
-                    TRY(dbspk::join_emit_prepared(
-                        c->stream, DevBatch{keys, dv, dw, nk}, t, cnts,
-                        offsets, total, DBSP_PROJ_HI_K_LO_V2, 0, o));
-                    outs.push_back(o);
-                }
-                free_batch(c, tmp2);
-            } else {
-                DevBatch o;
-                TRY(dbspk::join_spine_rows(c->stream,
-                                           DevBatch{keys, dv, dw, nk}, t,
-                                           DBSP_PROJ_HI_K_LO_V2, 0, &o));
-                if (o.n > 0) outs.push_back(o);
-                else free_batch(c, o);
-            }
-            free_batch(c, tmp);
-        }
-    }
-    HIP_CHECK_ST(dbspk::cache_free(acc, c->stream));
-    HIP_CHECK_ST(dbspk::cache_free(keys, c->stream));
-    TRY(finalize_raw(c, outs, out));
-    return DBSP_OK;
-}
-
-// f64 twin of agg_linear_spine: per-key f64 sums across the weighted-integral
-// spine (aggregate_linear's sum, aggregate/mod.rs:297-323; batch-order
-// accumulation, tolerance 2 ulp * depth), retractions against the
-// i64-weighted output trace exactly as the i64 path
-static dbsp_status agg_linear_spine_f64(dbsp_ctx *c, const DevBatch &delta,
-                                        const Spine &in_trace,
-                                        Spine &out_trace, DevBatch &out) {
-    if (delta.n == 0) {
-        out = DevBatch{};
-        return DBSP_OK;
-    }
-    ScopedTimer timer(c, 3, 0.0);
-    uint64_t *keys = nullptr;
-    int64_t nk = 0;
-    TRY(dbspk::unique_keys(c->stream, delta.k, delta.n, &keys, &nk));
-    int64_t *acc;  // f64 sums as bit patterns
-    HIP_CHECK_ST(dbspk::cache_malloc((void **)&acc, nk * 8 + 8, c->stream));
-    HIP_CHECK_ST(hipMemsetAsync(acc, 0, nk * 8, c->stream));
-    for (auto &b : in_trace.batches)
-        TRY(dbspk::agg_sum_batch(c->stream, keys, nk, b, acc, true));
-    std::vector<DevBatch> outs;
-    DevBatch ins;
-    TRY(alloc_batch(c, nk, ins, true));
-    TRY(dbspk::emit_nonzero(c->stream, keys, acc, nk, true, &ins));
-    if (ins.n > 0) outs.push_back(ins);
-    // retractions: probe the (i64-weighted) output trace with (key, _, -1)
-    // rows under proj (k, v2) — the upsert contract (upsert.rs:180-195)
-    if (!out_trace.batches.empty()) {
-        TRY(out_trace.cap_batches(c));
-        const TraceArgs t = trace_args_of(out_trace);
-        if (t.nb > 0) {
-            uint64_t *dv = (uint64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
-            int64_t *dw = (int64_t *)arena_alloc(c, (size_t)nk * 8 + 8);
-            DevBatch tmp;
-            if (!dv || !dw) {
-                TRY(alloc_batch(c, nk, tmp));
-                dv = tmp.k;
-                dw = (int64_t *)tmp.v;
-            }
-            HIP_CHECK_ST(hipMemsetAsync(dv, 0, nk * 8, c->stream));
-            HIP_CHECK_ST(hipMemsetAsync(dw, 0xFF, nk * 8, c->stream));  // -1
+            ScratchBuf dv, dw;
+            TRY(dv.alloc(c, (size_t)nk * 8 + 8, /*arena_first=*/true));
+            TRY(dw.alloc(c, (size_t)nk * 8 + 8, /*arena_first=*/true));
+            HIP_CHECK_ST(hipMemsetAsync(dv.p, 0, nk * 8, c->stream));
+            HIP_CHECK_ST(hipMemsetAsync(dw.p, 0xFF, nk * 8, c->stream));  // -1
+            const DevBatch probe{k, dv.as<uint64_t>(), dw.as<int64_t>(), nk};
+            // by size: q4's handful of categories against C5's millions of keys
             DevBatch o;
-            TRY(dbspk::join_spine_rows(c->stream, DevBatch{keys, dv, dw, nk}, t,
-                                       DBSP_PROJ_HI_K_LO_V2, 0, &o));
+            if (nk <= 8192)
+                TRY(join_small(c, probe, t, DBSP_PROJ_HI_K_LO_V2, 0,
+                               /*transient=*/true, o));
+            else
+                TRY(dbspk::join_spine_rows(c->stream, probe, t,
+                                           DBSP_PROJ_HI_K_LO_V2, 0, &o));
             if (o.n > 0) outs.push_back(o);
             else free_batch(c, o);
-            free_batch(c, tmp);
         }
     }
-    HIP_CHECK_ST(dbspk::cache_free(acc, c->stream));
-    HIP_CHECK_ST(dbspk::cache_free(keys, c->stream));
-    TRY(finalize_raw(c, outs, out));
-    return DBSP_OK;
+    return finalize_raw(c, outs, out);
 }
 
 static bool spine_needs_merge(Spine &s) {
@@ -2877,11 +2833,7 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     TRY(dbspk::roll_ranges(c->stream, delta, time_hi(), before, after, &rb,
                            &n_gather, &n_affected, &err));
     if (err) return DBSP_ERR_INVALID;
-    {
-        DevBatch cpy;
-        TRY(copy_batch(c, delta, cpy));
-        TRY(in_sp.insert(c, cpy));
-    }
+    TRY(in_sp.insert_copy(c, delta));
     TRY(in_sp.cap_batches(c));
     TRY(out_sp.cap_batches(c));
     // gather + consolidate the slice of the input integral
@@ -2915,11 +2867,7 @@ dbsp_status RollingOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
     }
     HIP_CHECK_ST(dbspk::cache_free(rb, c->stream));
     if (!parts.empty()) TRY(finalize_raw(c, parts, out));
-    if (out.n > 0) {
-        DevBatch cpy;
-        TRY(copy_batch(c, out, cpy));
-        TRY(out_sp.insert(c, cpy));
-    }
+    if (out.n > 0) TRY(out_sp.insert_copy(c, out));
     timer.bytes = 24.0 * (double)moved;  // rows gathered + rows emitted
     return DBSP_OK;
 }
@@ -4311,9 +4259,7 @@ static dbsp_status q5_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         dWB = t1;
     }
     // aggregate_linear: input trace includes this tick (trace.rs TraceAppend)
-    DevBatch wb_copy;
-    TRY(copy_batch(c, dWB, wb_copy));
-    TRY(e->wb_int.insert(c, wb_copy));
+    TRY(e->wb_int.insert_copy(c, dWB));
     DevBatch dCounts;
     TRY(agg_linear_spine(c, dWB, e->wb_int, e->counts_int, dCounts));
     free_batch(c, dWB);
@@ -4401,6 +4347,7 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
     uint64_t *keys = nullptr;
     int64_t nk = 0;
     TRY(dbspk::unique_keys(c->stream, delta.k, delta.n, &keys, &nk));
+    ScratchBuf keys_owner(c, keys);
     DevBatch kb;
     TRY(alloc_batch(c, nk, kb, true));
     HIP_CHECK_ST(hipMemcpyAsync(kb.k, keys, nk * 8, hipMemcpyDeviceToDevice,
@@ -4420,7 +4367,7 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
             nk, gathered, out_int, &raw));
     }
     free_batch(c, gathered);
-    HIP_CHECK_ST(dbspk::cache_free(keys, c->stream));
+    keys_owner.reset();
     TRY(sort_consolidate_batch(c, raw, dOut));
     if (dOut.n > 0) {
         DevBatch cpy, m;
@@ -4430,6 +4377,46 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
         free_batch(c, cpy);
         out_int = m;
     }
+    return DBSP_OK;
+}
+
+// the front q4 and q6 share: the tick's deltas, the winning-bid join under
+// the query's projection pair, and Max per auction with upsert retractions
+static dbsp_status winning_bids_front(dbsp_engine *e, int proj_bid_x_auc,
+                                      int proj_auc_x_bid,
+                                      const dbsp_event *d_ev, int64_t n,
+                                      DevBatch &dA, DevBatch &dB,
+                                      DevBatch &dWin) {
+    dbsp_ctx *c = e->ctx;
+    WinningBids &wb = e->win;
+    engine_free_output(e);
+    // auction / bid deltas, keyed by auction id
+    TRY(build_deltas(e, d_ev, n, dA, dB, true));
+    // bilinear expansion against PREVIOUS traces:
+    //   dB ⋈ A_prev + dA ⋈ B_prev + dA ⋈ dB   (join.rs:217-292)
+    std::vector<DevBatch> outs;
+    TRY(join_vs_spine(c, dB, wb.a_int, proj_bid_x_auc, 0, outs));
+    TRY(join_vs_spine(c, dA, wb.b_int, proj_auc_x_bid, 0, outs));
+    TRY(join_vs_batch(c, dA, dB, proj_auc_x_bid, 0, outs));
+    DevBatch dWinIn;
+    TRY(finalize_raw(c, outs, dWinIn));
+    dWin = DevBatch{};
+    if (dWinIn.n > 0) {
+        // max input lives in a SPINE (amortized log maintenance); the Max
+        // aggregator re-reads only the AFFECTED keys' value runs each tick
+        TRY(wb.maxin_sp.insert_copy(c, dWinIn));
+        TRY(agg_keyed_spine(e, dWinIn, wb.maxin_sp, wb.maxout, 1, dWin));
+    }
+    free_batch(c, dWinIn);
+    return DBSP_OK;
+}
+
+// the shared tail: TraceAppend both input deltas
+static dbsp_status winning_bids_tail(dbsp_engine *e, DevBatch dA, DevBatch dB) {
+    dbsp_ctx *c = e->ctx;
+    TRY(e->win.a_int.insert(c, dA));
+    TRY(e->win.b_int.insert(c, dB));
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
     return DBSP_OK;
 }
 
@@ -4448,27 +4435,9 @@ static dbsp_status agg_keyed_spine(dbsp_engine *e, const DevBatch &delta,
 
 static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
-    engine_free_output(e);
-    DevBatch dA, dB;  // auction / bid deltas, keyed by auction id
-    TRY(build_deltas(e, d_ev, n, dA, dB, true));
-    // bilinear expansion against PREVIOUS traces:
-    //   dB ⋈ A_prev + dA ⋈ B_prev + dA ⋈ dB   (join.rs:217-292)
-    std::vector<DevBatch> outs;
-    TRY(join_vs_spine(c, dB, e->q4_a_int, DBSP_PROJ_Q4_BID_X_AUC, 0, outs));
-    TRY(join_vs_spine(c, dA, e->q4_b_int, DBSP_PROJ_Q4_AUC_X_BID, 0, outs));
-    TRY(join_vs_batch(c, dA, dB, DBSP_PROJ_Q4_AUC_X_BID, 0, outs));
-    DevBatch dWinIn;
-    TRY(finalize_raw(c, outs, dWinIn));
-    DevBatch dWin{};
-    if (dWinIn.n > 0) {
-        // max input lives in a SPINE (amortized log maintenance); the Max
-        // aggregator re-reads only the AFFECTED keys' value runs each tick
-        DevBatch cpy;
-        TRY(copy_batch(c, dWinIn, cpy));
-        TRY(e->q4_maxin_sp.insert(c, cpy));
-        TRY(agg_keyed_spine(e, dWinIn, e->q4_maxin_sp, e->q4_maxout, 1, dWin));
-    }
-    free_batch(c, dWinIn);
+    DevBatch dA, dB, dWin;
+    TRY(winning_bids_front(e, DBSP_PROJ_Q4_BID_X_AUC, DBSP_PROJ_Q4_AUC_X_BID,
+                           d_ev, n, dA, dB, dWin));
     // average per category: weigh into the packed (sum<<20)+count weight,
     // aggregate linearly over the integral spine, upsert, divide at output
     if (dWin.n > 0) {
@@ -4478,17 +4447,13 @@ static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         TRY(sort_consolidate_batch(c, wraw, dAvgIn));
         free_batch(c, dWin);
         if (dAvgIn.n > 0) {
-            DevBatch cpy;
-            TRY(copy_batch(c, dAvgIn, cpy));
-            TRY(e->q4_avg_int.insert(c, cpy));
+            TRY(e->q4_avg_int.insert_copy(c, dAvgIn));
             DevBatch upd;
             TRY(agg_linear_spine(c, dAvgIn, e->q4_avg_int, e->q4_avgout,
                                  upd));
             free_batch(c, dAvgIn);
             if (upd.n > 0) {
-                DevBatch cpy2;
-                TRY(copy_batch(c, upd, cpy2));
-                TRY(e->q4_avgout.insert(c, cpy2));
+                TRY(e->q4_avgout.insert_copy(c, upd));
                 // output: divide the packed sums (two packed values can map
                 // to one average, so consolidate after the map)
                 TRY(map_sorted(c, upd, 6, e->output));
@@ -4498,11 +4463,7 @@ static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     } else {
         free_batch(c, dWin);
     }
-    // TraceAppend both input deltas
-    TRY(e->q4_a_int.insert(c, dA));
-    TRY(e->q4_b_int.insert(c, dB));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    return DBSP_OK;
+    return winning_bids_tail(e, dA, dB);
 }
 
 // ---------------------------------------------------------------------------
@@ -4515,23 +4476,9 @@ static dbsp_status q4_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
 
 static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     dbsp_ctx *c = e->ctx;
-    engine_free_output(e);
-    DevBatch dA, dB;
-    TRY(build_deltas(e, d_ev, n, dA, dB, true));
-    std::vector<DevBatch> outs;
-    TRY(join_vs_spine(c, dB, e->q6_a_int, DBSP_PROJ_Q6_BID_X_AUC, 0, outs));
-    TRY(join_vs_spine(c, dA, e->q6_b_int, DBSP_PROJ_Q6_AUC_X_BID, 0, outs));
-    TRY(join_vs_batch(c, dA, dB, DBSP_PROJ_Q6_AUC_X_BID, 0, outs));
-    DevBatch dWinIn;
-    TRY(finalize_raw(c, outs, dWinIn));
-    DevBatch dWin{};
-    if (dWinIn.n > 0) {
-        DevBatch cpy;
-        TRY(copy_batch(c, dWinIn, cpy));
-        TRY(e->q6_maxin_sp.insert(c, cpy));
-        TRY(agg_keyed_spine(e, dWinIn, e->q6_maxin_sp, e->q6_maxout, 1, dWin));
-    }
-    free_batch(c, dWinIn);
+    DevBatch dA, dB, dWin;
+    TRY(winning_bids_front(e, DBSP_PROJ_Q6_BID_X_AUC, DBSP_PROJ_Q6_AUC_X_BID,
+                           d_ev, n, dA, dB, dWin));
     if (dWin.n > 0) {
         // map_index (q6.rs:92-94): key by seller, val (auction<<27)|price
         DevBatch fraw, dFoldIn;
@@ -4540,9 +4487,7 @@ static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
         TRY(sort_consolidate_batch(c, fraw, dFoldIn));
         free_batch(c, dWin);
         if (dFoldIn.n > 0) {
-            DevBatch cpy;
-            TRY(copy_batch(c, dFoldIn, cpy));
-            TRY(e->q6_fold_sp.insert(c, cpy));
+            TRY(e->q6_fold_sp.insert_copy(c, dFoldIn));
             TRY(agg_keyed_spine(e, dFoldIn, e->q6_fold_sp, e->q6_foldout, 2,
                                 e->output));
         }
@@ -4550,10 +4495,7 @@ static dbsp_status q6_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
     } else {
         free_batch(c, dWin);
     }
-    TRY(e->q6_a_int.insert(c, dA));
-    TRY(e->q6_b_int.insert(c, dB));
-    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
-    return DBSP_OK;
+    return winning_bids_tail(e, dA, dB);
 }
 
 // ---------------------------------------------------------------------------
@@ -4639,22 +4581,12 @@ static dbsp_status c5_step(dbsp_engine *e, int64_t lo, int64_t hi) {
     // tick's weighted delta, which is inserted first) + upsert retractions
     DevBatch upd{};
     if (dwb.n > 0) {
-        DevBatch wcopy;
-        {
-            std::vector<DevBatch> one{dwb};
-            TRY(concat_batches(c, one, wcopy));
-        }
-        TRY(e->c5_wint.insert(c, wcopy));
-        TRY(agg_linear_spine_f64(c, dwb, e->c5_wint, e->c5_out, upd));
+        TRY(e->c5_wint.insert_copy(c, dwb));
+        TRY(agg_linear_spine(c, dwb, e->c5_wint, e->c5_out, upd));
         free_batch(c, dwb);
     }
     // 4. output delta + TraceAppend on the output trace
-    if (upd.n > 0) {
-        DevBatch ocopy;
-        std::vector<DevBatch> one{upd};
-        TRY(concat_batches(c, one, ocopy));
-        TRY(e->c5_out.insert(c, ocopy));
-    }
+    if (upd.n > 0) TRY(e->c5_out.insert_copy(c, upd));
     e->output = upd;
     e->output_is_store = false;
     // 5. TraceAppend the delta into the join trace

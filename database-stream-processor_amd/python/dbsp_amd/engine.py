@@ -418,51 +418,10 @@ class Ctx:
             else None,
         }
 
-    def agg_linear_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        dk = ctypes.c_void_p()
-        _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
-                                        ctypes.byref(dk)), "alloc")
-        if len(keys):
-            _check(self._lib.dbsp_h2d(self._h, dk, _p(keys), len(keys) * 8), "h2d")
-        it = self.upload_rows(in_rows)
-        ot = self.upload_rows(out_rows)
-        out = BatchStruct()
-        _check(self._lib.dbsp_agg_linear_upsert(self._h, dk, len(keys),
-                                                ctypes.byref(it),
-                                                ctypes.byref(ot),
-                                                ctypes.byref(out)), "agg")
-        self.sync()
-        res = self.download_rows(out)
-        self._lib.dbsp_dev_free(self._h, dk)
-        for x in (it, ot, out):
-            self.free_batch(x)
-        return res
-
-    def agg_max_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        dk = ctypes.c_void_p()
-        _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
-                                        ctypes.byref(dk)), "alloc")
-        if len(keys):
-            _check(self._lib.dbsp_h2d(self._h, dk, _p(keys), len(keys) * 8), "h2d")
-        it = self.upload_rows(in_rows)
-        ot = self.upload_rows(out_rows)
-        out = BatchStruct()
-        _check(self._lib.dbsp_agg_max_upsert(self._h, dk, len(keys),
-                                             ctypes.byref(it), ctypes.byref(ot),
-                                             ctypes.byref(out)), "aggmax")
-        self.sync()
-        res = self.download_rows(out)
-        self._lib.dbsp_dev_free(self._h, dk)
-        for x in (it, ot, out):
-            self.free_batch(x)
-        return res
-
-    def agg_last10_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
-        """q6's fold + upsert: per key the floor average of the last <= 10
-        prices (low 27 bits of v) of its run in in_rows, then the key's
-        out_rows negated; raw rows in kernel order."""
+    def _agg_upsert(self, fn, what, keys, in_rows, out_rows) -> np.ndarray:
+        """Upload the keys and both traces, run one dbsp_agg_*_upsert entry
+        point (`fn`), download its rows; the device buffers go back even when
+        the call raises."""
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         dk = ctypes.c_void_p()
         _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
@@ -473,11 +432,8 @@ class Ctx:
         ot = self.upload_rows(out_rows)
         out = BatchStruct()
         try:
-            _check(self._lib.dbsp_agg_last10_upsert(self._h, dk, len(keys),
-                                                    ctypes.byref(it),
-                                                    ctypes.byref(ot),
-                                                    ctypes.byref(out)),
-                   "agglast10")
+            _check(fn(self._h, dk, len(keys), ctypes.byref(it),
+                      ctypes.byref(ot), ctypes.byref(out)), what)
             self.sync()
             res = self.download_rows(out)
         finally:
@@ -485,6 +441,21 @@ class Ctx:
             for x in (it, ot, out):
                 self.free_batch(x)
         return res
+
+    def agg_linear_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
+        return self._agg_upsert(self._lib.dbsp_agg_linear_upsert, "agg",
+                                keys, in_rows, out_rows)
+
+    def agg_max_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
+        return self._agg_upsert(self._lib.dbsp_agg_max_upsert, "aggmax",
+                                keys, in_rows, out_rows)
+
+    def agg_last10_upsert(self, keys, in_rows, out_rows) -> np.ndarray:
+        """q6's fold + upsert: per key the floor average of the last <= 10
+        prices (low 27 bits of v) of its run in in_rows, then the key's
+        out_rows negated; raw rows in kernel order."""
+        return self._agg_upsert(self._lib.dbsp_agg_last10_upsert, "agglast10",
+                                keys, in_rows, out_rows)
 
     def agg_sum_spine(self, delta_rows, batches):
         """(unique keys of the consolidated delta, emitted rows): per-key
@@ -636,25 +607,8 @@ class Ctx:
         return res
 
     def agg_linear_upsert_f64(self, keys, in_rows, out_rows) -> np.ndarray:
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        dk = ctypes.c_void_p()
-        _check(self._lib.dbsp_dev_alloc(self._h, max(len(keys), 1) * 8,
-                                        ctypes.byref(dk)), "alloc")
-        if len(keys):
-            _check(self._lib.dbsp_h2d(self._h, dk, _p(keys), len(keys) * 8), "h2d")
-        it = self.upload_rows(in_rows)
-        ot = self.upload_rows(out_rows)
-        out = BatchStruct()
-        _check(self._lib.dbsp_agg_linear_upsert_f64(self._h, dk, len(keys),
-                                                    ctypes.byref(it),
-                                                    ctypes.byref(ot),
-                                                    ctypes.byref(out)), "aggf64")
-        self.sync()
-        res = self.download_rows(out)
-        self._lib.dbsp_dev_free(self._h, dk)
-        for x in (it, ot, out):
-            self.free_batch(x)
-        return res
+        return self._agg_upsert(self._lib.dbsp_agg_linear_upsert_f64, "aggf64",
+                                keys, in_rows, out_rows)
 
     def distinct_inc(self, delta_rows, trace_batch_rows_list):
         d = self.upload_rows(delta_rows)

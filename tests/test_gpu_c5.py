@@ -46,9 +46,10 @@ def c5_gen(n, stride, jitter, seed, val_mode):
     return out
 
 
-def c5_oracle_tick(trace, wint, out_trace, delta):
+def c5_oracle_tick(trace, wint, out_trace, delta, key_counts=None):
     """One C5 tick on the CPU oracle; returns (new wint, new out_trace,
-    output delta)."""
+    output delta).  key_counts, if given, collects the tick's affected-key
+    count."""
     # caps sized for this workload (1 val/key: <= 1 match per delta row;
     # join_raw's default cap is delta*trace — petabytes at C5 scale)
     joined = oracle.join_raw(delta, trace, 8, cap=4 * len(delta) + 1024)
@@ -58,6 +59,8 @@ def c5_oracle_tick(trace, wint, out_trace, delta):
     dwb = oracle.consolidate_f64(weighed)
     wint = oracle.merge_f64(wint, dwb) if len(wint) else dwb
     keys = np.unique(dwb["k"])
+    if key_counts is not None:
+        key_counts.append(len(keys))
     upd = oracle.agg_linear_upsert_f64(keys, wint, out_trace,
                                        cap=4 * len(keys) + 1024)
     upd = oracle.consolidate(upd)
@@ -66,9 +69,11 @@ def c5_oracle_tick(trace, wint, out_trace, delta):
     return wint, out_trace, upd
 
 
-def test_c5_engine_parity():
+def run_c5_parity(n_trace, n_delta, steps, seed=41):
+    """Engine vs oracle over `steps` ticks; returns the affected-key count of
+    every tick."""
     from dbsp_amd.engine import Ctx, Engine
-    n_trace, n_delta, steps, seed = 200_000, 20_000, 6, 41
+    key_counts = []
     ctx = Ctx(0)
     eng = Engine(ctx, query=100)
     eng.c5_init(n_trace, n_delta, seed=seed)
@@ -82,7 +87,8 @@ def test_c5_engine_parity():
         got = eng.output()
         dseed = (seed + 0x9E3779B97F4A7C15 * (t + 1)) % (1 << 64)
         delta = c5_gen(n_delta, stride, stride - 1, dseed, 1)
-        wint, out_trace, exp = c5_oracle_tick(trace, wint, out_trace, delta)
+        wint, out_trace, exp = c5_oracle_tick(trace, wint, out_trace, delta,
+                                              key_counts)
         # structure (keys, vals-as-bits partition, weights): compare as f64
         # z-sets with tolerance on the aggregate bit patterns
         g = {(int(r["k"]), int(r["w"])): np.int64(r["v"]).view(np.float64)
@@ -96,6 +102,37 @@ def test_c5_engine_parity():
         trace = oracle.merge(trace, delta)
     eng.close()
     ctx.close()
+    return key_counts
+
+
+def test_c5_engine_parity():
+    run_c5_parity(200_000, 20_000, steps=6)
+
+
+# the linear aggregate picks its retraction join by the tick's affected-key
+# count: the small probe / one-workgroup scan / emit route up to 8192 keys,
+# the sized count / scan / emit route above
+SMALL_ROUTE_MAX = 8192
+
+
+@pytest.mark.parametrize("n_trace,n_delta,small", [
+    (20_000, 2_000, True),
+    (600_000, 60_000, False),
+])
+def test_c5_engine_parity_routes(n_trace, n_delta, small):
+    """Parity on each side of the retraction-route threshold, three ticks
+    each, same oracle tick and tolerance as test_c5_engine_parity.  About
+    one delta row in five meets the trace.  Affected keys per tick
+    (np.unique of the oracle's weighted delta, seed 41): 20_000 x 2_000 ->
+    399, 448, 411 (small route); 600_000 x 60_000 -> 12299, 12167, 12246
+    (sized route; 400_000 x 40_000 gives 8291, 8198, 8123 and would
+    straddle).  test_c5_engine_parity's own 200_000 x 20_000 gives about
+    4100 and takes the small route.  The first tick has no output trace,
+    so nothing to retract; the later two retract 7 and 16 rows (small) and
+    241 and 484 rows (sized)."""
+    counts = run_c5_parity(n_trace, n_delta, steps=3)
+    assert len(counts) == 3
+    assert all((nk <= SMALL_ROUTE_MAX) == small and nk > 0 for nk in counts), counts
 
 
 def test_c5_generator_matches_device():
