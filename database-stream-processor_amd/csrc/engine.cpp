@@ -917,6 +917,34 @@ struct RollingOp {
     }
 };
 
+// Incremental top-K per group: the last min(K, present rows) present rows of
+// every group in (k, v) order, each at weight +1, kept up to date (the
+// aggregate(Fold) + flat_map of crates/nexmark/src/queries/q19.rs; SQL's
+// ROW_NUMBER() OVER (PARTITION BY g ORDER BY x DESC) <= K).  A row's group is
+// k >> group_shift; a row is present iff its total weight in the input
+// integral is non-zero, negative totals included (aggregate/fold.rs:83-92).
+// in_sp is the input integral, out_sp the integral of this operator's own
+// outputs EXCLUDING the current tick; step() is defined below the spine
+// helpers it uses.
+struct TopKOp {
+    int64_t K = 10;
+    int group_shift = 0;
+    bool refill_all = false;  // DBSP_TOPK_REFILL_ALL
+    Spine in_sp, out_sp;
+    // cumulative: affected groups, groups sent down the refill path, rows the
+    // refill gather copied out of in_sp
+    int64_t groups_seen = 0, groups_refilled = 0, rows_gathered = 0;
+
+    // delta: consolidated rows, retained by the caller; out: the tick's
+    // consolidated output delta (k, v, +-1).  Any (k, v) is valid.
+    dbsp_status step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out);
+
+    void clear(dbsp_ctx *c) {
+        in_sp.clear(c);
+        out_sp.clear(c);
+    }
+};
+
 // ---- pieces of the keyed-aggregate stage, shared with their test probes ----
 
 // The small join route (delta.n <= 8192): probe and single-workgroup scan,
@@ -1700,19 +1728,26 @@ struct dbsp_engine {
     int64_t out_cap = 0;
     bool output_is_store = false;
     std::vector<dbsp_event> q0_output;  // q0 CPU path
+    // query 19 state: the top K bids of every auction
+    TopKOp topk;
+    bool topk_stepped = false;  // topk_init is rejected after a step
 };
 
 extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
                                           int query, int rank, int world) {
     if (query != 0 && query != 3 && query != 4 && query != 5 &&
-        query != 6 && query != 8 && query != 100 && query != 101 &&
-        query != 102)
+        query != 6 && query != 8 && query != 19 && query != 100 &&
+        query != 101 && query != 102)
         return DBSP_ERR_INVALID;
+    // the exchange hashes k, which for query 19 packs the price under the
+    // auction: it would split a group across ranks
+    if (query == 19 && world > 1) return DBSP_ERR_INVALID;
 
     dbsp_engine *e = new dbsp_engine();
     e->ctx = ctx;
     e->query = query;
     if (query == 102) e->roll.agg = DBSP_ROLL_MAX;
+    if (query == 19) e->topk.group_shift = 27;
     e->rank = rank;
     e->world = world;
     if (ctx) {
@@ -1747,6 +1782,7 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
                      &e->q4_avg_int, &e->q4_avgout, &e->q6_fold_sp})
         s->clear(c);
     e->roll.clear(c);
+    e->topk.clear(c);
     free_batch(c, e->win.maxout);
     free_batch(c, e->q6_foldout);
     free_batch(c, e->maxin_int);
@@ -2124,9 +2160,11 @@ static dbsp_status sort_pair_chain(dbsp_ctx *c, const DevBatch &inA,
     return DBSP_OK;
 }
 
+// n1_raw (optional): receives the second raw stream's row count, which the
+// front reads back either way (query 19's error word)
 static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
                                 int64_t n, DevBatch &d0, DevBatch &d1,
-                                bool want_two) {
+                                bool want_two, int64_t *n1_raw = nullptr) {
     // Explicit-path deltas (sharded ranks, oversized ticks): the front still
     // CHAINS — flatmap and the speculative fused sorts launch back-to-back
     // and one sync reads counts + lengths; deltas over the fused capacity
@@ -2144,6 +2182,7 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
         const bool hc = staged_cols(e, d_ev, cols);
         TRY(dbspk::flatmap_events(c->stream, d_ev, hc ? &cols : nullptr, n,
                                   e->query, &raw0, &raw1));
+        if (n1_raw) *n1_raw = raw1.n;
         if (want_two && raw0.n <= 8192 && raw1.n <= 8192) {
             TRY(sort_two_small(c, raw0, raw1, d0, d1));
         } else {
@@ -2157,6 +2196,7 @@ static dbsp_status build_deltas(dbsp_engine *e, const dbsp_event *d_ev,
         DevBatch rawA, rawB, oA, oB;
         TRY(build_deltas_chain(e, d_ev, n, rawA, rawB, oA, oB));
         TRY(read_len(c, LEN_BASE0, LEN_TICK));
+        if (n1_raw) *n1_raw = c->h_len[L_RAW + 1];
         if (c->h_len[L_DELTA] < 0 || c->h_len[L_DELTA + 1] < 0) {
             rawA.n = c->h_len[L_RAW];
             rawB.n = c->h_len[L_RAW + 1];
@@ -4595,6 +4635,10 @@ static dbsp_status c5_step(dbsp_engine *e, int64_t lo, int64_t hi) {
     return DBSP_OK;
 }
 
+// query 19's tick, defined with its operator at the end of this file
+static dbsp_status q19_step(dbsp_engine *e, const dbsp_event *d_ev,
+                            int64_t n);
+
 extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
                                                int64_t hi) {
     if (lo < 0 || hi > e->n_events || lo > hi) return DBSP_ERR_INVALID;
@@ -4622,6 +4666,7 @@ extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
         case 6: return q6_step(e, d_ev, hi - lo);
         case 5: return q5_step(e, d_ev, hi - lo);
         case 8: return q8_step(e, d_ev, hi - lo);
+        case 19: return q19_step(e, d_ev, hi - lo);
         case 101:
         case 102: return q101_step(e, d_ev, hi - lo);
     }
@@ -4670,6 +4715,7 @@ extern "C" dbsp_status dbsp_engine_step(dbsp_engine *e, const dbsp_event *events
         case 6: st = q6_step(e, d_ev, n); break;
         case 5: st = q5_step(e, d_ev, n); break;
         case 8: st = q8_step(e, d_ev, n); break;
+        case 19: st = q19_step(e, d_ev, n); break;
         case 101:
         case 102: st = q101_step(e, d_ev, n); break;
         default: st = DBSP_ERR_INVALID;
@@ -4710,5 +4756,224 @@ extern "C" dbsp_status dbsp_engine_kernel_stats(dbsp_engine *e, int kind,
     *total_ms = e->ctx->stats[kind].ms;
     *algo_bytes = e->ctx->stats[kind].bytes;
     *launches = e->ctx->stats[kind].launches;
+    return DBSP_OK;
+}
+
+// ---- incremental top-K per group (queries/q19.rs; fold.rs:83-92) ----
+// Per tick, over a consolidated delta D:
+//   classify  every row of D against in_sp BEFORE the tick: appear (absent ->
+//             present), vanish (present -> absent) or neither; head flags
+//             and one scan list the affected groups and their key ranges
+//   current   out_sp rows inside those ranges, consolidated: Oc, at most K
+//             rows per affected group, all of weight +1
+//   verdict   a group refills iff one of its vanish rows r has
+//             count(Oc_g) == K and r >= first(Oc_g): only a full top-K that
+//             loses a member must look deeper.  A short Oc_g holds every
+//             present row of its group, and a row below a full Oc_g's first
+//             member was not in it.
+//   insert    D into in_sp
+//   slice     groups not refilled: Oc_g at +1, appear rows at +1, vanish rows
+//             that are in Oc_g at -1; refilled groups: their whole run out of
+//             in_sp with its real weights (rows_gathered), and none of Oc_g,
+//             whose synthetic +1 would corrupt them.  Consolidated into S.
+//   select    a row of S is kept iff at most K - 1 rows follow it in its group
+//   output    consolidate(selected - Oc), appended to out_sp
+// An append-only stream never refills: step cost follows the delta and K,
+// not the group.  The explicit per-op path (a host length sync per phase, as
+// q4/q6 and the rolling operator); no chaining.  No row is invalid, so
+// nothing can fail after the first write to in_sp for a reason the caller
+// controls.
+dbsp_status TopKOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
+    out = DevBatch{};
+    if (delta.n == 0) return DBSP_OK;
+    ScopedTimer timer(c, 3, 0.0);
+    const int64_t n = delta.n;
+    TRY(in_sp.cap_batches(c));
+    TRY(out_sp.cap_batches(c));
+    uint64_t *pb = nullptr;
+    int64_t ng = 0;
+    TRY(dbspk::topk_classify(c->stream, delta, trace_args_of(in_sp),
+                             group_shift, &pb, &ng));
+    ScratchBuf plan(c, pb);
+    DevBatch cur;
+    {
+        DevBatch raw;
+        TRY(dbspk::keyrange_gather(c->stream, pb + 2 * n, pb + 3 * n, ng,
+                                   trace_args_of(out_sp), 1, &raw));
+        TRY(sort_consolidate_batch(c, raw, cur));
+    }
+    uint64_t *vb = nullptr;
+    int64_t n_refill = 0;
+    TRY(dbspk::topk_verdict(c->stream, delta, pb, ng, cur, K, refill_all, &vb,
+                            &n_refill));
+    ScratchBuf verdict(c, vb);
+    TRY(in_sp.insert_copy(c, delta));
+    TRY(in_sp.cap_batches(c));
+    // the candidate slice
+    std::vector<DevBatch> parts;
+    int64_t gathered = 0;
+    {
+        DevBatch cand;
+        TRY(dbspk::topk_candidates(c->stream, delta, pb, ng, vb, cur, &cand));
+        if (cand.n > 0) parts.push_back(cand);
+    }
+    if (n_refill > 0) {
+        DevBatch runs;
+        TRY(dbspk::keyrange_gather(c->stream, vb + ng, vb + 2 * ng, n_refill,
+                                   trace_args_of(in_sp), 1, &runs));
+        gathered = runs.n;
+        if (runs.n > 0) parts.push_back(runs);
+    }
+    DevBatch slice, sel;
+    if (!parts.empty()) TRY(finalize_raw(c, parts, slice));
+    TRY(dbspk::topk_select(c->stream, slice, K, group_shift, &sel));
+    const int64_t moved = cur.n + gathered + slice.n + sel.n;
+    free_batch(c, slice);
+    // selected - Oc: Oc's weights are all +1, so -1 throughout negates it
+    if (cur.n > 0) dbspk::fill_u64(c->stream, (uint64_t *)cur.w, ~0ull, cur.n);
+    if (cur.n == 0) {
+        out = sel;
+    } else if (sel.n == 0) {
+        out = cur;
+    } else {
+        TRY(merge_batches(c, sel, cur, out));
+        free_batch(c, sel);
+        free_batch(c, cur);
+    }
+    if (out.n == 0) free_batch(c, out);
+    if (out.n > 0) TRY(out_sp.insert_copy(c, out));
+    groups_seen += ng;
+    groups_refilled += n_refill;
+    rows_gathered += gathered;
+    timer.bytes = 24.0 * (double)moved;
+    return DBSP_OK;
+}
+
+struct dbsp_topk_op {
+    dbsp_ctx *ctx = nullptr;
+    TopKOp op;
+};
+
+static bool topk_args_valid(int64_t K, int group_shift) {
+    return K >= 1 && K <= 65536 && group_shift >= 0 && group_shift <= 63;
+}
+
+// the select stage over a caller's batch: the recompute route
+extern "C" dbsp_status dbsp_topk(dbsp_ctx *c, const dbsp_batch *in, int64_t K,
+                                 int group_shift, dbsp_batch *out) {
+    if (!c || !in || !out || in->len < 0 || !topk_args_valid(K, group_shift))
+        return DBSP_ERR_INVALID;
+    DevBatch res;
+    {
+        ScopedTimer t(c, 3, 0.0);
+        TRY(dbspk::topk_select(c->stream, as_batch(in), K, group_shift, &res));
+    }
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_topk_create(dbsp_ctx *c, int64_t K,
+                                        int group_shift, uint32_t flags,
+                                        dbsp_topk_op **out) {
+    if (!c || !out || !topk_args_valid(K, group_shift) ||
+        (flags & ~(uint32_t)DBSP_TOPK_REFILL_ALL))
+        return DBSP_ERR_INVALID;
+    dbsp_topk_op *t = new dbsp_topk_op();
+    t->ctx = c;
+    t->op.K = K;
+    t->op.group_shift = group_shift;
+    t->op.refill_all = (flags & DBSP_TOPK_REFILL_ALL) != 0;
+    *out = t;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_topk_step(dbsp_topk_op *t, const uint64_t *k,
+                                      const uint64_t *v, const int64_t *w,
+                                      int64_t n, dbsp_batch *out) {
+    if (!t || !out || n < 0) return DBSP_ERR_INVALID;
+    dbsp_ctx *c = t->ctx;
+    *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
+    if (n == 0) return DBSP_OK;
+    DevBatch raw, delta, res;
+    TRY(alloc_batch(c, n, raw));
+    TRY(copy_cols(c, raw, 0, k, v, w, n));
+    TRY(sort_consolidate_batch(c, raw, delta));
+    const dbsp_status st = t->op.step(c, delta, res);
+    free_batch(c, delta);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    if (st != DBSP_OK) return st;
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_topk_stats(dbsp_topk_op *t, int64_t *in_rows,
+                                       int *in_batches, int64_t *out_rows,
+                                       int *out_batches, int64_t *groups_seen,
+                                       int64_t *groups_refilled,
+                                       int64_t *rows_gathered) {
+    if (!t) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = t->op.in_sp.total();
+    if (in_batches) *in_batches = (int)t->op.in_sp.batches.size();
+    if (out_rows) *out_rows = t->op.out_sp.total();
+    if (out_batches) *out_batches = (int)t->op.out_sp.batches.size();
+    if (groups_seen) *groups_seen = t->op.groups_seen;
+    if (groups_refilled) *groups_refilled = t->op.groups_refilled;
+    if (rows_gathered) *rows_gathered = t->op.rows_gathered;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_topk_destroy(dbsp_topk_op *t) {
+    if (!t) return DBSP_OK;
+    t->op.clear(t->ctx);
+    (void)hipStreamSynchronize(t->ctx->stream);
+    delete t;
+    return DBSP_OK;
+}
+
+// ---- query 19: the top K bids of every auction (queries/q19.rs) ----
+// bids.flat_map_index(|b| (b.auction, (b.price, b))) into the top-K operator:
+// rows k = auction << 27 | price, v = bidder << 32 | date_time with
+// group_shift 27, so the group is the auction and the order inside it
+// (price, bidder, date_time): the reference's (price, Bid) order restricted
+// to the fields dbsp_event carries (channel, url and extra are not in the
+// event row).  The output rows are the input rows.
+// A field too wide for its place is caught on the device: the flatmap sends
+// such a bid to its second stream, whose length build_deltas reads back with
+// the other lengths; a non-empty second stream makes the step
+// DBSP_ERR_INVALID before the operator runs, so its state is unchanged.
+static dbsp_status q19_step(dbsp_engine *e, const dbsp_event *d_ev,
+                            int64_t n) {
+    dbsp_ctx *c = e->ctx;
+    engine_free_output(e);
+    e->topk_stepped = true;
+    DevBatch d, dummy;
+    int64_t n_wide = 0;
+    TRY(build_deltas(e, d_ev, n, d, dummy, false, &n_wide));
+    dbsp_status st = DBSP_ERR_INVALID;
+    if (n_wide == 0) st = e->topk.step(c, d, e->output);
+    free_batch(c, d);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return st;
+}
+
+extern "C" dbsp_status dbsp_engine_topk_init(dbsp_engine *e, int64_t K) {
+    if (!e || e->query != 19 || e->topk_stepped || !topk_args_valid(K, 27))
+        return DBSP_ERR_INVALID;
+    e->topk.K = K;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_engine_topk_stats(dbsp_engine *e, int64_t *in_rows,
+                                              int64_t *out_rows,
+                                              int64_t *groups_seen,
+                                              int64_t *groups_refilled,
+                                              int64_t *rows_gathered) {
+    if (!e || e->query != 19) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = e->topk.in_sp.total();
+    if (out_rows) *out_rows = e->topk.out_sp.total();
+    if (groups_seen) *groups_seen = e->topk.groups_seen;
+    if (groups_refilled) *groups_refilled = e->topk.groups_refilled;
+    if (rows_gathered) *rows_gathered = e->topk.rows_gathered;
     return DBSP_OK;
 }

@@ -4095,6 +4095,12 @@ dbsp_status columnize_events(hipStream_t s, const dbsp_event *ev, int64_t n,
     return DBSP_OK;
 }
 
+// query 19's front, defined with the top-K kernels below
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_topk(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1);
+
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
                                  const Rows &out0, const Rows &out1,
@@ -4106,6 +4112,10 @@ dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
     if (n > 0 && query == 102)
         k_flatmap_bid_tv<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
             ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1);
+    else if (n > 0 && query == 19)
+        k_flatmap_bid_topk<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
+            ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1, out1.k,
+            out1.v, out1.w, out1.n);
     else if (n > 0)
         k_flatmap<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
             ev, c, n, query, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1,
@@ -4965,6 +4975,379 @@ dbsp_status roll_eval_minmax_rows(hipStream_t s, const Rows &slice,
             r.w);
     }
     return give_rows(lv, r, out);
+}
+
+// ---------------------------------------------------------------------------
+// Incremental top-K per group (the aggregate(Fold) + flat_map of
+// crates/nexmark/src/queries/q19.rs: a VecDeque that keeps the last K values
+// of the group's cursor-ordered run, every value of non-zero weight stepping
+// once, aggregate/fold.rs:83-92).  A row's group is k >> shift; plain (k, v)
+// order is (group, rank) order.  A group's keys are the INCLUSIVE range
+// [k & ~mask, k | mask] with mask = 2^shift - 1: the first key of the next
+// group is never formed, it does not exist for the all-ones group.
+//   k_topk_classify        per delta row: total weight in the input integral
+//                          before the tick (one lexicographic search per
+//                          spine batch) -> appear / vanish / neither, and
+//                          the group head flag
+//   k_topk_groups          head flags + scan -> row's group index, the
+//                          affected groups' key ranges
+//   k_keyrange_count       key-range-only gather count (k_range_emit emits)
+//   k_topk_verdict         per vanish row: its group must refill iff the
+//                          current top-K is full and the row is not below
+//                          its first member
+//   k_topk_refill_ranges   the refilled groups' key ranges, compacted
+//   k_topk_cand_flags/emit the candidate rows of the groups NOT refilled
+//   k_topk_select_flags/emit  a slice row is kept iff at most K - 1 rows
+//                          follow it in its group: one binary search per row
+// Every data-dependent size is flags -> scan -> emit; nothing passes between
+// workgroups.
+// ---------------------------------------------------------------------------
+
+__device__ inline uint64_t topk_mask(int shift) {
+    return shift ? ~0ull >> (64 - shift) : 0ull;
+}
+
+// cls: +1 appear (absent before, present after), -1 vanish, 0 neither.
+// Presence is a non-zero total, negative totals included (fold.rs:83-92).
+__global__ void k_topk_classify(const uint64_t *dk, const uint64_t *dv,
+                                const int64_t *dw, int64_t n, TraceArgs t,
+                                int shift, int64_t *cls, uint64_t *heads) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = dk[i], v = dv[i];
+        int64_t before = 0;
+        for (int b = 0; b < t.nb; b++) {
+            const int64_t nb = t.n[b];
+            const int64_t j = lex_lower(t.k[b], t.v[b], 0, nb, k, v);
+            if (j < nb && t.k[b][j] == k && t.v[b][j] == v) before += t.w[b][j];
+        }
+        const int64_t after = before + dw[i];
+        cls[i] = (int64_t)(before == 0 && after != 0) -
+                 (int64_t)(before != 0 && after == 0);
+        heads[i] = i == 0 || (dk[i - 1] >> shift) != (k >> shift);
+    }
+}
+
+// gidx[i]: the affected-group index of delta row i; a head row writes its
+// group's inclusive key range
+__global__ void k_topk_groups(const uint64_t *dk, int64_t n, int shift,
+                              const uint64_t *heads, const uint64_t *hscan,
+                              uint64_t *gidx, uint64_t *glo, uint64_t *ghi) {
+    const uint64_t mask = topk_mask(shift);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t h = heads[i];
+        // row 0 is a head, so the index is never negative
+        const uint64_t g = hscan[i] + h - 1;
+        gidx[i] = g;
+        if (h) {
+            glo[g] = dk[i] & ~mask;
+            ghi[g] = dk[i] | mask;
+        }
+    }
+}
+
+// key-range gather count: one thread per (range, spine batch) pair, rows with
+// k in [klo, khi] whatever their v.  A sibling of k_range_count, whose modes
+// split a 64-bit word into partition and time halves.
+__global__ void k_keyrange_count(const uint64_t *klo, const uint64_t *khi,
+                                 int64_t nr, TraceArgs t, uint64_t *cnt,
+                                 uint64_t *start) {
+    const int64_t np = nr * t.nb;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < np;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = j / t.nb;
+        const int b = (int)(j % t.nb);
+        const int64_t n = t.n[b];
+        int64_t lo = 0, hi = 0;
+        if (n > 0 && klo[r] <= khi[r]) {
+            lo = lower_bound_k(t.k[b], n, klo[r]);
+            hi = lo + upper_bound_k(t.k[b] + lo, n - lo, khi[r]);
+        }
+        cnt[j] = (uint64_t)(hi - lo);
+        start[j] = (uint64_t)lo;
+    }
+}
+
+// ok/ov: the affected groups' current top-K rows (consolidated, at most K per
+// group).  Several rows of a group may raise its flag: all store the same 1.
+__global__ void k_topk_verdict(const uint64_t *dk, const uint64_t *dv,
+                               const int64_t *cls, const uint64_t *gidx,
+                               int64_t n, const uint64_t *glo,
+                               const uint64_t *ghi, const uint64_t *ok,
+                               const uint64_t *ov, int64_t no, int64_t K,
+                               uint64_t *refill) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (cls[i] >= 0) continue;
+        const uint64_t g = gidx[i];
+        const int64_t a = lower_bound_k(ok, no, glo[g]);
+        const int64_t b = a + upper_bound_k(ok + a, no - a, ghi[g]);
+        if (b - a == K && !row_lt(dk[i], dv[i], ok[a], ov[a])) refill[g] = 1;
+    }
+}
+
+__global__ void k_topk_refill_ranges(const uint64_t *refill,
+                                     const uint64_t *rscan, int64_t ng,
+                                     const uint64_t *glo, const uint64_t *ghi,
+                                     uint64_t *rlo, uint64_t *rhi) {
+    for (int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; g < ng;
+         g += (int64_t)gridDim.x * blockDim.x) {
+        if (!refill[g]) continue;
+        rlo[rscan[g]] = glo[g];
+        rhi[rscan[g]] = ghi[g];
+    }
+}
+
+// Candidates of the groups that are not refilled, over the index space
+// [0, no) = the current top-K rows, [no, no + n) = the delta rows: a top-K
+// row stays, an appear row enters, a vanish row enters (negated) iff it is a
+// top-K row.  Rows of refilled groups stay out: those groups come from the
+// input integral with their real weights.
+__global__ void k_topk_cand_flags(const uint64_t *dk, const uint64_t *dv,
+                                  const int64_t *cls, const uint64_t *gidx,
+                                  int64_t n, const uint64_t *glo, int64_t ng,
+                                  const uint64_t *refill, const uint64_t *ok,
+                                  const uint64_t *ov, int64_t no,
+                                  uint64_t *flags) {
+    const int64_t tot = no + n;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < tot;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t f;
+        if (j < no) {
+            // every top-K row lies in an affected group: it was gathered by
+            // that group's range, and glo[0] <= its key
+            const int64_t g = upper_bound_k(glo, ng, ok[j]) - 1;
+            f = g >= 0 && !refill[g];
+        } else {
+            const int64_t i = j - no;
+            const int64_t c = cls[i];
+            f = 0;
+            if (c != 0 && !refill[gidx[i]]) {
+                f = 1;
+                if (c < 0) {
+                    const int64_t p = lex_lower(ok, ov, 0, no, dk[i], dv[i]);
+                    f = p < no && ok[p] == dk[i] && ov[p] == dv[i];
+                }
+            }
+        }
+        flags[j] = f;
+    }
+}
+
+__global__ void k_topk_cand_emit(const uint64_t *dk, const uint64_t *dv,
+                                 const int64_t *cls, int64_t n,
+                                 const uint64_t *ok, const uint64_t *ov,
+                                 int64_t no, const uint64_t *flags,
+                                 const uint64_t *fscan, uint64_t *ck,
+                                 uint64_t *cv, int64_t *cw) {
+    const int64_t tot = no + n;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < tot;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[j]) continue;
+        const uint64_t o = fscan[j];
+        if (j < no) {
+            ck[o] = ok[j]; cv[o] = ov[j]; cw[o] = 1;
+        } else {
+            const int64_t i = j - no;
+            ck[o] = dk[i]; cv[o] = dv[i]; cw[o] = cls[i];
+        }
+    }
+}
+
+// a row of the consolidated slice is selected iff at most K - 1 rows follow
+// it inside its group: the group's end is one binary search over the keys
+__global__ void k_topk_select_flags(const uint64_t *sk, int64_t n, int shift,
+                                    int64_t K, uint64_t *flags) {
+    const uint64_t mask = topk_mask(shift);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t from = i + 1;
+        const int64_t end =
+            from + upper_bound_k(sk + from, n - from, sk[i] | mask);
+        flags[i] = end - i <= K;
+    }
+}
+
+__global__ void k_topk_select_emit(const uint64_t *sk, const uint64_t *sv,
+                                   int64_t n, const uint64_t *flags,
+                                   const uint64_t *fscan, uint64_t *ok,
+                                   uint64_t *ov, int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t o = fscan[i];
+        ok[o] = sk[i]; ov[o] = sv[i]; ow[o] = 1;
+    }
+}
+
+dbsp_status topk_classify(hipStream_t s, const Rows &delta, const TraceArgs &t,
+                          int shift, uint64_t **plan, int64_t *n_groups) {
+    const int64_t n = delta.n;
+    *plan = nullptr;
+    *n_groups = 0;
+    if (n <= 0) return DBSP_OK;
+    Scratch sc(s);
+    uint64_t *heads, *hscan, *pb;
+    HIP_CHECK(sc.get(&heads, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&hscan, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&pb, 4 * n * sizeof(uint64_t)));
+    k_topk_classify<<<grid_for(n), BLK, 0, s>>>(delta.k, delta.v, delta.w, n, t,
+                                                shift, (int64_t *)pb, heads);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, heads, hscan, n, &total));
+    k_topk_groups<<<grid_for(n), BLK, 0, s>>>(delta.k, n, shift, heads, hscan,
+                                              pb + n, pb + 2 * n, pb + 3 * n);
+    *n_groups = (int64_t)total;
+    sc.keep(pb);
+    *plan = pb;
+    return DBSP_OK;
+}
+
+dbsp_status keyrange_gather(hipStream_t s, const uint64_t *klo,
+                            const uint64_t *khi, int64_t nr,
+                            const TraceArgs &t, int64_t sign, Rows *out) {
+    if (nr <= 0 || t.nb <= 0) return no_rows(out);
+    const int64_t np = nr * t.nb;
+    Scratch sc(s);
+    uint64_t *cnt, *start;
+    HIP_CHECK(sc.get(&cnt, np * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&start, np * sizeof(uint64_t)));
+    k_keyrange_count<<<grid_for(np), BLK, 0, s>>>(klo, khi, nr, t, cnt, start);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, cnt, cnt, np, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_range_emit<<<grid_for((int64_t)total), BLK, 0, s>>>(
+        t, np, cnt, start, (int64_t)total, sign, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+dbsp_status topk_verdict(hipStream_t s, const Rows &delta,
+                         const uint64_t *plan, int64_t ng, const Rows &cur,
+                         int64_t K, bool refill_all, uint64_t **verdict,
+                         int64_t *n_refill) {
+    const int64_t n = delta.n;
+    *verdict = nullptr;
+    *n_refill = 0;
+    if (n <= 0 || ng <= 0) return DBSP_OK;
+    const int64_t *cls = (const int64_t *)plan;
+    const uint64_t *gidx = plan + n, *glo = plan + 2 * n, *ghi = plan + 3 * n;
+    Scratch sc(s);
+    uint64_t *vb, *rscan;
+    HIP_CHECK(sc.get(&vb, 3 * ng * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&rscan, ng * sizeof(uint64_t)));
+    if (refill_all) {
+        k_fill_u64<<<grid_for(ng), BLK, 0, s>>>(vb, 1, ng);
+    } else {
+        HIP_CHECK(hipMemsetAsync(vb, 0, ng * sizeof(uint64_t), s));
+        k_topk_verdict<<<grid_for(n), BLK, 0, s>>>(delta.k, delta.v, cls, gidx,
+                                                   n, glo, ghi, cur.k, cur.v,
+                                                   cur.n, K, vb);
+    }
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, vb, rscan, ng, &total));
+    if (total > 0)
+        k_topk_refill_ranges<<<grid_for(ng), BLK, 0, s>>>(
+            vb, rscan, ng, glo, ghi, vb + ng, vb + 2 * ng);
+    *n_refill = (int64_t)total;
+    sc.keep(vb);
+    *verdict = vb;
+    return DBSP_OK;
+}
+
+dbsp_status topk_candidates(hipStream_t s, const Rows &delta,
+                            const uint64_t *plan, int64_t ng,
+                            const uint64_t *refill, const Rows &cur,
+                            Rows *out) {
+    const int64_t n = delta.n, no = cur.n, tot = n + no;
+    if (n <= 0 || ng <= 0) return no_rows(out);
+    const int64_t *cls = (const int64_t *)plan;
+    const uint64_t *gidx = plan + n, *glo = plan + 2 * n;
+    Scratch sc(s);
+    uint64_t *flags, *fscan;
+    HIP_CHECK(sc.get(&flags, tot * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, tot * sizeof(uint64_t)));
+    k_topk_cand_flags<<<grid_for(tot), BLK, 0, s>>>(delta.k, delta.v, cls,
+                                                    gidx, n, glo, ng, refill,
+                                                    cur.k, cur.v, no, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, tot, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_topk_cand_emit<<<grid_for(tot), BLK, 0, s>>>(delta.k, delta.v, cls, n,
+                                                   cur.k, cur.v, no, flags,
+                                                   fscan, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+dbsp_status topk_select(hipStream_t s, const Rows &slice, int64_t K, int shift,
+                        Rows *out) {
+    const int64_t n = slice.n;
+    if (n <= 0) return no_rows(out);
+    Scratch sc(s);
+    uint64_t *flags, *fscan;
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_topk_select_flags<<<grid_for(n), BLK, 0, s>>>(slice.k, n, shift, K,
+                                                    flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_topk_select_emit<<<grid_for(n), BLK, 0, s>>>(slice.k, slice.v, n, flags,
+                                                   fscan, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+// Query 19's front (queries/q19.rs: bids.flat_map_index(|b| (b.auction,
+// (b.price, b)))), a kernel of its own as k_flatmap_bid_tv is, so that
+// k_flatmap (on q3's measured path) stays as it is.  Stream
+// 0: k = auction << 27 | price, v = bidder << 32 | date_time, so (k, v) order
+// is (auction, price, bidder, date_time) order.  Stream 1 collects the bids
+// with a field too wide for its place, as (auction, price, w): its counter is
+// the step's error word, read back with the lengths the step syncs on anyway.
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_topk(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1) {
+    __shared__ uint32_t s_cnt[2][FLATMAP_WAVES];
+    __shared__ unsigned long long s_base[2][FLATMAP_WAVES];
+    const int64_t stride = (int64_t)gridDim.x * FLATMAP_BLK;
+    for (int64_t base = blockIdx.x * (int64_t)FLATMAP_BLK; base < n;
+         base += stride) {
+        const int64_t i = base + threadIdx.x;
+        uint64_t kind = 0, auction = 0, bidder = 0, price = 0, dt = 0;
+        int64_t w = 0;
+        if (i < n) {
+            if (cols.kind) {
+                kind = cols.kind[i]; auction = cols.f0[i]; bidder = cols.f1[i];
+                price = cols.f2[i]; dt = cols.f3[i]; w = cols.w[i];
+            } else {
+                const dbsp_event e = ev[i];
+                kind = e.kind; auction = e.f0; bidder = e.f1; price = e.f2;
+                dt = e.f3; w = e.w;
+            }
+        }
+        const bool bid = i < n && kind == 2;
+        const bool wide = (auction >> 37) || (price >> 27) || (bidder >> 32) ||
+                          (dt >> 32);
+        const bool p0 = bid && !wide, p1 = bid && wide;
+        uint64_t pos0, pos1;
+        block_append2((unsigned long long *)c0, (unsigned long long *)c1, p0,
+                      p1, s_cnt, s_base, pos0, pos1);
+        if (p0 && pos0 < (uint64_t)cap0) {
+            k0[pos0] = (auction << 27) | price;
+            v0[pos0] = (bidder << 32) | dt;
+            w0[pos0] = w;
+        }
+        if (p1 && pos1 < (uint64_t)cap1) {
+            k1[pos1] = auction; v1[pos1] = price; w1[pos1] = w;
+        }
+    }
 }
 
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed) {

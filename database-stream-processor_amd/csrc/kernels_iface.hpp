@@ -438,6 +438,45 @@ dbsp_status roll_eval_minmax_rows(hipStream_t s, const Rows &slice,
                                   const Rows &delta, bool is_min,
                                   uint64_t before, uint64_t after, Rows *out);
 
+// ---- incremental top-K per group (the aggregate(Fold) + flat_map of
+// queries/q19.rs; presence = non-zero total weight, aggregate/fold.rs:83-92).
+// A row's group is k >> shift (0..63); its keys are the inclusive range
+// [k & ~mask, k | mask], mask = 2^shift - 1 ----
+// Classify the rows of a consolidated delta against the input integral
+// BEFORE the tick (t: its spine batches) and list the affected groups.
+// *plan is one 4*n-word device buffer (caller frees with cache_free) holding
+// the columns [cls | gidx | glo | ghi], each n words apart: cls (int64) +1
+// appear / -1 vanish / 0 neither and gidx the group index per delta row;
+// glo/ghi the key range of the first n_groups affected groups, in key order.
+// One host sync.
+dbsp_status topk_classify(hipStream_t s, const Rows &delta, const TraceArgs &t,
+                          int shift, uint64_t **plan, int64_t *n_groups);
+// copy the rows of every spine batch with k in [klo[r], khi[r]], weights
+// times sign; ranges disjoint, output RAW (range-major, batch-minor runs)
+dbsp_status keyrange_gather(hipStream_t s, const uint64_t *klo,
+                            const uint64_t *khi, int64_t nr,
+                            const TraceArgs &t, int64_t sign, Rows *out);
+// Per-group refill flag.  cur: the affected groups' current top-K rows,
+// consolidated (weights unread).  A group refills iff one of its vanish rows
+// r has count(cur_g) == K and r >= first(cur_g); refill_all flags them all.
+// *verdict is one 3*ng-word device buffer (caller frees) [refill | rlo | rhi]:
+// the flag per group, then the key ranges of the n_refill flagged groups.
+// One host sync.
+dbsp_status topk_verdict(hipStream_t s, const Rows &delta,
+                         const uint64_t *plan, int64_t ng, const Rows &cur,
+                         int64_t K, bool refill_all, uint64_t **verdict,
+                         int64_t *n_refill);
+// raw candidate rows of the groups NOT refilled: cur's rows at +1, appear
+// rows at +1, vanish rows that are in cur at -1
+dbsp_status topk_candidates(hipStream_t s, const Rows &delta,
+                            const uint64_t *plan, int64_t ng,
+                            const uint64_t *refill, const Rows &cur,
+                            Rows *out);
+// the last <= K rows of every group of a consolidated slice, as (k, v, +1),
+// in order
+dbsp_status topk_select(hipStream_t s, const Rows &slice, int64_t K, int shift,
+                        Rows *out);
+
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 
 }  // namespace dbspk

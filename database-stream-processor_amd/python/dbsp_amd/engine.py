@@ -212,6 +212,29 @@ def _L():
                                                 ctypes.POINTER(i64),
                                                 ctypes.POINTER(i64),
                                                 ctypes.POINTER(i64)]
+        L.dbsp_topk.restype = i32
+        L.dbsp_topk.argtypes = [vp, ctypes.POINTER(BatchStruct), i64,
+                                ctypes.c_int, ctypes.POINTER(BatchStruct)]
+        L.dbsp_topk_create.restype = i32
+        L.dbsp_topk_create.argtypes = [vp, i64, ctypes.c_int, ctypes.c_uint32,
+                                       ctypes.POINTER(vp)]
+        L.dbsp_topk_step.restype = i32
+        L.dbsp_topk_step.argtypes = [vp, vp, vp, vp, i64,
+                                     ctypes.POINTER(BatchStruct)]
+        L.dbsp_topk_stats.restype = i32
+        L.dbsp_topk_stats.argtypes = [vp, ctypes.POINTER(i64),
+                                      ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(i64),
+                                      ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(i64),
+                                      ctypes.POINTER(i64),
+                                      ctypes.POINTER(i64)]
+        L.dbsp_topk_destroy.restype = i32
+        L.dbsp_topk_destroy.argtypes = [vp]
+        L.dbsp_engine_topk_init.restype = i32
+        L.dbsp_engine_topk_init.argtypes = [vp, i64]
+        L.dbsp_engine_topk_stats.restype = i32
+        L.dbsp_engine_topk_stats.argtypes = [vp] + [ctypes.POINTER(i64)] * 5
         L.dbsp_engine_c5_init.restype = i32
         L.dbsp_engine_c5_init.argtypes = [vp, i64, i64, u64]
         L.dbsp_engine_kernel_stats.restype = i32
@@ -673,6 +696,20 @@ class Ctx:
         [ts - before, ts + after] (see `Rolling`)."""
         return Rolling(self, before, after, agg=agg)
 
+    def topk(self, rows, k, group_shift):
+        """The last <= k rows of every group (key >> group_shift) of a
+        consolidated batch, each at weight +1, in order: the recompute route
+        of `TopK`."""
+        inp = self.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_topk(self._h, ctypes.byref(inp), k, group_shift,
+                                 ctypes.byref(out))
+        self.free_batch(inp)
+        _check(st, "topk")
+        res = self.download_rows(out)
+        self.free_batch(out)
+        return res
+
     def shard_partition(self, rows, nshards):
         inp = self.upload_rows(rows)
         out = BatchStruct()
@@ -782,6 +819,65 @@ class Rolling:
         return ir.value, ib.value, orr.value, ob.value
 
 
+TOPK_REFILL_ALL = 1  # DBSP_TOPK_REFILL_ALL
+
+
+class TopK:
+    """Stateful incremental top-K per group (the aggregate(Fold) + flat_map
+    of Nexmark q19).  Input rows are (k, v, w); a row's group is
+    k >> group_shift and (k, v) order ranks the rows inside it.  The operator
+    keeps, per group, the last min(k, present rows) rows whose total weight is
+    non-zero, each at weight +1; each step returns the tick's consolidated
+    change of that relation.  refill_all recomputes every affected group from
+    its whole run (a diagnostic: outputs are the same)."""
+
+    def __init__(self, ctx: Ctx, k: int, group_shift: int, refill_all=False):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        _check(self._lib.dbsp_topk_create(
+            ctx._h, k, group_shift, TOPK_REFILL_ALL if refill_all else 0,
+            ctypes.byref(h)), "topk_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):
+                self._lib.dbsp_topk_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def step(self, rows: np.ndarray) -> np.ndarray:
+        """One tick: raw (unsorted, unconsolidated) delta rows in, the
+        consolidated output delta (k, v, +-1) out."""
+        raw = self._ctx.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_topk_step(self._h, raw.k, raw.v, raw.w, raw.len,
+                                      ctypes.byref(out))
+        self._ctx.free_batch(raw)
+        _check(st, "topk_step")
+        res = self._ctx.download_rows(out)
+        self._ctx.free_batch(out)
+        return res
+
+    def stats(self) -> dict:
+        """in_rows / in_batches / out_rows / out_batches of the two traces
+        and the cumulative groups_seen, groups_refilled, rows_gathered."""
+        ir, orr = ctypes.c_int64(), ctypes.c_int64()
+        ib, ob = ctypes.c_int(), ctypes.c_int()
+        gs, gr, rg = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(self._lib.dbsp_topk_stats(
+            self._h, ctypes.byref(ir), ctypes.byref(ib), ctypes.byref(orr),
+            ctypes.byref(ob), ctypes.byref(gs), ctypes.byref(gr),
+            ctypes.byref(rg)), "topk_stats")
+        return {"in_rows": ir.value, "in_batches": ib.value,
+                "out_rows": orr.value, "out_batches": ob.value,
+                "groups_seen": gs.value, "groups_refilled": gr.value,
+                "rows_gathered": rg.value}
+
+
 def xxh3_u64(key, seed=0x7F95EF85BE33C337):
     return _L().dbsp_xxh3_u64(key, seed)
 
@@ -844,6 +940,21 @@ class Engine:
         _check(self._lib.dbsp_engine_rolling_stats(
             self._h, *[ctypes.byref(x) for x in vals]), "rolling_stats")
         return tuple(x.value for x in vals)
+
+    def topk_init(self, k):
+        """Query 19: how many bids per auction to keep (default 10);
+        rejected after the first step."""
+        _check(self._lib.dbsp_engine_topk_init(self._h, k), "topk_init")
+
+    def topk_stats(self) -> dict:
+        """Query 19: in_rows, out_rows and the cumulative groups_seen,
+        groups_refilled, rows_gathered."""
+        vals = [ctypes.c_int64() for _ in range(5)]
+        _check(self._lib.dbsp_engine_topk_stats(
+            self._h, *[ctypes.byref(x) for x in vals]), "topk_stats")
+        return dict(zip(("in_rows", "out_rows", "groups_seen",
+                         "groups_refilled", "rows_gathered"),
+                        (x.value for x in vals)))
 
     def step_staged(self, lo, hi):
         _check(self._lib.dbsp_engine_step_staged(self._h, lo, hi), "step")

@@ -354,6 +354,66 @@ dbsp_status dbsp_rolling_wm_stats(dbsp_rolling *r, uint64_t *watermark,
 dbsp_status dbsp_truncate_below(dbsp_ctx *ctx, const dbsp_batch *in, int mode,
                                 uint64_t bound, dbsp_batch *out);
 
+/* ---- incremental top-K per group ----
+ * SQL's ROW_NUMBER() OVER (PARTITION BY g ORDER BY x DESC) <= K, kept up to
+ * date.  Replaces the aggregate(Fold) that keeps the last K values of a
+ * key's cursor-ordered run in a VecDeque (pop_front at capacity, push_back)
+ * and the flat_map behind it (crates/nexmark/src/queries/q19.rs).
+ * Rows are (k, v, w).  A row's group is g = k >> group_shift; the low
+ * group_shift bits of k, then all of v, order the rows inside a group, so
+ * plain (k, v) order is (group, rank) order.  A row is PRESENT iff its total
+ * weight in the input integral is non-zero, negative totals included
+ * (Fold::aggregate steps on !weight.is_zero(), aggregate/fold.rs:83-92, once
+ * per value whatever the weight).  The maintained relation holds, for every
+ * group, its last min(K, present rows) present rows in (k, v) order, each
+ * with weight +1.  So a weight change that keeps presence (1 -> 2) outputs
+ * nothing, a row taken to net 0 vanishes, and a row at net -1 is present.
+ * Out of scope: ascending order (q18's fold), a rank-number column,
+ * watermark-bounded state, sharded ranks. */
+
+/* The batch primitive (q19.rs's fold + flat_map over one consolidated
+ * batch): the last <= K rows of every group of `in`, each with weight +1, in
+ * order.  1 <= K <= 65536 and 0 <= group_shift <= 63, else DBSP_ERR_INVALID.
+ * out: device arrays owned by the caller, null when empty; host visible on
+ * return. */
+dbsp_status dbsp_topk(dbsp_ctx *ctx, const dbsp_batch *in, int64_t K,
+                      int group_shift, dbsp_batch *out);
+
+/* The stateful operator (the aggregate operator under q19.rs's fold with its
+ * input trace and its output trace, operator/aggregate/mod.rs:479-547): the
+ * input integral and the integral of its own outputs, both as spines. */
+typedef struct dbsp_topk_op dbsp_topk_op;
+/* flags: every affected group recomputes its top-K from its whole run of the
+ * input integral (the refill path), whether or not the tick could have
+ * changed its membership that way.  A diagnostic and a test oracle: outputs
+ * are the same either way. */
+#define DBSP_TOPK_REFILL_ALL 1u
+/* circuit construction of the aggregate (Stream::aggregate,
+ * aggregate/mod.rs:204-250).  K and
+ * group_shift as for dbsp_topk; an unknown flag bit is DBSP_ERR_INVALID. */
+dbsp_status dbsp_topk_create(dbsp_ctx *ctx, int64_t K, int group_shift,
+                             uint32_t flags, dbsp_topk_op **out);
+/* AggregateIncremental::eval (aggregate/mod.rs:479-547) for this fold.
+ * k/v/w: n raw (unsorted, unconsolidated) delta rows in device memory; any
+ * (k, v) is valid.  out: the tick's consolidated change of the relation, rows
+ * (k, v, +-1) (device arrays owned by the caller, null when empty; host
+ * visible on return).  n == 0 and a delta that consolidates to nothing
+ * change nothing and return an empty out.  Work per tick follows the delta:
+ * only a group whose full top-K loses a member reads its run of the input
+ * integral. */
+dbsp_status dbsp_topk_step(dbsp_topk_op *op, const uint64_t *k,
+                           const uint64_t *v, const int64_t *w, int64_t n,
+                           dbsp_batch *out);
+/* rows / spine batches of the two traces (Spine introspection,
+ * trace/spine_fueled.rs:107-119) and cumulative counters: groups a delta
+ * touched, groups sent down the refill path, rows the refill gather copied
+ * out of the input trace.  Any out pointer may be null. */
+dbsp_status dbsp_topk_stats(dbsp_topk_op *op, int64_t *in_rows,
+                            int *in_batches, int64_t *out_rows,
+                            int *out_batches, int64_t *groups_seen,
+                            int64_t *groups_refilled, int64_t *rows_gathered);
+dbsp_status dbsp_topk_destroy(dbsp_topk_op *op);
+
 dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *ctx,
                                    const uint64_t *delta_keys, int64_t nd,
                                    const dbsp_batch *in_trace,
@@ -546,7 +606,18 @@ typedef struct dbsp_engine dbsp_engine;
  *  rolling_aggregate.rs:235-321; input rows (auction, date_time<<32 | price,
  *  w), output rows (auction<<32 | date_time, highest price, +-1); a bid
  *  whose date_time or price is >= 2^32 makes the step DBSP_ERR_INVALID with
- *  the state unchanged). */
+ *  the state unchanged), or
+ * 19 (Nexmark q19, the top K bids of every auction, queries/q19.rs:40-57:
+ *      bids.flat_map_index(|b| (b.auction, (b.price, b))) into the top-K
+ *  operator above; rows k = auction << 27 | price, v = bidder << 32 |
+ *  date_time, group_shift 27, so the group is the auction and the order
+ *  inside it (price, bidder, date_time): the reference's (price, Bid) order
+ *  restricted to the fields dbsp_event carries (channel, url and extra are
+ *  not in the event row).  Output rows are input rows, +-1.  A bid with
+ *  auction >= 2^37, price >= 2^27, bidder >= 2^32 or date_time >= 2^32 makes
+ *  the step DBSP_ERR_INVALID, detected on the device, with the state
+ *  unchanged; the next tick is unaffected.  world > 1 is DBSP_ERR_INVALID at
+ *  create: the exchange hashes k, which would split a group across ranks). */
 dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
                                int rank, int world);
 
@@ -573,6 +644,15 @@ dbsp_status dbsp_engine_rolling_agg(dbsp_engine *e, dbsp_roll_agg agg);
 dbsp_status dbsp_engine_rolling_stats(dbsp_engine *e, int64_t *in_rows,
                                       int64_t *out_rows, int64_t *late_rows,
                                       int64_t *sweeps);
+/* Query 19's K (q19.rs:38 TOP_BIDS; default 10, 1..65536).
+ * DBSP_ERR_INVALID on another query or after the engine's first step. */
+dbsp_status dbsp_engine_topk_init(dbsp_engine *e, int64_t K);
+/* query 19 trace rows and the operator's cumulative counters (as
+ * dbsp_topk_stats); any out pointer may be null */
+dbsp_status dbsp_engine_topk_stats(dbsp_engine *e, int64_t *in_rows,
+                                   int64_t *out_rows, int64_t *groups_seen,
+                                   int64_t *groups_refilled,
+                                   int64_t *rows_gathered);
 dbsp_status dbsp_engine_destroy(dbsp_engine *e);
 
 /* C5 (query 100) setup: device-generates the n_trace-row (k, f64-bits, +1)

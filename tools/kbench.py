@@ -9,6 +9,7 @@ Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
                        python tools/kbench.py --only rolling [--roll-rows N]
                        python tools/kbench.py --only rolling_wm
                        python tools/kbench.py --only rolling_minmax [--roll-rows N]
+                       python tools/kbench.py --only topk [--topk-rows N ...]
 Prints one JSON line per primitive.
 """
 import argparse
@@ -616,6 +617,151 @@ def bench_truncate(ctx, L, n, reps=5, run=64):
     }
 
 
+TOPK_SHIFT = 40
+
+
+def _topk_stream(n_per, groups, n_delta, ticks, retract_frac, seed):
+    """Per-tick raw deltas over a trace of `groups` groups x n_per rows at the
+    even ranks (k = group << 40 | 2 * i, v = 0, w = +1).  Appends are distinct
+    new rows at odd ranks (v = tick + 1 keeps them distinct across ticks).
+    With retract_frac, that share of a tick takes back, for as many distinct
+    groups, the group's highest trace row not yet taken back: a member of its
+    current top-K unless appended rows have crowded it out."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    n_ret = int(n_delta * retract_frac)
+    assert n_ret <= groups
+    taken = torch.zeros(groups, dtype=torch.int64, device="cuda")
+    out = []
+    for t in range(ticks):
+        n_app = n_delta - n_ret
+        pos = torch.randperm(n_per * groups, generator=g,
+                             device="cuda")[:n_app]
+        k = ((pos // n_per) << TOPK_SHIFT) | (2 * (pos % n_per) + 1)
+        v = torch.full((n_app,), t + 1, dtype=torch.int64, device="cuda")
+        w = torch.ones(n_app, dtype=torch.int64, device="cuda")
+        if n_ret:
+            gr = torch.randperm(groups, generator=g, device="cuda")[:n_ret]
+            rk = (gr << TOPK_SHIFT) | (2 * (n_per - 1 - taken[gr]))
+            taken[gr] += 1
+            k = torch.cat([k, rk])
+            v = torch.cat([v, torch.zeros(n_ret, dtype=torch.int64,
+                                          device="cuda")])
+            w = torch.cat([w, -torch.ones(n_ret, dtype=torch.int64,
+                                          device="cuda")])
+        out.append((k.contiguous(), v.contiguous(), w.contiguous()))
+    torch.cuda.synchronize()
+    return out
+
+
+def bench_topk(ctx, L, n_trace, groups=1024, K=10, n_delta=40_000, ticks=12,
+               warm=2, retract_frac=0.01):
+    """Incremental top-K per group (dbsp_topk_step) on a trace of n_trace rows
+    in `groups` groups: (a) an append-only stream, (b) the same stream with
+    DBSP_TOPK_REFILL_ALL, (c) the recompute route: sort the delta, merge it
+    into ONE consolidated integral and run dbsp_topk over all of it (the diff
+    against the previous result, which that route also needs, is NOT
+    included: a lower bound), (d) a second stream where retract_frac of each
+    delta takes back a current top-K member.  Host clock around calls that end
+    in a stream synchronise; `warm` leading ticks are excluded."""
+    from dbsp_amd.engine import TopK
+    n_per = max(K + ticks + warm + 1, n_trace // groups)
+    n_trace = n_per * groups
+    tk = ((torch.arange(groups, dtype=torch.int64, device="cuda")
+           << TOPK_SHIFT).repeat_interleave(n_per)
+          | (2 * torch.arange(n_per, dtype=torch.int64,
+                              device="cuda")).repeat(groups))
+    tv = torch.zeros(n_trace, dtype=torch.int64, device="cuda")
+    tw = torch.ones(n_trace, dtype=torch.int64, device="cuda")
+    appends = _topk_stream(n_per, groups, n_delta, warm + ticks, 0.0, 23)
+    mixed = _topk_stream(n_per, groups, n_delta, warm + ticks, retract_frac, 29)
+
+    def run_op(stream, refill_all):
+        op = TopK(ctx, K, TOPK_SHIFT, refill_all=refill_all)
+        out = BatchStruct()
+        t0 = time.perf_counter()
+        assert L.dbsp_topk_step(op._h, tk.data_ptr(), tv.data_ptr(),
+                                tw.data_ptr(), n_trace, ctypes.byref(out)) == 0
+        load_ms = (time.perf_counter() - t0) * 1e3
+        assert out.len == K * groups
+        ctx.free_batch(out)
+        ms, rows_out, refilled, gathered = [], [], [], []
+        prev = op.stats()
+        for i, (k, v, w) in enumerate(stream):
+            out = BatchStruct()
+            ctx.sync()
+            t0 = time.perf_counter()
+            assert L.dbsp_topk_step(op._h, k.data_ptr(), v.data_ptr(),
+                                    w.data_ptr(), len(k),
+                                    ctypes.byref(out)) == 0
+            dt = (time.perf_counter() - t0) * 1e3
+            st = op.stats()
+            if i >= warm:
+                ms.append(dt)
+                rows_out.append(out.len)
+                refilled.append(st["groups_refilled"] - prev["groups_refilled"])
+                gathered.append(st["rows_gathered"] - prev["rows_gathered"])
+            prev = st
+            ctx.free_batch(out)
+        op.close()
+        return {"load_ms": round(load_ms, 2),
+                "ms_per_step": [round(x, 3) for x in ms],
+                "ms_median": round(_med(ms), 3),
+                "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                "rows_out_per_tick": rows_out,
+                "groups_refilled_per_tick": refilled,
+                "rows_gathered_per_tick": gathered,
+                "in_rows": prev["in_rows"], "in_batches": prev["in_batches"],
+                "out_rows": prev["out_rows"],
+                "out_batches": prev["out_batches"]}
+
+    a = run_op(appends, False)
+    b = run_op(appends, True)
+    d = run_op(mixed, False)
+
+    # ---- (c) recompute: consolidated integral + batch primitive ----
+    integral = as_batch(tk, tv, tw)
+    owned = False
+    full_ms = []
+    for i, (k, v, w) in enumerate(appends):
+        ctx.sync()
+        t0 = time.perf_counter()
+        dl = BatchStruct()
+        assert L.dbsp_sort_consolidate(ctx._h, k.data_ptr(), v.data_ptr(),
+                                       w.data_ptr(), len(k),
+                                       ctypes.byref(dl)) == 0
+        m = BatchStruct()
+        assert L.dbsp_merge(ctx._h, ctypes.byref(integral), ctypes.byref(dl),
+                            ctypes.byref(m)) == 0
+        res = BatchStruct()
+        assert L.dbsp_topk(ctx._h, ctypes.byref(m), K, TOPK_SHIFT,
+                           ctypes.byref(res)) == 0
+        ctx.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        if i >= warm:
+            full_ms.append(dt)
+        ctx.free_batch(dl)
+        ctx.free_batch(res)
+        if owned:
+            ctx.free_batch(integral)
+        integral, owned = m, True
+    if owned:
+        ctx.free_batch(integral)
+    return {
+        "primitive": "dbsp_topk_step (incremental top-K per group) vs "
+                     "refill_all vs merge + dbsp_topk over the trace",
+        "trace_rows": n_trace, "groups": groups, "k": K,
+        "delta_rows": n_delta, "ticks": ticks, "warmup_ticks": warm,
+        "retract_frac": retract_frac,
+        "a_append_only": a, "b_append_only_refill_all": b,
+        "c_recompute_ms_per_step": [round(x, 3) for x in full_ms],
+        "c_recompute_ms_median": round(_med(full_ms), 3),
+        "c_recompute_ms_min": round(min(full_ms), 3),
+        "c_recompute_ms_max": round(max(full_ms), 3),
+        "c_recompute_excludes": "diff against the previous result",
+        "d_with_retractions": d,
+    }
+
+
 def bench_rolling_wm(ctx, L, args):
     yield bench_rolling_wm_operator(ctx, L, args.roll_parts, args.roll_delta,
                                     args.roll_late, args.roll_before,
@@ -633,7 +779,11 @@ def main():
     ap.add_argument("--sort-rows", type=int, default=50_000_000)
     ap.add_argument("--only", default=None,
                     choices=["merge", "join", "sort", "incremental", "c5",
-                             "rolling", "rolling_wm", "rolling_minmax"])
+                             "rolling", "rolling_wm", "rolling_minmax",
+                             "topk"])
+    ap.add_argument("--topk-rows", type=int, nargs="*",
+                    default=[4_000_000, 16_000_000, 64_000_000],
+                    help="topk leg: trace rows")
     ap.add_argument("--wm-ticks", type=int, default=200,
                     help="rolling_wm leg: ticks of the frontier stream")
     ap.add_argument("--wm-lateness", type=int, default=1024)
@@ -675,6 +825,9 @@ def main():
                 ctx, L, args.roll_rows, args.roll_parts, args.roll_delta,
                 args.roll_late, args.roll_before, args.roll_after,
                 args.roll_ticks, agg=agg)), flush=True)
+    if args.only == "topk":             # on request only, as the rolling leg
+        for n in args.topk_rows:
+            print(json.dumps(bench_topk(ctx, L, n)), flush=True)
     if args.only == "rolling_wm":       # on request only, as the rolling leg
         for res in bench_rolling_wm(ctx, L, args):
             print(json.dumps(res), flush=True)
