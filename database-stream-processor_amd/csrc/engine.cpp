@@ -945,6 +945,33 @@ struct TopKOp {
     }
 };
 
+// Incremental antijoin / semijoin: A restricted to the keys absent from
+// (DBSP_ANTIJOIN) or present in (DBSP_SEMIJOIN) a key set B, kept up to date
+// (Stream::antijoin, operator/join.rs:294-320, which composes it as
+// A - A |><| distinct(B); the semijoin is the subtracted term, join.rs:313).
+// A key is present iff its total weight in the integral of B is > 0
+// (operator/distinct.rs).  a_sp is the integral of A, b_sp the integral of
+// B's keys as rows (k, 0, w), both EXCLUDING the current tick on entry;
+// step() is defined below the spine helpers it uses.
+struct AntiJoinOp {
+    bool anti = true;  // DBSP_ANTIJOIN
+    Spine a_sp, b_sp;
+    // cumulative: keys whose presence flipped, rows of the A integral
+    // (consolidated) that a flip re-emitted, delta rows the filter dropped
+    int64_t keys_flipped = 0, rows_gathered = 0, rows_filtered = 0;
+
+    // da: consolidated rows, db: consolidated key rows (k, 0, w); both
+    // retained by the caller, either may be empty.  out: the tick's
+    // consolidated output delta.  Any row and any key is valid.
+    dbsp_status step(dbsp_ctx *c, const DevBatch &da, const DevBatch &db,
+                     DevBatch &out);
+
+    void clear(dbsp_ctx *c) {
+        a_sp.clear(c);
+        b_sp.clear(c);
+    }
+};
+
 // ---- pieces of the keyed-aggregate stage, shared with their test probes ----
 
 // The small join route (delta.n <= 8192): probe and single-workgroup scan,
@@ -1731,14 +1758,19 @@ struct dbsp_engine {
     // query 19 state: the top K bids of every auction
     TopKOp topk;
     bool topk_stepped = false;  // topk_init is rejected after a step
+    // query 103 state: auctions antijoined with the bids' auction keys
+    AntiJoinOp anti;
 };
 
 extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
                                           int query, int rank, int world) {
     if (query != 0 && query != 3 && query != 4 && query != 5 &&
         query != 6 && query != 8 && query != 19 && query != 100 &&
-        query != 101 && query != 102)
+        query != 101 && query != 102 && query != 103)
         return DBSP_ERR_INVALID;
+    // query 103 would shard correctly by k, but no multi-rank run of it has
+    // been made
+    if (query == 103 && world > 1) return DBSP_ERR_INVALID;
     // the exchange hashes k, which for query 19 packs the price under the
     // auction: it would split a group across ranks
     if (query == 19 && world > 1) return DBSP_ERR_INVALID;
@@ -1783,6 +1815,7 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
         s->clear(c);
     e->roll.clear(c);
     e->topk.clear(c);
+    e->anti.clear(c);
     free_batch(c, e->win.maxout);
     free_batch(c, e->q6_foldout);
     free_batch(c, e->maxin_int);
@@ -4638,6 +4671,9 @@ static dbsp_status c5_step(dbsp_engine *e, int64_t lo, int64_t hi) {
 // query 19's tick, defined with its operator at the end of this file
 static dbsp_status q19_step(dbsp_engine *e, const dbsp_event *d_ev,
                             int64_t n);
+// query 103's tick, likewise
+static dbsp_status q103_step(dbsp_engine *e, const dbsp_event *d_ev,
+                             int64_t n);
 
 extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
                                                int64_t hi) {
@@ -4669,6 +4705,7 @@ extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
         case 19: return q19_step(e, d_ev, hi - lo);
         case 101:
         case 102: return q101_step(e, d_ev, hi - lo);
+        case 103: return q103_step(e, d_ev, hi - lo);
     }
     return DBSP_ERR_INVALID;
 }
@@ -4718,6 +4755,7 @@ extern "C" dbsp_status dbsp_engine_step(dbsp_engine *e, const dbsp_event *events
         case 19: st = q19_step(e, d_ev, n); break;
         case 101:
         case 102: st = q101_step(e, d_ev, n); break;
+        case 103: st = q103_step(e, d_ev, n); break;
         default: st = DBSP_ERR_INVALID;
     }
     (void)dbspk::cache_free(d_ev, c->stream);
@@ -4975,5 +5013,216 @@ extern "C" dbsp_status dbsp_engine_topk_stats(dbsp_engine *e, int64_t *in_rows,
     if (groups_seen) *groups_seen = e->topk.groups_seen;
     if (groups_refilled) *groups_refilled = e->topk.groups_refilled;
     if (rows_gathered) *rows_gathered = e->topk.rows_gathered;
+    return DBSP_OK;
+}
+
+// ---- incremental antijoin / semijoin (Stream::antijoin, join.rs:294-320) ----
+//   d(A |> B) = dA * [k not in B'] + A * ([k not in B'] - [k not in B])
+// with A, B the integrals before the tick and B' the key set after it.  Per
+// tick, over consolidated DA and DB:
+//   flip     every key of DB against b_sp BEFORE the tick:
+//            flip = [before + dw > 0] - [before > 0]; the flipped keys are
+//            compacted with their multiplier (-flip antijoin, +flip semijoin)
+//   gather   the flipped keys' runs out of a_sp, BEFORE DA goes in, weights
+//            times the multiplier, consolidated: G.  No flip, no gather.
+//   insert   DB into b_sp
+//   filter   a row of DA is kept iff (antijoin) != (its key present in b_sp
+//            now): F, rows_filtered counts the rest
+//   insert   DA into a_sp
+//   output   consolidate(F ++ G): both are consolidated, so one merge
+// Nothing else of either trace is read: step cost follows the delta and the
+// flipped keys' runs.  The explicit per-op path (a host length sync per
+// phase, as q4/q6, the rolling operator and top-K); no chaining.  No row and
+// no key is invalid, so nothing can fail after the first write to a spine
+// for a reason the caller controls.
+dbsp_status AntiJoinOp::step(dbsp_ctx *c, const DevBatch &da,
+                             const DevBatch &db, DevBatch &out) {
+    out = DevBatch{};
+    if (da.n == 0 && db.n == 0) return DBSP_OK;
+    ScopedTimer timer(c, 3, 0.0);
+    TRY(a_sp.cap_batches(c));
+    TRY(b_sp.cap_batches(c));
+    DevBatch G, F;
+    int64_t n_flip = 0, copied = 0;
+    if (db.n > 0) {
+        uint64_t *pb = nullptr;
+        TRY(dbspk::anti_flip(c->stream, db, trace_args_of(b_sp), anti, &pb,
+                             &n_flip));
+        ScratchBuf plan(c, pb);
+        if (n_flip > 0) {
+            DevBatch raw;
+            TRY(dbspk::keyrange_gather_mul(c->stream, pb,
+                                           (const int64_t *)(pb + n_flip),
+                                           n_flip, trace_args_of(a_sp), &raw));
+            copied = raw.n;
+            // a key's runs of several batches follow one another: sort them
+            TRY(sort_consolidate_batch(c, raw, G));
+        }
+        TRY(b_sp.insert_copy(c, db));
+        TRY(b_sp.cap_batches(c));
+    }
+    if (da.n > 0) {
+        TRY(dbspk::anti_filter(c->stream, da, trace_args_of(b_sp), anti, &F));
+        TRY(a_sp.insert_copy(c, da));
+    }
+    const int64_t moved = db.n + da.n + 2 * copied + F.n;
+    keys_flipped += n_flip;
+    rows_gathered += G.n;
+    rows_filtered += da.n - F.n;
+    if (G.n == 0) {
+        free_batch(c, G);
+        out = F;
+    } else if (F.n == 0) {
+        out = G;
+    } else {
+        TRY(merge_batches(c, F, G, out));
+        free_batch(c, F);
+        free_batch(c, G);
+    }
+    if (out.n == 0) free_batch(c, out);
+    timer.bytes = 24.0 * (double)moved;
+    return DBSP_OK;
+}
+
+struct dbsp_antijoin_op {
+    dbsp_ctx *ctx = nullptr;
+    AntiJoinOp op;
+};
+
+static bool antijoin_mode_valid(int mode) {
+    return mode == DBSP_ANTIJOIN || mode == DBSP_SEMIJOIN;
+}
+
+// raw keys (k, w) as consolidated key rows (k, 0, w)
+static dbsp_status key_rows(dbsp_ctx *c, const uint64_t *bk, const int64_t *bw,
+                            int64_t nb, DevBatch &out) {
+    out = DevBatch{};
+    if (nb == 0) return DBSP_OK;
+    DevBatch raw;
+    TRY(alloc_batch(c, nb, raw));
+    HIP_CHECK_ST(hipMemcpyAsync(raw.k, bk, nb * 8, hipMemcpyDeviceToDevice,
+                                c->stream));
+    HIP_CHECK_ST(hipMemsetAsync(raw.v, 0, nb * 8, c->stream));
+    HIP_CHECK_ST(hipMemcpyAsync(raw.w, bw, nb * 8, hipMemcpyDeviceToDevice,
+                                c->stream));
+    return sort_consolidate_batch(c, raw, out);
+}
+
+// the filter alone over a caller's batch and key set: the recompute route
+extern "C" dbsp_status dbsp_antijoin(dbsp_ctx *c, const dbsp_batch *a,
+                                     const uint64_t *bk, const int64_t *bw,
+                                     int64_t nb, int mode, dbsp_batch *out) {
+    if (!c || !a || !out || a->len < 0 || nb < 0 || !antijoin_mode_valid(mode))
+        return DBSP_ERR_INVALID;
+    TraceArgs t{};
+    if (nb > 0)
+        trace_push(t, DevBatch{(uint64_t *)bk, (uint64_t *)bk, (int64_t *)bw,
+                               nb});
+    DevBatch res;
+    {
+        ScopedTimer timer(c, 3, 0.0);
+        TRY(dbspk::anti_filter(c->stream, as_batch(a), t,
+                               mode == DBSP_ANTIJOIN, &res));
+        timer.bytes = 24.0 * (double)(a->len + nb + res.n);
+    }
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_antijoin_create(dbsp_ctx *c, int mode,
+                                            dbsp_antijoin_op **out) {
+    if (!c || !out || !antijoin_mode_valid(mode)) return DBSP_ERR_INVALID;
+    dbsp_antijoin_op *t = new dbsp_antijoin_op();
+    t->ctx = c;
+    t->op.anti = mode == DBSP_ANTIJOIN;
+    *out = t;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_antijoin_step(dbsp_antijoin_op *t,
+                                          const uint64_t *ak,
+                                          const uint64_t *av,
+                                          const int64_t *aw, int64_t na,
+                                          const uint64_t *bk,
+                                          const int64_t *bw, int64_t nb,
+                                          dbsp_batch *out) {
+    if (!t || !out || na < 0 || nb < 0) return DBSP_ERR_INVALID;
+    dbsp_ctx *c = t->ctx;
+    *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
+    if (na == 0 && nb == 0) return DBSP_OK;
+    DevBatch da, db, res;
+    if (na > 0) {
+        DevBatch raw;
+        TRY(alloc_batch(c, na, raw));
+        TRY(copy_cols(c, raw, 0, ak, av, aw, na));
+        TRY(sort_consolidate_batch(c, raw, da));
+    }
+    dbsp_status st = key_rows(c, bk, bw, nb, db);
+    if (st == DBSP_OK) st = t->op.step(c, da, db, res);
+    free_batch(c, da);
+    free_batch(c, db);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    if (st != DBSP_OK) return st;
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_antijoin_stats(dbsp_antijoin_op *t,
+                                           int64_t *a_rows, int *a_batches,
+                                           int64_t *b_rows, int *b_batches,
+                                           int64_t *keys_flipped,
+                                           int64_t *rows_gathered,
+                                           int64_t *rows_filtered) {
+    if (!t) return DBSP_ERR_INVALID;
+    if (a_rows) *a_rows = t->op.a_sp.total();
+    if (a_batches) *a_batches = (int)t->op.a_sp.batches.size();
+    if (b_rows) *b_rows = t->op.b_sp.total();
+    if (b_batches) *b_batches = (int)t->op.b_sp.batches.size();
+    if (keys_flipped) *keys_flipped = t->op.keys_flipped;
+    if (rows_gathered) *rows_gathered = t->op.rows_gathered;
+    if (rows_filtered) *rows_filtered = t->op.rows_filtered;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_antijoin_destroy(dbsp_antijoin_op *t) {
+    if (!t) return DBSP_OK;
+    t->op.clear(t->ctx);
+    (void)hipStreamSynchronize(t->ctx->stream);
+    delete t;
+    return DBSP_OK;
+}
+
+// ---- query 103: auctions nobody has bid on yet ----
+// auctions.map_index(|a| (a.id, a.seller))
+//     .antijoin(&bids.map_index(|b| (b.auction, ())))
+// (Stream::antijoin, join.rs:294-320).  The flatmap's stream 0 carries the
+// auctions as (id, seller, w), stream 1 the bids as key rows (auction, 0, w);
+// the output rows are the auction rows, signed.
+static dbsp_status q103_step(dbsp_engine *e, const dbsp_event *d_ev,
+                             int64_t n) {
+    dbsp_ctx *c = e->ctx;
+    engine_free_output(e);
+    DevBatch da, db;
+    TRY(build_deltas(e, d_ev, n, da, db, true));
+    const dbsp_status st = e->anti.step(c, da, db, e->output);
+    free_batch(c, da);
+    free_batch(c, db);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return st;
+}
+
+extern "C" dbsp_status dbsp_engine_antijoin_stats(dbsp_engine *e,
+                                                  int64_t *a_rows,
+                                                  int64_t *b_rows,
+                                                  int64_t *keys_flipped,
+                                                  int64_t *rows_gathered,
+                                                  int64_t *rows_filtered) {
+    if (!e || e->query != 103) return DBSP_ERR_INVALID;
+    if (a_rows) *a_rows = e->anti.a_sp.total();
+    if (b_rows) *b_rows = e->anti.b_sp.total();
+    if (keys_flipped) *keys_flipped = e->anti.keys_flipped;
+    if (rows_gathered) *rows_gathered = e->anti.rows_gathered;
+    if (rows_filtered) *rows_filtered = e->anti.rows_filtered;
     return DBSP_OK;
 }

@@ -4101,6 +4101,12 @@ __global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_topk(
         uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
         uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1);
 
+// query 103's front, defined with the antijoin kernels below
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_auction_bidkey(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1);
+
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
                                  const Rows &out0, const Rows &out1,
@@ -4114,6 +4120,11 @@ dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
             ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1);
     else if (n > 0 && query == 19)
         k_flatmap_bid_topk<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
+            ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1, out1.k,
+            out1.v, out1.w, out1.n);
+    else if (n > 0 && query == 103)
+        k_flatmap_auction_bidkey<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0,
+                                   s>>>(
             ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1, out1.k,
             out1.v, out1.w, out1.n);
     else if (n > 0)
@@ -5346,6 +5357,234 @@ __global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_topk(
         }
         if (p1 && pos1 < (uint64_t)cap1) {
             k1[pos1] = auction; v1[pos1] = price; w1[pos1] = w;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Incremental antijoin / semijoin (Stream::antijoin, operator/join.rs:294-320:
+// A - A |><| distinct(B), as ONE operator over two spines).  The right side is
+// a key set stored as rows (k, 0, w); a key is PRESENT iff its total weight
+// over every batch of its spine is > 0 (operator/distinct.rs), so a key at
+// net -1 is absent.
+//   k_anti_flip            per key of the consolidated dB: its weight in the
+//                          right spine before the tick (one lower_bound_k per
+//                          batch, a batch holds a key at most once) ->
+//                          flip = [before + dw > 0] - [before > 0]
+//   k_anti_flip_emit       flags + scan -> the flipped keys and their signed
+//                          multiplier (-flip antijoin, +flip semijoin)
+//   k_keyrange_count       the flipped keys' runs of the left spine
+//   k_range_emit_mul       k_range_emit with a multiplier per range instead
+//                          of one sign per launch, over the OUTPUT index space
+//   k_anti_heads           key-head flags of the consolidated dA
+//   k_anti_present         one search per key HEAD: present after the tick
+//   k_anti_keep            a row is kept iff anti != present[its head]
+//   k_anti_emit            flags + scan -> the kept rows
+// Every data-dependent size is flags -> scan -> emit; nothing passes between
+// workgroups.
+// ---------------------------------------------------------------------------
+
+// total weight of key over every batch of a key-set spine
+__device__ inline int64_t anti_weight(const TraceArgs &t, uint64_t key) {
+    int64_t sum = 0;
+    for (int b = 0; b < t.nb; b++) {
+        const int64_t nb = t.n[b];
+        const int64_t j = lower_bound_k(t.k[b], nb, key);
+        if (j < nb && t.k[b][j] == key) sum += t.w[b][j];
+    }
+    return sum;
+}
+
+__global__ void k_anti_flip(const uint64_t *bk, const int64_t *bw, int64_t n,
+                            TraceArgs t, int64_t *flip, uint64_t *flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t before = anti_weight(t, bk[i]);
+        const int64_t f =
+            (int64_t)(before + bw[i] > 0) - (int64_t)(before > 0);
+        flip[i] = f;
+        flags[i] = f != 0;
+    }
+}
+
+__global__ void k_anti_flip_emit(const uint64_t *bk, const int64_t *flip,
+                                 const uint64_t *flags, const uint64_t *fscan,
+                                 int64_t n, int64_t sign, uint64_t *fkey,
+                                 int64_t *fmul) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t o = fscan[i];
+        fkey[o] = bk[i];
+        fmul[o] = sign * flip[i];
+    }
+}
+
+// k_range_emit with the weight multiplier read per range (pair j belongs to
+// range j / t.nb): one thread per OUTPUT row, so a key with 100,000 values
+// costs 100,000 threads, not one thread's loop
+__global__ void k_range_emit_mul(TraceArgs t, int64_t np,
+                                 const uint64_t *offsets, const uint64_t *start,
+                                 int64_t n_out, const int64_t *mul,
+                                 uint64_t *ok, uint64_t *ov, int64_t *ow) {
+    for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < n_out;
+         o += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = upper_bound_k(offsets, np, (uint64_t)o) - 1;
+        const int b = (int)(j % t.nb);
+        const int64_t src = (int64_t)start[j] + (o - (int64_t)offsets[j]);
+        ok[o] = t.k[b][src];
+        ov[o] = t.v[b][src];
+        ow[o] = mul[j / t.nb] * t.w[b][src];
+    }
+}
+
+__global__ void k_anti_heads(const uint64_t *ak, int64_t n, uint64_t *heads) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        heads[i] = i == 0 || ak[i - 1] != ak[i];
+}
+
+// present[h]: the key of head number h is present in the key-set spine
+__global__ void k_anti_present(const uint64_t *ak, int64_t n,
+                               const uint64_t *heads, const uint64_t *hscan,
+                               TraceArgs t, uint64_t *present) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!heads[i]) continue;
+        present[hscan[i]] = anti_weight(t, ak[i]) > 0;
+    }
+}
+
+// row 0 is a head, so hscan[i] + heads[i] - 1 is the row's head number
+__global__ void k_anti_keep(int64_t n, const uint64_t *heads,
+                            const uint64_t *hscan, const uint64_t *present,
+                            int anti, uint64_t *flags) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        flags[i] = (anti != 0) != (present[hscan[i] + heads[i] - 1] != 0);
+}
+
+__global__ void k_anti_emit(const uint64_t *ak, const uint64_t *av,
+                            const int64_t *aw, int64_t n, const uint64_t *flags,
+                            const uint64_t *fscan, uint64_t *ok, uint64_t *ov,
+                            int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t o = fscan[i];
+        ok[o] = ak[i]; ov[o] = av[i]; ow[o] = aw[i];
+    }
+}
+
+dbsp_status anti_flip(hipStream_t s, const Rows &db, const TraceArgs &t,
+                      bool anti, uint64_t **plan, int64_t *n_flip) {
+    const int64_t n = db.n;
+    *plan = nullptr;
+    *n_flip = 0;
+    if (n <= 0) return DBSP_OK;
+    Scratch sc(s);
+    uint64_t *flags, *fscan, *pb;
+    int64_t *flip;
+    HIP_CHECK(sc.get(&flip, n * sizeof(int64_t)));
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_anti_flip<<<grid_for(n), BLK, 0, s>>>(db.k, db.w, n, t, flip, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));
+    if (total == 0) return DBSP_OK;
+    HIP_CHECK(sc.get(&pb, 2 * total * sizeof(uint64_t)));
+    k_anti_flip_emit<<<grid_for(n), BLK, 0, s>>>(
+        db.k, flip, flags, fscan, n, anti ? -1 : 1, pb,
+        (int64_t *)(pb + total));
+    *n_flip = (int64_t)total;
+    sc.keep(pb);
+    *plan = pb;
+    return DBSP_OK;
+}
+
+dbsp_status keyrange_gather_mul(hipStream_t s, const uint64_t *keys,
+                                const int64_t *mul, int64_t nr,
+                                const TraceArgs &t, Rows *out) {
+    if (nr <= 0 || t.nb <= 0) return no_rows(out);
+    const int64_t np = nr * t.nb;
+    Scratch sc(s);
+    uint64_t *cnt, *start;
+    HIP_CHECK(sc.get(&cnt, np * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&start, np * sizeof(uint64_t)));
+    k_keyrange_count<<<grid_for(np), BLK, 0, s>>>(keys, keys, nr, t, cnt,
+                                                  start);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, cnt, cnt, np, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_range_emit_mul<<<grid_for((int64_t)total), BLK, 0, s>>>(
+        t, np, cnt, start, (int64_t)total, mul, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+dbsp_status anti_filter(hipStream_t s, const Rows &a, const TraceArgs &t,
+                        bool anti, Rows *out) {
+    const int64_t n = a.n;
+    if (n <= 0) return no_rows(out);
+    Scratch sc(s);
+    uint64_t *heads, *hscan, *present, *flags;
+    HIP_CHECK(sc.get(&heads, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&hscan, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&present, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    k_anti_heads<<<grid_for(n), BLK, 0, s>>>(a.k, n, heads);
+    TRY_K(scan_exclusive(s, heads, hscan, n, nullptr));
+    k_anti_present<<<grid_for(n), BLK, 0, s>>>(a.k, n, heads, hscan, t,
+                                               present);
+    k_anti_keep<<<grid_for(n), BLK, 0, s>>>(n, heads, hscan, present, anti,
+                                            flags);
+    // the head flags are spent: their column takes the second scan
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, heads, n, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_anti_emit<<<grid_for(n), BLK, 0, s>>>(a.k, a.v, a.w, n, flags, heads,
+                                            r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+// Query 103's front (auctions.map_index(|a| (a.id, a.seller)) and
+// bids.map_index(|b| (b.auction, ()))), a kernel of its own as
+// k_flatmap_bid_tv is, so that k_flatmap (on q3's measured path) stays as it
+// is.  Stream 0: auctions as (id, seller, w); stream 1: bids as the key rows
+// (auction, 0, w) of the antijoin's right side.
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_auction_bidkey(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1) {
+    __shared__ uint32_t s_cnt[2][FLATMAP_WAVES];
+    __shared__ unsigned long long s_base[2][FLATMAP_WAVES];
+    const int64_t stride = (int64_t)gridDim.x * FLATMAP_BLK;
+    for (int64_t base = blockIdx.x * (int64_t)FLATMAP_BLK; base < n;
+         base += stride) {
+        const int64_t i = base + threadIdx.x;
+        uint64_t kind = 0, f0 = 0, f1 = 0;
+        int64_t w = 0;
+        if (i < n) {
+            if (cols.kind) {
+                kind = cols.kind[i]; f0 = cols.f0[i]; f1 = cols.f1[i];
+                w = cols.w[i];
+            } else {
+                const dbsp_event e = ev[i];
+                kind = e.kind; f0 = e.f0; f1 = e.f1; w = e.w;
+            }
+        }
+        const bool p0 = i < n && kind == 1, p1 = i < n && kind == 2;
+        uint64_t pos0, pos1;
+        block_append2((unsigned long long *)c0, (unsigned long long *)c1, p0,
+                      p1, s_cnt, s_base, pos0, pos1);
+        if (p0 && pos0 < (uint64_t)cap0) {
+            k0[pos0] = f0; v0[pos0] = f1; w0[pos0] = w;
+        }
+        if (p1 && pos1 < (uint64_t)cap1) {
+            k1[pos1] = f0; v1[pos1] = 0; w1[pos1] = w;
         }
     }
 }

@@ -477,6 +477,28 @@ dbsp_status topk_candidates(hipStream_t s, const Rows &delta,
 dbsp_status topk_select(hipStream_t s, const Rows &slice, int64_t K, int shift,
                         Rows *out);
 
+// ---- incremental antijoin / semijoin (Stream::antijoin, operator/join.rs:
+// 294-320).  The right side is a key set held as rows (k, 0, w); a key is
+// present iff its total weight over every batch is > 0 (operator/distinct.rs).
+// The kernels read k and w of a key-set batch, never v ----
+// Per key of the consolidated key delta db (distinct keys, v unread):
+// flip = [before + dw > 0] - [before > 0] with before its weight in t BEFORE
+// the tick.  *plan is one 2*n_flip-word device buffer (caller frees with
+// cache_free; null when nothing flips) [key | mul]: the flipped keys in order
+// and mul (int64) = -flip for the antijoin, +flip for the semijoin.  One host
+// sync.
+dbsp_status anti_flip(hipStream_t s, const Rows &db, const TraceArgs &t,
+                      bool anti, uint64_t **plan, int64_t *n_flip);
+// copy the rows of every spine batch with k == keys[r], weights times
+// mul[r]; keys distinct, output RAW (key-major, batch-minor runs)
+dbsp_status keyrange_gather_mul(hipStream_t s, const uint64_t *keys,
+                                const int64_t *mul, int64_t nr,
+                                const TraceArgs &t, Rows *out);
+// the rows of a consolidated batch a whose key is absent from (anti) or
+// present in (!anti) the key set t, in order: one search per key head
+dbsp_status anti_filter(hipStream_t s, const Rows &a, const TraceArgs &t,
+                        bool anti, Rows *out);
+
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 
 }  // namespace dbspk

@@ -235,6 +235,29 @@ def _L():
         L.dbsp_engine_topk_init.argtypes = [vp, i64]
         L.dbsp_engine_topk_stats.restype = i32
         L.dbsp_engine_topk_stats.argtypes = [vp] + [ctypes.POINTER(i64)] * 5
+        L.dbsp_antijoin.restype = i32
+        L.dbsp_antijoin.argtypes = [vp, ctypes.POINTER(BatchStruct), vp, vp,
+                                    i64, ctypes.c_int,
+                                    ctypes.POINTER(BatchStruct)]
+        L.dbsp_antijoin_create.restype = i32
+        L.dbsp_antijoin_create.argtypes = [vp, ctypes.c_int,
+                                           ctypes.POINTER(vp)]
+        L.dbsp_antijoin_step.restype = i32
+        L.dbsp_antijoin_step.argtypes = [vp, vp, vp, vp, i64, vp, vp, i64,
+                                         ctypes.POINTER(BatchStruct)]
+        L.dbsp_antijoin_stats.restype = i32
+        L.dbsp_antijoin_stats.argtypes = [vp, ctypes.POINTER(i64),
+                                          ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(i64),
+                                          ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(i64),
+                                          ctypes.POINTER(i64),
+                                          ctypes.POINTER(i64)]
+        L.dbsp_antijoin_destroy.restype = i32
+        L.dbsp_antijoin_destroy.argtypes = [vp]
+        L.dbsp_engine_antijoin_stats.restype = i32
+        L.dbsp_engine_antijoin_stats.argtypes = (
+            [vp] + [ctypes.POINTER(i64)] * 5)
         L.dbsp_engine_c5_init.restype = i32
         L.dbsp_engine_c5_init.argtypes = [vp, i64, i64, u64]
         L.dbsp_engine_kernel_stats.restype = i32
@@ -710,6 +733,25 @@ class Ctx:
         self.free_batch(out)
         return res
 
+    def antijoin(self, a_rows, b_keys, mode=0):
+        """The rows of a consolidated batch whose key is absent from
+        (ANTIJOIN) or present in (SEMIJOIN) a key set, in order: the
+        recompute route of `AntiJoin`.  b_keys: rows (k, ignored, w) of
+        sorted distinct keys with non-zero weights; a key is present iff its
+        weight is > 0."""
+        inp = self.upload_rows(a_rows)
+        keys = self.upload_rows(b_keys)
+        out = BatchStruct()
+        st = self._lib.dbsp_antijoin(self._h, ctypes.byref(inp), keys.k,
+                                     keys.w, keys.len, mode,
+                                     ctypes.byref(out))
+        self.free_batch(inp)
+        self.free_batch(keys)
+        _check(st, "antijoin")
+        res = self.download_rows(out)
+        self.free_batch(out)
+        return res
+
     def shard_partition(self, rows, nshards):
         inp = self.upload_rows(rows)
         out = BatchStruct()
@@ -878,6 +920,67 @@ class TopK:
                 "rows_gathered": rg.value}
 
 
+ANTIJOIN, SEMIJOIN = 0, 1  # DBSP_ANTIJOIN, DBSP_SEMIJOIN
+
+
+class AntiJoin:
+    """Stateful incremental antijoin (Stream::antijoin) or semijoin.  Left
+    rows are (k, v, w); the right side is a key set, rows (k, ignored, w).
+    A key is present iff its total weight in the right side's integral is
+    > 0.  The maintained relation is the left integral restricted to the
+    absent (ANTIJOIN) or present (SEMIJOIN) keys; each step returns the
+    tick's consolidated change of it.  The semijoin keeps a left row's own
+    weight: it is A joined with distinct(B), not the reference's per-batch
+    semijoin_stream."""
+
+    def __init__(self, ctx: Ctx, mode=ANTIJOIN):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        _check(self._lib.dbsp_antijoin_create(ctx._h, mode, ctypes.byref(h)),
+               "antijoin_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):
+                self._lib.dbsp_antijoin_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def step(self, a_rows: np.ndarray, b_keys: np.ndarray) -> np.ndarray:
+        """One tick: raw (unsorted, unconsolidated) left rows and right keys
+        in, either possibly empty; the consolidated output delta out."""
+        a = self._ctx.upload_rows(a_rows)
+        b = self._ctx.upload_rows(b_keys)
+        out = BatchStruct()
+        st = self._lib.dbsp_antijoin_step(self._h, a.k, a.v, a.w, a.len, b.k,
+                                          b.w, b.len, ctypes.byref(out))
+        self._ctx.free_batch(a)
+        self._ctx.free_batch(b)
+        _check(st, "antijoin_step")
+        res = self._ctx.download_rows(out)
+        self._ctx.free_batch(out)
+        return res
+
+    def stats(self) -> dict:
+        """a_rows / a_batches / b_rows / b_batches of the two traces and the
+        cumulative keys_flipped, rows_gathered, rows_filtered."""
+        ar, br = ctypes.c_int64(), ctypes.c_int64()
+        ab, bb = ctypes.c_int(), ctypes.c_int()
+        kf, rg, rf = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(self._lib.dbsp_antijoin_stats(
+            self._h, ctypes.byref(ar), ctypes.byref(ab), ctypes.byref(br),
+            ctypes.byref(bb), ctypes.byref(kf), ctypes.byref(rg),
+            ctypes.byref(rf)), "antijoin_stats")
+        return {"a_rows": ar.value, "a_batches": ab.value,
+                "b_rows": br.value, "b_batches": bb.value,
+                "keys_flipped": kf.value, "rows_gathered": rg.value,
+                "rows_filtered": rf.value}
+
+
 def xxh3_u64(key, seed=0x7F95EF85BE33C337):
     return _L().dbsp_xxh3_u64(key, seed)
 
@@ -955,6 +1058,15 @@ class Engine:
         return dict(zip(("in_rows", "out_rows", "groups_seen",
                          "groups_refilled", "rows_gathered"),
                         (x.value for x in vals)))
+
+    def antijoin_stats(self) -> dict:
+        """Query 103: a_rows, b_rows and the cumulative keys_flipped,
+        rows_gathered, rows_filtered."""
+        vals = [ctypes.c_int64() for _ in range(5)]
+        _check(self._lib.dbsp_engine_antijoin_stats(
+            self._h, *[ctypes.byref(x) for x in vals]), "antijoin_stats")
+        return dict(zip(("a_rows", "b_rows", "keys_flipped", "rows_gathered",
+                         "rows_filtered"), (x.value for x in vals)))
 
     def step_staged(self, lo, hi):
         _check(self._lib.dbsp_engine_step_staged(self._h, lo, hi), "step")

@@ -414,6 +414,75 @@ dbsp_status dbsp_topk_stats(dbsp_topk_op *op, int64_t *in_rows,
                             int64_t *groups_refilled, int64_t *rows_gathered);
 dbsp_status dbsp_topk_destroy(dbsp_topk_op *op);
 
+/* ---- incremental antijoin and semijoin ----
+ * SQL's NOT EXISTS / NOT IN (antijoin) and EXISTS / IN (semijoin), kept up
+ * to date; with dbsp_join_spine, the parts of LEFT / FULL OUTER JOIN.
+ * Replaces Stream::antijoin (crates/dbsp/src/operator/join.rs:294-320), which
+ * composes A - A |><| distinct(B) out of a distinct, a two-sided join and a
+ * minus; here it is one operator over two traces.
+ * Left rows are (k, v, w).  The right side is a KEY SET: keys (k, w), the
+ * case I2::Val = ().  A key is PRESENT iff its total weight in the integral
+ * of the right side is > 0, the distinct rule (operator/distinct.rs); a key
+ * at net -1 is absent.
+ *   DBSP_ANTIJOIN  A restricted to the keys absent from B: `antijoin`.
+ *   DBSP_SEMIJOIN  A restricted to the keys present in B: A |><| distinct(B),
+ *                  the term join.rs:313 subtracts.  It is NOT the reference's
+ *                  semijoin_stream (operator/semijoin.rs:38-142), the
+ *                  per-batch operator that multiplies a row's weight by its
+ *                  key's weight: here a left row keeps its own weight.
+ * Multi-valued right sides: the reference applies distinct() to the right
+ * side's (key, value) PAIRS before its join, so a key with m distinct present
+ * values yields weight w * (1 - m).  That follows from its composition, not
+ * from SQL; it is not reproduced.  Callers project the right side to its
+ * keys first, the case in which both agree.
+ * Out of scope: the outer join itself (DESIGN.md says how it composes),
+ * watermark-bounded state, sharded ranks. */
+#define DBSP_ANTIJOIN 0
+#define DBSP_SEMIJOIN 1
+
+/* The batch primitive (join.rs:298-319 over one batch and one key set): the
+ * rows of the consolidated batch `a` whose key is absent from (antijoin) or
+ * present in (semijoin) the key set, in order, weights unchanged.  bk/bw: nb
+ * sorted distinct keys in device memory with non-zero weights; a key of
+ * negative weight is absent.  An unknown mode is DBSP_ERR_INVALID.  out:
+ * device arrays owned by the caller, null when empty; host visible on
+ * return. */
+dbsp_status dbsp_antijoin(dbsp_ctx *ctx, const dbsp_batch *a,
+                          const uint64_t *bk, const int64_t *bw, int64_t nb,
+                          int mode, dbsp_batch *out);
+
+/* The stateful operator (antijoin's distinct, join and minus with their three
+ * traces, join.rs:298-319): the integrals of both sides, as spines. */
+typedef struct dbsp_antijoin_op dbsp_antijoin_op;
+/* circuit construction (Stream::antijoin, join.rs:294-297); the mode is fixed
+ * here, an unknown one is DBSP_ERR_INVALID */
+dbsp_status dbsp_antijoin_create(dbsp_ctx *ctx, int mode,
+                                 dbsp_antijoin_op **out);
+/* One tick of the composed circuit (distinct.rs:273 DistinctIncremental::eval,
+ * JoinTrace::eval for both sides, and the minus).  ak/av/aw: na raw
+ * (unsorted, unconsolidated) left rows, bk/bw: nb raw right keys, all in
+ * device memory; either side may be empty (its pointers then unread); any
+ * row and any key is valid.  out: the tick's consolidated change (device
+ * arrays owned by the caller, null when empty; host visible on return).  Both
+ * sides empty, or consolidating to nothing, change nothing and return an
+ * empty out.  Work per tick follows the deltas: the left trace is read only
+ * for keys whose presence FLIPS this tick, and a tick that flips no key
+ * reads none of it. */
+dbsp_status dbsp_antijoin_step(dbsp_antijoin_op *op, const uint64_t *ak,
+                               const uint64_t *av, const int64_t *aw,
+                               int64_t na, const uint64_t *bk,
+                               const int64_t *bw, int64_t nb, dbsp_batch *out);
+/* rows / spine batches of the two traces (Spine introspection,
+ * trace/spine_fueled.rs:107-119) and cumulative counters: keys whose presence
+ * flipped, rows of the left integral (consolidated) re-emitted under a flip,
+ * delta rows the filter dropped.  Any out pointer may be null. */
+dbsp_status dbsp_antijoin_stats(dbsp_antijoin_op *op, int64_t *a_rows,
+                                int *a_batches, int64_t *b_rows,
+                                int *b_batches, int64_t *keys_flipped,
+                                int64_t *rows_gathered,
+                                int64_t *rows_filtered);
+dbsp_status dbsp_antijoin_destroy(dbsp_antijoin_op *op);
+
 dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *ctx,
                                    const uint64_t *delta_keys, int64_t nd,
                                    const dbsp_batch *in_trace,
@@ -559,8 +628,9 @@ dbsp_status dbsp_agg_linear_upsert_f64(dbsp_ctx *ctx,
  * root scope): for each delta pair, out = [w_before + dw > 0] - [w_before > 0]
  * where w_before is the pair's total weight in the delayed integral (passed
  * as its spine batches: distinct is NOT linear in the trace).  The output is
- * consolidated by construction.  Unlocks antijoin/outer-join and Nexmark
- * q4/q6/q9. */
+ * consolidated by construction.  Unlocks Nexmark q4/q6/q9 (SURVEY.md
+ * §8f.2); the antijoin has an operator of its own, dbsp_antijoin_step, which
+ * applies this rule to a key set. */
 dbsp_status dbsp_distinct_inc(dbsp_ctx *ctx, const dbsp_batch *delta,
                               const dbsp_batch *trace_batches, int n_batches,
                               dbsp_batch *out);
@@ -617,7 +687,14 @@ typedef struct dbsp_engine dbsp_engine;
  *  auction >= 2^37, price >= 2^27, bidder >= 2^32 or date_time >= 2^32 makes
  *  the step DBSP_ERR_INVALID, detected on the device, with the state
  *  unchanged; the next tick is unaffected.  world > 1 is DBSP_ERR_INVALID at
- *  create: the exchange hashes k, which would split a group across ranks). */
+ *  create: the exchange hashes k, which would split a group across ranks), or
+ * 103 (auctions nobody has bid on yet:
+ *      auctions.map_index(|a| (a.id, a.seller))
+ *          .antijoin(&bids.map_index(|b| (b.auction, ())))
+ *  Stream::antijoin, join.rs:294-320, on the antijoin operator above; rows
+ *  (auction id, seller, w), output rows are input rows, signed.  world > 1
+ *  is DBSP_ERR_INVALID at create: sharding by k would be correct, but no
+ *  multi-rank run of it has been made). */
 dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
                                int rank, int world);
 
@@ -653,6 +730,12 @@ dbsp_status dbsp_engine_topk_stats(dbsp_engine *e, int64_t *in_rows,
                                    int64_t *out_rows, int64_t *groups_seen,
                                    int64_t *groups_refilled,
                                    int64_t *rows_gathered);
+/* query 103 trace rows and the operator's cumulative counters (as
+ * dbsp_antijoin_stats); any out pointer may be null */
+dbsp_status dbsp_engine_antijoin_stats(dbsp_engine *e, int64_t *a_rows,
+                                       int64_t *b_rows, int64_t *keys_flipped,
+                                       int64_t *rows_gathered,
+                                       int64_t *rows_filtered);
 dbsp_status dbsp_engine_destroy(dbsp_engine *e);
 
 /* C5 (query 100) setup: device-generates the n_trace-row (k, f64-bits, +1)

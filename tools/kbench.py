@@ -10,6 +10,7 @@ Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
                        python tools/kbench.py --only rolling_wm
                        python tools/kbench.py --only rolling_minmax [--roll-rows N]
                        python tools/kbench.py --only topk [--topk-rows N ...]
+                       python tools/kbench.py --only antijoin [--anti-rows N ...]
 Prints one JSON line per primitive.
 """
 import argparse
@@ -762,6 +763,131 @@ def bench_topk(ctx, L, n_trace, groups=1024, K=10, n_delta=40_000, ticks=12,
     }
 
 
+def bench_antijoin(ctx, L, n_trace, per_key=64, n_delta=40_000, n_flip=256,
+                   ticks=12, warm=2):
+    """Incremental antijoin (dbsp_antijoin_step) over a row trace of n_trace
+    rows, per_key values per key (k = key index, v = 0..per_key-1, w = +1),
+    with the even keys present in the key trace.  Every tick sends n_delta new
+    rows over uniform keys plus n_flip distinct keys whose presence flips
+    (-1 if present, +1 if absent), so about n_flip * per_key trace rows are
+    re-emitted.  Beside it the recompute route: sort both deltas, merge them
+    into ONE consolidated integral each and run dbsp_antijoin over all of it
+    (the diff against the previous result, which that route also needs, is
+    NOT included: a lower bound).  Host clock around calls that end in a
+    stream synchronise; `warm` leading ticks are excluded."""
+    from dbsp_amd.engine import AntiJoin, ANTIJOIN
+    nkeys = max(2 * n_flip, n_trace // per_key)
+    n_trace = nkeys * per_key
+    i64 = dict(dtype=torch.int64, device="cuda")
+    tk = torch.arange(nkeys, **i64).repeat_interleave(per_key)
+    tv = torch.arange(per_key, **i64).repeat(nkeys)
+    tw = torch.ones(n_trace, **i64)
+    bk = torch.arange(0, nkeys, 2, **i64)
+    bw = torch.ones(len(bk), **i64)
+    g = torch.Generator(device="cuda").manual_seed(31)
+    present = torch.zeros(nkeys, dtype=torch.bool, device="cuda")
+    present[bk] = True
+    stream = []
+    for t in range(warm + ticks):
+        ak = torch.randint(0, nkeys, (n_delta,), generator=g, **i64)
+        av = per_key + t * n_delta + torch.arange(n_delta, **i64)
+        aw = torch.ones(n_delta, **i64)
+        fk = torch.randperm(nkeys, generator=g, device="cuda")[:n_flip]
+        fw = torch.where(present[fk], -1, 1).to(torch.int64)
+        present[fk] = ~present[fk]
+        stream.append((ak, av, aw, fk.contiguous(), fw.contiguous()))
+    torch.cuda.synchronize()
+
+    op = AntiJoin(ctx, ANTIJOIN)
+    out = BatchStruct()
+    t0 = time.perf_counter()
+    assert L.dbsp_antijoin_step(op._h, tk.data_ptr(), tv.data_ptr(),
+                                tw.data_ptr(), n_trace, bk.data_ptr(),
+                                bw.data_ptr(), len(bk),
+                                ctypes.byref(out)) == 0
+    load_ms = (time.perf_counter() - t0) * 1e3
+    assert out.len == (nkeys - len(bk)) * per_key
+    ctx.free_batch(out)
+    ms, rows_out, flipped, gathered, filtered = [], [], [], [], []
+    prev = op.stats()
+    for i, (ak, av, aw, fk, fw) in enumerate(stream):
+        out = BatchStruct()
+        ctx.sync()
+        t0 = time.perf_counter()
+        assert L.dbsp_antijoin_step(op._h, ak.data_ptr(), av.data_ptr(),
+                                    aw.data_ptr(), len(ak), fk.data_ptr(),
+                                    fw.data_ptr(), len(fk),
+                                    ctypes.byref(out)) == 0
+        dt = (time.perf_counter() - t0) * 1e3
+        st = op.stats()
+        if i >= warm:
+            ms.append(dt)
+            rows_out.append(out.len)
+            flipped.append(st["keys_flipped"] - prev["keys_flipped"])
+            gathered.append(st["rows_gathered"] - prev["rows_gathered"])
+            filtered.append(st["rows_filtered"] - prev["rows_filtered"])
+        prev = st
+        ctx.free_batch(out)
+    op.close()
+    inc = {"load_ms": round(load_ms, 2),
+           "ms_per_step": [round(x, 3) for x in ms],
+           "ms_median": round(_med(ms), 3),
+           "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+           "rows_out_per_tick": rows_out, "keys_flipped_per_tick": flipped,
+           "rows_gathered_per_tick": gathered,
+           "rows_filtered_per_tick": filtered,
+           "a_rows": prev["a_rows"], "a_batches": prev["a_batches"],
+           "b_rows": prev["b_rows"], "b_batches": prev["b_batches"]}
+
+    # ---- recompute: consolidated integrals + the batch primitive ----
+    ia, ib = as_batch(tk, tv, tw), as_batch(bk, torch.zeros_like(bk), bw)
+    owned = False
+    full_ms = []
+    for i, (ak, av, aw, fk, fw) in enumerate(stream):
+        fz = torch.zeros_like(fk)
+        ctx.sync()
+        t0 = time.perf_counter()
+        da, db, ma, mb, res = (BatchStruct() for _ in range(5))
+        assert L.dbsp_sort_consolidate(ctx._h, ak.data_ptr(), av.data_ptr(),
+                                       aw.data_ptr(), len(ak),
+                                       ctypes.byref(da)) == 0
+        assert L.dbsp_sort_consolidate(ctx._h, fk.data_ptr(), fz.data_ptr(),
+                                       fw.data_ptr(), len(fk),
+                                       ctypes.byref(db)) == 0
+        assert L.dbsp_merge(ctx._h, ctypes.byref(ia), ctypes.byref(da),
+                            ctypes.byref(ma)) == 0
+        assert L.dbsp_merge(ctx._h, ctypes.byref(ib), ctypes.byref(db),
+                            ctypes.byref(mb)) == 0
+        assert L.dbsp_antijoin(ctx._h, ctypes.byref(ma), mb.k, mb.w, mb.len,
+                               ANTIJOIN, ctypes.byref(res)) == 0
+        ctx.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        if i >= warm:
+            full_ms.append(dt)
+        for b in (da, db, res):
+            ctx.free_batch(b)
+        if owned:
+            ctx.free_batch(ia)
+            ctx.free_batch(ib)
+        ia, ib, owned = ma, mb, True
+    if owned:
+        ctx.free_batch(ia)
+        ctx.free_batch(ib)
+    return {
+        "primitive": "dbsp_antijoin_step (incremental antijoin) vs merge + "
+                     "dbsp_antijoin over the traces",
+        "trace_rows": n_trace, "keys": nkeys, "values_per_key": per_key,
+        "delta_rows": n_delta, "keys_flipped": n_flip, "ticks": ticks,
+        "warmup_ticks": warm,
+        "incremental": inc,
+        "recompute_ms_per_step": [round(x, 3) for x in full_ms],
+        "recompute_ms_median": round(_med(full_ms), 3),
+        "recompute_ms_min": round(min(full_ms), 3),
+        "recompute_ms_max": round(max(full_ms), 3),
+        "recompute_excludes": "diff against the previous result",
+    }
+
+
 def bench_rolling_wm(ctx, L, args):
     yield bench_rolling_wm_operator(ctx, L, args.roll_parts, args.roll_delta,
                                     args.roll_late, args.roll_before,
@@ -780,7 +906,10 @@ def main():
     ap.add_argument("--only", default=None,
                     choices=["merge", "join", "sort", "incremental", "c5",
                              "rolling", "rolling_wm", "rolling_minmax",
-                             "topk"])
+                             "topk", "antijoin"])
+    ap.add_argument("--anti-rows", type=int, nargs="*",
+                    default=[4_000_000, 16_000_000, 64_000_000],
+                    help="antijoin leg: row-trace rows")
     ap.add_argument("--topk-rows", type=int, nargs="*",
                     default=[4_000_000, 16_000_000, 64_000_000],
                     help="topk leg: trace rows")
@@ -828,6 +957,9 @@ def main():
     if args.only == "topk":             # on request only, as the rolling leg
         for n in args.topk_rows:
             print(json.dumps(bench_topk(ctx, L, n)), flush=True)
+    if args.only == "antijoin":         # on request only, as the rolling leg
+        for n in args.anti_rows:
+            print(json.dumps(bench_antijoin(ctx, L, n)), flush=True)
     if args.only == "rolling_wm":       # on request only, as the rolling leg
         for res in bench_rolling_wm(ctx, L, args):
             print(json.dumps(res), flush=True)
