@@ -972,6 +972,38 @@ struct AntiJoinOp {
     }
 };
 
+// Incremental arg-max per group, ties kept: for every group with a present
+// row, all present rows whose rank is the group's largest present rank, each
+// at its own integral weight, kept up to date (the tail of
+// crates/nexmark/src/queries/q7.rs:82-93, aggregate(Min) over the negated
+// price joined back on the price; SQL's RANK() OVER (PARTITION BY g ORDER BY
+// x DESC) = 1).  A row's group is k >> group_shift, its rank k >> rank_shift
+// (rank_shift <= group_shift); presence is top-K's rule, per row.  One
+// divergence: Min::aggregate (operator/aggregate/min.rs:38-57) sums the
+// weights of all rows sharing a price and skips a price whose sum is zero,
+// while here a rank is present as long as one row at it is; the two differ
+// only when different rows at one rank carry weights of mixed sign that
+// cancel, never on positive weights.  in_sp is the input integral, out_sp
+// the integral of this operator's own outputs EXCLUDING the current tick;
+// step() is defined at the end of this file.
+struct ArgMaxOp {
+    int group_shift = 0, rank_shift = 0;
+    bool refill_all = false;  // DBSP_ARGMAX_REFILL_ALL
+    Spine in_sp, out_sp;
+    // cumulative: affected groups, groups sent down the refill path, rows the
+    // refill gather copied out of in_sp
+    int64_t groups_seen = 0, groups_refilled = 0, rows_gathered = 0;
+
+    // delta: consolidated rows, retained by the caller; out: the tick's
+    // consolidated output delta.  Any (k, v) is valid.
+    dbsp_status step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out);
+
+    void clear(dbsp_ctx *c) {
+        in_sp.clear(c);
+        out_sp.clear(c);
+    }
+};
+
 // ---- pieces of the keyed-aggregate stage, shared with their test probes ----
 
 // The small join route (delta.n <= 8192): probe and single-workgroup scan,
@@ -1760,12 +1792,19 @@ struct dbsp_engine {
     bool topk_stepped = false;  // topk_init is rejected after a step
     // query 103 state: auctions antijoined with the bids' auction keys
     AntiJoinOp anti;
+    // query 7 state: the bids by time, the host watermark {wm, s0, e0,
+    // have_prev} in ms (the words k_wm_update keeps on the device for q5 and
+    // q8), and the highest bids of the window
+    Spine q7_bt;
+    uint64_t q7_wm[4] = {0, 0, 0, 0};
+    ArgMaxOp argmax;
 };
 
 extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
                                           int query, int rank, int world) {
     if (query != 0 && query != 3 && query != 4 && query != 5 &&
-        query != 6 && query != 8 && query != 19 && query != 100 &&
+        query != 6 && query != 7 && query != 8 && query != 19 &&
+        query != 100 &&
         query != 101 && query != 102 && query != 103)
         return DBSP_ERR_INVALID;
     // query 103 would shard correctly by k, but no multi-rank run of it has
@@ -1774,12 +1813,18 @@ extern "C" dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx,
     // the exchange hashes k, which for query 19 packs the price under the
     // auction: it would split a group across ranks
     if (query == 19 && world > 1) return DBSP_ERR_INVALID;
+    // query 7 has one group, the window: it cannot be split across ranks
+    if (query == 7 && world > 1) return DBSP_ERR_INVALID;
 
     dbsp_engine *e = new dbsp_engine();
     e->ctx = ctx;
     e->query = query;
     if (query == 102) e->roll.agg = DBSP_ROLL_MAX;
     if (query == 19) e->topk.group_shift = 27;
+    if (query == 7) {
+        e->argmax.group_shift = 59;
+        e->argmax.rank_shift = 32;
+    }
     e->rank = rank;
     e->world = world;
     if (ctx) {
@@ -1816,6 +1861,8 @@ extern "C" dbsp_status dbsp_engine_destroy(dbsp_engine *e) {
     e->roll.clear(c);
     e->topk.clear(c);
     e->anti.clear(c);
+    e->q7_bt.clear(c);
+    e->argmax.clear(c);
     free_batch(c, e->win.maxout);
     free_batch(c, e->q6_foldout);
     free_batch(c, e->maxin_int);
@@ -4674,6 +4721,8 @@ static dbsp_status q19_step(dbsp_engine *e, const dbsp_event *d_ev,
 // query 103's tick, likewise
 static dbsp_status q103_step(dbsp_engine *e, const dbsp_event *d_ev,
                              int64_t n);
+// query 7's tick, likewise
+static dbsp_status q7_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n);
 
 extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
                                                int64_t hi) {
@@ -4702,6 +4751,7 @@ extern "C" dbsp_status dbsp_engine_step_staged(dbsp_engine *e, int64_t lo,
         case 6: return q6_step(e, d_ev, hi - lo);
         case 5: return q5_step(e, d_ev, hi - lo);
         case 8: return q8_step(e, d_ev, hi - lo);
+        case 7: return q7_step(e, d_ev, hi - lo);
         case 19: return q19_step(e, d_ev, hi - lo);
         case 101:
         case 102: return q101_step(e, d_ev, hi - lo);
@@ -4752,6 +4802,7 @@ extern "C" dbsp_status dbsp_engine_step(dbsp_engine *e, const dbsp_event *events
         case 6: st = q6_step(e, d_ev, n); break;
         case 5: st = q5_step(e, d_ev, n); break;
         case 8: st = q8_step(e, d_ev, n); break;
+        case 7: st = q7_step(e, d_ev, n); break;
         case 19: st = q19_step(e, d_ev, n); break;
         case 101:
         case 102: st = q101_step(e, d_ev, n); break;
@@ -5224,5 +5275,283 @@ extern "C" dbsp_status dbsp_engine_antijoin_stats(dbsp_engine *e,
     if (keys_flipped) *keys_flipped = e->anti.keys_flipped;
     if (rows_gathered) *rows_gathered = e->anti.rows_gathered;
     if (rows_filtered) *rows_filtered = e->anti.rows_filtered;
+    return DBSP_OK;
+}
+
+// ---- incremental arg-max per group, ties kept (queries/q7.rs:82-93) ----
+// Per tick, over a consolidated delta D:
+//   classify  every row of D against in_sp BEFORE the tick (top-K's kernels):
+//             appear, vanish or neither, the affected groups and their ranges
+//   current   out_sp rows inside those ranges, consolidated: Oc, each
+//             affected group's tie set at its real weights
+//   verdict   with m the rank of Oc_g, the group KEEPS its maximum iff an
+//             Oc_g row is not taken away by a vanish row of D, or a delta row
+//             of rank >= m is present after the tick.  A group with rows in
+//             Oc and neither refills: its maximum drops or it empties.
+//             Proof that the others need nothing of in_sp: every present row
+//             of rank m is in Oc_g and no row of rank > m was present, so
+//             after the tick the present rows of rank >= m are Oc_g's
+//             survivors and delta rows, and one of them exists.
+//   insert    D into in_sp
+//   slice     groups not refilled: Oc_g at its weights and the delta rows of
+//             rank >= m at dw (all of them where Oc_g is empty), whose sums
+//             are the new integral weights; refilled groups: their whole run
+//             out of in_sp (rows_gathered) and none of Oc_g.  Consolidated
+//             into S.
+//   select    a row of S is kept iff its rank is that of its group's last row
+//   output    consolidate(selected - Oc), appended to out_sp
+// A stream on which no group's maximum ever decreases reads nothing of
+// in_sp.  The explicit per-op path (a host length sync per phase, as top-K);
+// no chaining.  No row is invalid, so nothing can fail after the first write
+// to in_sp for a reason the caller controls.
+dbsp_status ArgMaxOp::step(dbsp_ctx *c, const DevBatch &delta, DevBatch &out) {
+    out = DevBatch{};
+    if (delta.n == 0) return DBSP_OK;
+    ScopedTimer timer(c, 3, 0.0);
+    const int64_t n = delta.n;
+    TRY(in_sp.cap_batches(c));
+    TRY(out_sp.cap_batches(c));
+    uint64_t *pb = nullptr;
+    int64_t ng = 0;
+    TRY(dbspk::topk_classify(c->stream, delta, trace_args_of(in_sp),
+                             group_shift, &pb, &ng));
+    ScratchBuf plan(c, pb);
+    DevBatch cur;
+    {
+        DevBatch raw;
+        TRY(dbspk::keyrange_gather(c->stream, pb + 2 * n, pb + 3 * n, ng,
+                                   trace_args_of(out_sp), 1, &raw));
+        TRY(sort_consolidate_batch(c, raw, cur));
+    }
+    uint64_t *vb = nullptr;
+    int64_t n_refill = 0;
+    TRY(dbspk::argmax_verdict(c->stream, delta, pb, ng, cur, rank_shift,
+                              refill_all, &vb, &n_refill));
+    ScratchBuf verdict(c, vb);
+    TRY(in_sp.insert_copy(c, delta));
+    TRY(in_sp.cap_batches(c));
+    // the candidate slice
+    std::vector<DevBatch> parts;
+    int64_t gathered = 0;
+    {
+        DevBatch cand;
+        TRY(dbspk::argmax_candidates(c->stream, delta, pb, ng, vb, cur,
+                                     rank_shift, &cand));
+        if (cand.n > 0) parts.push_back(cand);
+    }
+    if (n_refill > 0) {
+        DevBatch runs;
+        TRY(dbspk::keyrange_gather(c->stream, vb + ng, vb + 2 * ng, n_refill,
+                                   trace_args_of(in_sp), 1, &runs));
+        gathered = runs.n;
+        if (runs.n > 0) parts.push_back(runs);
+    }
+    DevBatch slice, sel;
+    if (!parts.empty()) TRY(finalize_raw(c, parts, slice));
+    TRY(dbspk::argmax_select(c->stream, slice, group_shift, rank_shift, &sel));
+    const int64_t moved = cur.n + gathered + slice.n + sel.n;
+    free_batch(c, slice);
+    // selected - Oc
+    dbspk::negate_weights(c->stream, cur.w, cur.n);
+    if (cur.n == 0) {
+        out = sel;
+    } else if (sel.n == 0) {
+        out = cur;
+    } else {
+        TRY(merge_batches(c, sel, cur, out));
+        free_batch(c, sel);
+        free_batch(c, cur);
+    }
+    if (out.n == 0) free_batch(c, out);
+    if (out.n > 0) TRY(out_sp.insert_copy(c, out));
+    groups_seen += ng;
+    groups_refilled += n_refill;
+    rows_gathered += gathered;
+    timer.bytes = 24.0 * (double)moved;
+    return DBSP_OK;
+}
+
+struct dbsp_argmax_op {
+    dbsp_ctx *ctx = nullptr;
+    ArgMaxOp op;
+};
+
+static bool argmax_args_valid(int group_shift, int rank_shift) {
+    return rank_shift >= 0 && rank_shift <= group_shift && group_shift <= 63;
+}
+
+// the select stage over a caller's batch: the recompute route
+extern "C" dbsp_status dbsp_argmax(dbsp_ctx *c, const dbsp_batch *in,
+                                   int group_shift, int rank_shift,
+                                   dbsp_batch *out) {
+    if (!c || !in || !out || in->len < 0 ||
+        !argmax_args_valid(group_shift, rank_shift))
+        return DBSP_ERR_INVALID;
+    DevBatch res;
+    {
+        ScopedTimer t(c, 3, 0.0);
+        TRY(dbspk::argmax_select(c->stream, as_batch(in), group_shift,
+                                 rank_shift, &res));
+    }
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_argmax_create(dbsp_ctx *c, int group_shift,
+                                          int rank_shift, uint32_t flags,
+                                          dbsp_argmax_op **out) {
+    if (!c || !out || !argmax_args_valid(group_shift, rank_shift) ||
+        (flags & ~(uint32_t)DBSP_ARGMAX_REFILL_ALL))
+        return DBSP_ERR_INVALID;
+    dbsp_argmax_op *t = new dbsp_argmax_op();
+    t->ctx = c;
+    t->op.group_shift = group_shift;
+    t->op.rank_shift = rank_shift;
+    t->op.refill_all = (flags & DBSP_ARGMAX_REFILL_ALL) != 0;
+    *out = t;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_argmax_step(dbsp_argmax_op *t, const uint64_t *k,
+                                        const uint64_t *v, const int64_t *w,
+                                        int64_t n, dbsp_batch *out) {
+    if (!t || !out || n < 0) return DBSP_ERR_INVALID;
+    dbsp_ctx *c = t->ctx;
+    *out = dbsp_batch{nullptr, nullptr, nullptr, 0};
+    if (n == 0) return DBSP_OK;
+    DevBatch raw, delta, res;
+    TRY(alloc_batch(c, n, raw));
+    TRY(copy_cols(c, raw, 0, k, v, w, n));
+    TRY(sort_consolidate_batch(c, raw, delta));
+    const dbsp_status st = t->op.step(c, delta, res);
+    free_batch(c, delta);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    if (st != DBSP_OK) return st;
+    put_batch(out, res);
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_argmax_stats(dbsp_argmax_op *t, int64_t *in_rows,
+                                         int *in_batches, int64_t *out_rows,
+                                         int *out_batches,
+                                         int64_t *groups_seen,
+                                         int64_t *groups_refilled,
+                                         int64_t *rows_gathered) {
+    if (!t) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = t->op.in_sp.total();
+    if (in_batches) *in_batches = (int)t->op.in_sp.batches.size();
+    if (out_rows) *out_rows = t->op.out_sp.total();
+    if (out_batches) *out_batches = (int)t->op.out_sp.batches.size();
+    if (groups_seen) *groups_seen = t->op.groups_seen;
+    if (groups_refilled) *groups_refilled = t->op.groups_refilled;
+    if (rows_gathered) *rows_gathered = t->op.rows_gathered;
+    return DBSP_OK;
+}
+
+extern "C" dbsp_status dbsp_argmax_destroy(dbsp_argmax_op *t) {
+    if (!t) return DBSP_OK;
+    t->op.clear(t->ctx);
+    (void)hipStreamSynchronize(t->ctx->stream);
+    delete t;
+    return DBSP_OK;
+}
+
+// ---- query 7: the highest bids of the last tumbled window (queries/q7.rs:
+// 45-94) ----
+//   front      bids as k = date_time << 27 | price, v = auction << 32 |
+//              bidder (q7.rs:47-54), so key order is time order.  A field too
+//              wide for its place is caught on the device as for query 19:
+//              a non-empty second stream makes the step DBSP_ERR_INVALID
+//              before any state changes.
+//   watermark  watermark_monotonic(date_time - 4000) (q7.rs:60-61,
+//              WATERMARK_INTERVAL_SECONDS, queries/mod.rs:12) from the tick's
+//              largest date_time, the last key of the sorted delta, on the
+//              host; the precondition of q5 (max >= lag) applies and the
+//              arithmetic is wm_advance's.  rounded = wm - wm % 10000, the
+//              window [rounded saturating-minus 10000, rounded) (q7.rs:64-70).
+//   window     the window stage by its host-bounds route over the
+//              bid-by-time spine, bounds << 27 (q7.rs:73): k_wm_update and
+//              the chained ranges launch of q5 and q8 are not involved
+//   tail       rows mapped to k' = price << 32 | date_time (q7.rs:74-79),
+//              sorted, into the arg-max operator with group_shift 59 and
+//              rank_shift 32: k' < 2^59, one group, its rank the price.  The
+//              operator's output is the tick's.
+// Every tumble of the window retracts the old maximum, so it refills; the
+// tick's delta is the whole window then anyway.  The bid-by-time spine grows
+// as q5's and q8's do.
+static dbsp_status q7_step(dbsp_engine *e, const dbsp_event *d_ev, int64_t n) {
+    dbsp_ctx *c = e->ctx;
+    constexpr uint64_t TUMBLE_MS = 10000, WM_LAG_MS = 4000;
+    DevBatch d, dummy;
+    int64_t n_wide = 0;
+    TRY(build_deltas(e, d_ev, n, d, dummy, false, &n_wide));
+    if (n_wide != 0) {
+        free_batch(c, d);
+        HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+        return DBSP_ERR_INVALID;
+    }
+    engine_free_output(e);
+    if (d.n == 0) {  // no bids: the watermark and the window stand still
+        free_batch(c, d);
+        return DBSP_OK;
+    }
+    uint64_t last = 0;
+    TRY(dbsp_d2h(c, &last, d.k + d.n - 1, sizeof(last)));
+    const uint64_t gmax = last >> 27;
+    uint64_t *st = e->q7_wm;
+    uint64_t wm = st[0];
+    if (gmax > 0) wm = std::max(wm, gmax - WM_LAG_MS);
+    const uint64_t rounded = wm - wm % TUMBLE_MS;
+    const uint64_t s1 = rounded >= TUMBLE_MS ? rounded - TUMBLE_MS : 0;
+    const uint64_t e1 = rounded;
+    WindowLeg leg{&e->q7_bt, &d, nullptr, L_WIN};
+    TRY(e->q7_bt.cap_batches(c));
+    leg.ta = trace_args_of(e->q7_bt);
+    leg.nreg = 3 * leg.ta.nb + 1;
+    TRY(leg.table.alloc(c, (size_t)leg.nreg * 5 * 8 + 8));
+    std::vector<DevBatch> wb_raw;
+    {
+        ScopedTimer t(c, 4, 0.0);
+        TRY(dbspk::window_ranges_multi(c->stream, leg.ta, d.k, d.n,
+                                       (int)st[3], st[1] << 27, st[2] << 27,
+                                       s1 << 27, e1 << 27,
+                                       leg.table.as<int64_t>(),
+                                       c->d_len + leg.slot));
+        TRY(read_len(c, leg.slot, 1));
+        TRY(window_emit(c, leg, wb_raw));
+    }
+    st[0] = wm;
+    st[1] = s1;
+    st[2] = e1;
+    st[3] = 1;
+    TRY(e->q7_bt.insert(c, d));
+    DevBatch wbr, dBP;
+    if (!wb_raw.empty()) TRY(finalize_raw(c, wb_raw, wbr));
+    if (wbr.n > 0) {
+        DevBatch raw;
+        TRY(alloc_batch(c, wbr.n, raw));
+        TRY(dbspk::map_price_time(c->stream, wbr, raw));
+        TRY(sort_consolidate_batch(c, raw, dBP));
+    }
+    free_batch(c, wbr);
+    const dbsp_status res = e->argmax.step(c, dBP, e->output);
+    free_batch(c, dBP);
+    HIP_CHECK_ST(hipStreamSynchronize(c->stream));
+    return res;
+}
+
+extern "C" dbsp_status dbsp_engine_argmax_stats(dbsp_engine *e,
+                                                int64_t *in_rows,
+                                                int64_t *out_rows,
+                                                int64_t *groups_seen,
+                                                int64_t *groups_refilled,
+                                                int64_t *rows_gathered) {
+    if (!e || e->query != 7) return DBSP_ERR_INVALID;
+    if (in_rows) *in_rows = e->argmax.in_sp.total();
+    if (out_rows) *out_rows = e->argmax.out_sp.total();
+    if (groups_seen) *groups_seen = e->argmax.groups_seen;
+    if (groups_refilled) *groups_refilled = e->argmax.groups_refilled;
+    if (rows_gathered) *rows_gathered = e->argmax.rows_gathered;
     return DBSP_OK;
 }

@@ -4107,6 +4107,12 @@ __global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_auction_bidkey(
         uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
         uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1);
 
+// query 7's front, defined with the arg-max kernels below
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_time(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1);
+
 dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
                                  const EventCols *cols, int64_t n, int query,
                                  const Rows &out0, const Rows &out1,
@@ -4125,6 +4131,10 @@ dbsp_status flatmap_events_chain(hipStream_t s, const dbsp_event *ev,
     else if (n > 0 && query == 103)
         k_flatmap_auction_bidkey<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0,
                                    s>>>(
+            ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1, out1.k,
+            out1.v, out1.w, out1.n);
+    else if (n > 0 && query == 7)
+        k_flatmap_bid_time<<<grid_for(n, FLATMAP_BLK), FLATMAP_BLK, 0, s>>>(
             ev, c, n, ctr, out0.k, out0.v, out0.w, out0.n, ctr + 1, out1.k,
             out1.v, out1.w, out1.n);
     else if (n > 0)
@@ -5587,6 +5597,302 @@ __global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_auction_bidkey(
             k1[pos1] = f0; v1[pos1] = 0; w1[pos1] = w;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// Incremental arg-max per group, ties kept (the tail of
+// crates/nexmark/src/queries/q7.rs:82-93: aggregate(Min) over the negated
+// price joined back on the price; SQL's RANK() OVER (PARTITION BY g ORDER BY
+// x DESC) = 1).  A row's group is k >> group_shift, its rank k >> rank_shift
+// with rank_shift <= group_shift, so equal ranks imply one group and (k, v)
+// order is (group, rank, tie) order.  The relation holds, per group, every
+// present row of the group's largest present rank AT ITS OWN WEIGHT.
+// Divergence from the reference: Min::aggregate
+// (operator/aggregate/min.rs:38-57) sums the weights of all rows sharing a
+// price and skips the price when that sum is zero; here a rank stays present
+// as long as any single row at it is present.  The two agree whenever the
+// weights are positive; they differ only when different rows at one rank
+// carry weights of mixed sign that cancel.
+// Classify, the group list and both gathers are the top-K ones
+// (k_topk_classify, k_topk_groups, k_keyrange_count, k_range_emit,
+// k_topk_refill_ranges).  New here:
+//   k_argmax_verdict       over Oc ++ D: a group's refill flag starts at 1
+//                          and every keep event stores the same 0
+//   k_argmax_cand_flags/emit  the candidate rows of the groups NOT refilled
+//   k_argmax_select_flags/emit  a slice row is kept iff its rank is the rank
+//                          of its group's last row: one binary search per row
+//   k_negate_weights       -Oc for the output merge
+// Every data-dependent size is flags -> scan -> emit; nothing passes between
+// workgroups.
+// ---------------------------------------------------------------------------
+
+// ok/ov: the affected groups' current tie sets, consolidated.  The group
+// keeps its maximum (no refill) iff an Oc row is not taken away by a vanish
+// row of D, or a delta row that is present after the tick has a rank >= the
+// rank of Oc_g.  A group whose Oc_g is empty had no present row: any of its
+// delta rows clears the flag.
+__global__ void k_argmax_verdict(const uint64_t *dk, const uint64_t *dv,
+                                 const int64_t *cls, const uint64_t *gidx,
+                                 int64_t n, const uint64_t *glo,
+                                 const uint64_t *ghi, int64_t ng,
+                                 const uint64_t *ok, const uint64_t *ov,
+                                 int64_t no, int rank_shift,
+                                 uint64_t *refill) {
+    const int64_t tot = no + n;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < tot;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        if (j < no) {
+            const uint64_t k = ok[j], v = ov[j];
+            const int64_t p = lex_lower(dk, dv, 0, n, k, v);
+            const bool gone = p < n && dk[p] == k && dv[p] == v && cls[p] < 0;
+            if (!gone) {
+                // every Oc row lies in an affected group: it was gathered by
+                // that group's range, and glo[0] <= its key
+                const int64_t g = upper_bound_k(glo, ng, k) - 1;
+                if (g >= 0) refill[g] = 0;
+            }
+        } else {
+            const int64_t i = j - no;
+            const uint64_t g = gidx[i];
+            const int64_t a = lower_bound_k(ok, no, glo[g]);
+            const bool empty = a >= no || ok[a] > ghi[g];
+            if (empty || (cls[i] >= 0 &&
+                          (dk[i] >> rank_shift) >= (ok[a] >> rank_shift)))
+                refill[g] = 0;
+        }
+    }
+}
+
+// Candidates of the groups that are not refilled, over the index space
+// [0, no) = Oc, [no, no + n) = D: an Oc row enters at its weight, a delta row
+// at dw iff its rank is >= the rank of Oc_g (every delta row when Oc_g is
+// empty).  A delta row above Oc_g's rank was absent before, one at that rank
+// is in Oc_g or was absent: the sums are the rows' new integral weights.
+__global__ void k_argmax_cand_flags(const uint64_t *dk, const uint64_t *gidx,
+                                    int64_t n, const uint64_t *glo,
+                                    const uint64_t *ghi, int64_t ng,
+                                    const uint64_t *refill, const uint64_t *ok,
+                                    int64_t no, int rank_shift,
+                                    uint64_t *flags) {
+    const int64_t tot = no + n;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < tot;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        uint64_t f = 0;
+        if (j < no) {
+            const int64_t g = upper_bound_k(glo, ng, ok[j]) - 1;
+            f = g >= 0 && !refill[g];
+        } else {
+            const int64_t i = j - no;
+            const uint64_t g = gidx[i];
+            if (!refill[g]) {
+                const int64_t a = lower_bound_k(ok, no, glo[g]);
+                f = a >= no || ok[a] > ghi[g] ||
+                    (dk[i] >> rank_shift) >= (ok[a] >> rank_shift);
+            }
+        }
+        flags[j] = f;
+    }
+}
+
+__global__ void k_argmax_cand_emit(const uint64_t *dk, const uint64_t *dv,
+                                   const int64_t *dw, int64_t n,
+                                   const uint64_t *ok, const uint64_t *ov,
+                                   const int64_t *ow, int64_t no,
+                                   const uint64_t *flags,
+                                   const uint64_t *fscan, uint64_t *ck,
+                                   uint64_t *cv, int64_t *cw) {
+    const int64_t tot = no + n;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < tot;
+         j += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[j]) continue;
+        const uint64_t o = fscan[j];
+        if (j < no) {
+            ck[o] = ok[j]; cv[o] = ov[j]; cw[o] = ow[j];
+        } else {
+            const int64_t i = j - no;
+            ck[o] = dk[i]; cv[o] = dv[i]; cw[o] = dw[i];
+        }
+    }
+}
+
+// a row of the consolidated slice is selected iff its rank is the rank of the
+// last row of its group: the group's end is one binary search over the keys
+__global__ void k_argmax_select_flags(const uint64_t *sk, int64_t n,
+                                      int group_shift, int rank_shift,
+                                      uint64_t *flags) {
+    const uint64_t mask = topk_mask(group_shift);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t from = i + 1;
+        const int64_t end =
+            from + upper_bound_k(sk + from, n - from, sk[i] | mask);
+        flags[i] = (sk[end - 1] >> rank_shift) == (sk[i] >> rank_shift);
+    }
+}
+
+__global__ void k_argmax_select_emit(const uint64_t *sk, const uint64_t *sv,
+                                     const int64_t *sw, int64_t n,
+                                     const uint64_t *flags,
+                                     const uint64_t *fscan, uint64_t *ok,
+                                     uint64_t *ov, int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint64_t o = fscan[i];
+        ok[o] = sk[i]; ov[o] = sv[i]; ow[o] = sw[i];
+    }
+}
+
+__global__ void k_negate_weights(int64_t *w, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x)
+        w[i] = -w[i];
+}
+
+dbsp_status argmax_verdict(hipStream_t s, const Rows &delta,
+                           const uint64_t *plan, int64_t ng, const Rows &cur,
+                           int rank_shift, bool refill_all, uint64_t **verdict,
+                           int64_t *n_refill) {
+    const int64_t n = delta.n;
+    *verdict = nullptr;
+    *n_refill = 0;
+    if (n <= 0 || ng <= 0) return DBSP_OK;
+    const int64_t *cls = (const int64_t *)plan;
+    const uint64_t *gidx = plan + n, *glo = plan + 2 * n, *ghi = plan + 3 * n;
+    Scratch sc(s);
+    uint64_t *vb, *rscan;
+    HIP_CHECK(sc.get(&vb, 3 * ng * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&rscan, ng * sizeof(uint64_t)));
+    k_fill_u64<<<grid_for(ng), BLK, 0, s>>>(vb, 1, ng);
+    if (!refill_all)
+        k_argmax_verdict<<<grid_for(cur.n + n), BLK, 0, s>>>(
+            delta.k, delta.v, cls, gidx, n, glo, ghi, ng, cur.k, cur.v, cur.n,
+            rank_shift, vb);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, vb, rscan, ng, &total));
+    if (total > 0)
+        k_topk_refill_ranges<<<grid_for(ng), BLK, 0, s>>>(
+            vb, rscan, ng, glo, ghi, vb + ng, vb + 2 * ng);
+    *n_refill = (int64_t)total;
+    sc.keep(vb);
+    *verdict = vb;
+    return DBSP_OK;
+}
+
+dbsp_status argmax_candidates(hipStream_t s, const Rows &delta,
+                              const uint64_t *plan, int64_t ng,
+                              const uint64_t *refill, const Rows &cur,
+                              int rank_shift, Rows *out) {
+    const int64_t n = delta.n, no = cur.n, tot = n + no;
+    if (n <= 0 || ng <= 0) return no_rows(out);
+    const uint64_t *gidx = plan + n, *glo = plan + 2 * n, *ghi = plan + 3 * n;
+    Scratch sc(s);
+    uint64_t *flags, *fscan;
+    HIP_CHECK(sc.get(&flags, tot * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, tot * sizeof(uint64_t)));
+    k_argmax_cand_flags<<<grid_for(tot), BLK, 0, s>>>(
+        delta.k, gidx, n, glo, ghi, ng, refill, cur.k, no, rank_shift, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, tot, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_argmax_cand_emit<<<grid_for(tot), BLK, 0, s>>>(
+        delta.k, delta.v, delta.w, n, cur.k, cur.v, cur.w, no, flags, fscan,
+        r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+dbsp_status argmax_select(hipStream_t s, const Rows &slice, int group_shift,
+                          int rank_shift, Rows *out) {
+    const int64_t n = slice.n;
+    if (n <= 0) return no_rows(out);
+    Scratch sc(s);
+    uint64_t *flags, *fscan;
+    HIP_CHECK(sc.get(&flags, n * sizeof(uint64_t)));
+    HIP_CHECK(sc.get(&fscan, n * sizeof(uint64_t)));
+    k_argmax_select_flags<<<grid_for(n), BLK, 0, s>>>(slice.k, n, group_shift,
+                                                      rank_shift, flags);
+    uint64_t total = 0;
+    TRY_K(scan_exclusive(s, flags, fscan, n, &total));
+    if (total == 0) return no_rows(out);
+    Rows r;
+    TRY_K(alloc_rows(sc, (int64_t)total, &r));
+    k_argmax_select_emit<<<grid_for(n), BLK, 0, s>>>(
+        slice.k, slice.v, slice.w, n, flags, fscan, r.k, r.v, r.w);
+    return give_rows(sc, r, out);
+}
+
+void negate_weights(hipStream_t s, int64_t *w, int64_t n) {
+    if (n > 0) k_negate_weights<<<grid_for(n), BLK, 0, s>>>(w, n);
+}
+
+// Query 7's front (queries/q7.rs:47-54: bids indexed by date_time), a kernel
+// of its own as k_flatmap_bid_tv is, so that k_flatmap (on q3's measured
+// path) stays as it is.  Stream 0: k = date_time << 27 | price, v = auction
+// << 32 | bidder, so key order is time order and the window stage's bounds
+// are date_time << 27.  Stream 1 collects the bids with a field too wide for
+// its place, as (date_time, price, w): its counter is the step's error word,
+// read back with the lengths the step syncs on anyway.
+__global__ __launch_bounds__(FLATMAP_BLK) void k_flatmap_bid_time(
+        const dbsp_event *ev, dbspk::EventCols cols, int64_t n, uint64_t *c0,
+        uint64_t *k0, uint64_t *v0, int64_t *w0, int64_t cap0, uint64_t *c1,
+        uint64_t *k1, uint64_t *v1, int64_t *w1, int64_t cap1) {
+    __shared__ uint32_t s_cnt[2][FLATMAP_WAVES];
+    __shared__ unsigned long long s_base[2][FLATMAP_WAVES];
+    const int64_t stride = (int64_t)gridDim.x * FLATMAP_BLK;
+    for (int64_t base = blockIdx.x * (int64_t)FLATMAP_BLK; base < n;
+         base += stride) {
+        const int64_t i = base + threadIdx.x;
+        uint64_t kind = 0, auction = 0, bidder = 0, price = 0, dt = 0;
+        int64_t w = 0;
+        if (i < n) {
+            if (cols.kind) {
+                kind = cols.kind[i]; auction = cols.f0[i]; bidder = cols.f1[i];
+                price = cols.f2[i]; dt = cols.f3[i]; w = cols.w[i];
+            } else {
+                const dbsp_event e = ev[i];
+                kind = e.kind; auction = e.f0; bidder = e.f1; price = e.f2;
+                dt = e.f3; w = e.w;
+            }
+        }
+        const bool bid = i < n && kind == 2;
+        const bool wide = (auction >> 32) || (price >> 27) || (bidder >> 32) ||
+                          (dt >> 32);
+        const bool p0 = bid && !wide, p1 = bid && wide;
+        uint64_t pos0, pos1;
+        block_append2((unsigned long long *)c0, (unsigned long long *)c1, p0,
+                      p1, s_cnt, s_base, pos0, pos1);
+        if (p0 && pos0 < (uint64_t)cap0) {
+            k0[pos0] = (dt << 27) | price;
+            v0[pos0] = (auction << 32) | bidder;
+            w0[pos0] = w;
+        }
+        if (p1 && pos1 < (uint64_t)cap1) {
+            k1[pos1] = dt; v1[pos1] = price; w1[pos1] = w;
+        }
+    }
+}
+
+// q7.rs:74-79, bids_by_price: a windowed row (date_time << 27 | price, v, w)
+// becomes (price << 32 | date_time, v, w).  Not order-preserving.
+__global__ void k_map_price_time(const uint64_t *ik, const uint64_t *iv,
+                                 const int64_t *iw, int64_t n, uint64_t *ok,
+                                 uint64_t *ov, int64_t *ow) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = ik[i];
+        ok[i] = ((k & ((1ull << 27) - 1)) << 32) | (k >> 27);
+        ov[i] = iv[i];
+        ow[i] = iw[i];
+    }
+}
+
+dbsp_status map_price_time(hipStream_t s, const Rows &in, const Rows &out) {
+    if (in.n > 0)
+        k_map_price_time<<<grid_for(in.n), BLK, 0, s>>>(in.k, in.v, in.w, in.n,
+                                                        out.k, out.v, out.w);
+    return DBSP_OK;
 }
 
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed) {

@@ -499,6 +499,37 @@ dbsp_status keyrange_gather_mul(hipStream_t s, const uint64_t *keys,
 dbsp_status anti_filter(hipStream_t s, const Rows &a, const TraceArgs &t,
                         bool anti, Rows *out);
 
+// ---- incremental arg-max per group, ties kept (the tail of queries/q7.rs:
+// 82-93).  Group k >> group_shift, rank k >> rank_shift, rank_shift <=
+// group_shift; presence as for top-K, per row.  The plan is topk_classify's
+// and both gathers are keyrange_gather ----
+// Per-group refill flag.  cur: the affected groups' current tie sets,
+// consolidated, at their real weights.  A group with rows in cur refills iff
+// every one of them vanishes in the tick and no delta row of rank >= cur's
+// rank is present after it; refill_all flags every affected group.  *verdict
+// is one 3*ng-word device buffer (caller frees) [refill | rlo | rhi], as
+// topk_verdict's.  One host sync.
+dbsp_status argmax_verdict(hipStream_t s, const Rows &delta,
+                           const uint64_t *plan, int64_t ng, const Rows &cur,
+                           int rank_shift, bool refill_all, uint64_t **verdict,
+                           int64_t *n_refill);
+// raw candidate rows of the groups NOT refilled: cur's rows at their weights
+// and the delta rows of rank >= cur's rank (all of them where the group has
+// none in cur) at theirs
+dbsp_status argmax_candidates(hipStream_t s, const Rows &delta,
+                              const uint64_t *plan, int64_t ng,
+                              const uint64_t *refill, const Rows &cur,
+                              int rank_shift, Rows *out);
+// the rows of a consolidated slice whose rank is their group's largest, at
+// their own weights, in order
+dbsp_status argmax_select(hipStream_t s, const Rows &slice, int group_shift,
+                          int rank_shift, Rows *out);
+// w[i] = -w[i] (no sync)
+void negate_weights(hipStream_t s, int64_t *w, int64_t n);
+// query 7: rows (date_time << 27 | price, v, w) -> (price << 32 | date_time,
+// v, w); out holds in.n rows (its n is ignored)
+dbsp_status map_price_time(hipStream_t s, const Rows &in, const Rows &out);
+
 uint64_t host_xxh3_u64(uint64_t key, uint64_t seed);
 
 }  // namespace dbspk

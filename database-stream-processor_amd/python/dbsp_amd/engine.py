@@ -258,6 +258,28 @@ def _L():
         L.dbsp_engine_antijoin_stats.restype = i32
         L.dbsp_engine_antijoin_stats.argtypes = (
             [vp] + [ctypes.POINTER(i64)] * 5)
+        L.dbsp_argmax.restype = i32
+        L.dbsp_argmax.argtypes = [vp, ctypes.POINTER(BatchStruct),
+                                  ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(BatchStruct)]
+        L.dbsp_argmax_create.restype = i32
+        L.dbsp_argmax_create.argtypes = [vp, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_uint32, ctypes.POINTER(vp)]
+        L.dbsp_argmax_step.restype = i32
+        L.dbsp_argmax_step.argtypes = [vp, vp, vp, vp, i64,
+                                       ctypes.POINTER(BatchStruct)]
+        L.dbsp_argmax_stats.restype = i32
+        L.dbsp_argmax_stats.argtypes = [vp, ctypes.POINTER(i64),
+                                        ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(i64)]
+        L.dbsp_argmax_destroy.restype = i32
+        L.dbsp_argmax_destroy.argtypes = [vp]
+        L.dbsp_engine_argmax_stats.restype = i32
+        L.dbsp_engine_argmax_stats.argtypes = [vp] + [ctypes.POINTER(i64)] * 5
         L.dbsp_engine_c5_init.restype = i32
         L.dbsp_engine_c5_init.argtypes = [vp, i64, i64, u64]
         L.dbsp_engine_kernel_stats.restype = i32
@@ -752,6 +774,20 @@ class Ctx:
         self.free_batch(out)
         return res
 
+    def argmax(self, rows, group_shift, rank_shift):
+        """The rows of a consolidated batch whose rank (key >> rank_shift) is
+        the largest of their group (key >> group_shift), weights unchanged,
+        in order: the recompute route of `ArgMax`."""
+        inp = self.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_argmax(self._h, ctypes.byref(inp), group_shift,
+                                   rank_shift, ctypes.byref(out))
+        self.free_batch(inp)
+        _check(st, "argmax")
+        res = self.download_rows(out)
+        self.free_batch(out)
+        return res
+
     def shard_partition(self, rows, nshards):
         inp = self.upload_rows(rows)
         out = BatchStruct()
@@ -981,6 +1017,67 @@ class AntiJoin:
                 "rows_filtered": rf.value}
 
 
+ARGMAX_REFILL_ALL = 1  # DBSP_ARGMAX_REFILL_ALL
+
+
+class ArgMax:
+    """Stateful incremental arg-max per group with ties (the tail of Nexmark
+    q7).  Input rows are (k, v, w); a row's group is k >> group_shift and its
+    rank k >> rank_shift, rank_shift <= group_shift.  The operator keeps, per
+    group, every row of non-zero total weight whose rank is the group's
+    largest, at that total weight; each step returns the tick's consolidated
+    change of that relation.  refill_all recomputes every affected group from
+    its whole run (a diagnostic: outputs are the same)."""
+
+    def __init__(self, ctx: Ctx, group_shift: int, rank_shift: int,
+                 refill_all=False):
+        self._ctx = ctx
+        self._lib = ctx._lib
+        h = ctypes.c_void_p()
+        _check(self._lib.dbsp_argmax_create(
+            ctx._h, group_shift, rank_shift,
+            ARGMAX_REFILL_ALL if refill_all else 0, ctypes.byref(h)),
+            "argmax_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self._ctx, "_h", None):
+                self._lib.dbsp_argmax_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def step(self, rows: np.ndarray) -> np.ndarray:
+        """One tick: raw (unsorted, unconsolidated) delta rows in, the
+        consolidated output delta out."""
+        raw = self._ctx.upload_rows(rows)
+        out = BatchStruct()
+        st = self._lib.dbsp_argmax_step(self._h, raw.k, raw.v, raw.w, raw.len,
+                                        ctypes.byref(out))
+        self._ctx.free_batch(raw)
+        _check(st, "argmax_step")
+        res = self._ctx.download_rows(out)
+        self._ctx.free_batch(out)
+        return res
+
+    def stats(self) -> dict:
+        """in_rows / in_batches / out_rows / out_batches of the two traces
+        and the cumulative groups_seen, groups_refilled, rows_gathered."""
+        ir, orr = ctypes.c_int64(), ctypes.c_int64()
+        ib, ob = ctypes.c_int(), ctypes.c_int()
+        gs, gr, rg = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(self._lib.dbsp_argmax_stats(
+            self._h, ctypes.byref(ir), ctypes.byref(ib), ctypes.byref(orr),
+            ctypes.byref(ob), ctypes.byref(gs), ctypes.byref(gr),
+            ctypes.byref(rg)), "argmax_stats")
+        return {"in_rows": ir.value, "in_batches": ib.value,
+                "out_rows": orr.value, "out_batches": ob.value,
+                "groups_seen": gs.value, "groups_refilled": gr.value,
+                "rows_gathered": rg.value}
+
+
 def xxh3_u64(key, seed=0x7F95EF85BE33C337):
     return _L().dbsp_xxh3_u64(key, seed)
 
@@ -1067,6 +1164,16 @@ class Engine:
             self._h, *[ctypes.byref(x) for x in vals]), "antijoin_stats")
         return dict(zip(("a_rows", "b_rows", "keys_flipped", "rows_gathered",
                          "rows_filtered"), (x.value for x in vals)))
+
+    def argmax_stats(self) -> dict:
+        """Query 7: in_rows, out_rows and the cumulative groups_seen,
+        groups_refilled, rows_gathered."""
+        vals = [ctypes.c_int64() for _ in range(5)]
+        _check(self._lib.dbsp_engine_argmax_stats(
+            self._h, *[ctypes.byref(x) for x in vals]), "argmax_stats")
+        return dict(zip(("in_rows", "out_rows", "groups_seen",
+                         "groups_refilled", "rows_gathered"),
+                        (x.value for x in vals)))
 
     def step_staged(self, lo, hi):
         _check(self._lib.dbsp_engine_step_staged(self._h, lo, hi), "step")

@@ -483,6 +483,69 @@ dbsp_status dbsp_antijoin_stats(dbsp_antijoin_op *op, int64_t *a_rows,
                                 int64_t *rows_filtered);
 dbsp_status dbsp_antijoin_destroy(dbsp_antijoin_op *op);
 
+/* ---- incremental arg-max per group, ties kept ----
+ * SQL's RANK() OVER (PARTITION BY g ORDER BY x DESC) = 1, or WHERE x =
+ * (SELECT MAX(x) ...) per group, kept up to date.  Replaces the tail of
+ * crates/nexmark/src/queries/q7.rs:82-93: aggregate(Min) over the negated
+ * price, joined back to the rows on the price.
+ * Rows are (k, v, w), with 0 <= rank_shift <= group_shift <= 63.  A row's
+ * group is k >> group_shift and its rank k >> rank_shift: the rank includes
+ * the group bits, so equal ranks imply one group and plain (k, v) order is
+ * (group, rank, tie order) order.  A row is PRESENT iff its total weight in
+ * the input integral is non-zero, negative totals included (top-K's rule).
+ * The maintained relation holds, for every group that has a present row, all
+ * present rows whose rank equals the group's largest present rank, EACH AT
+ * ITS OWN INTEGRAL WEIGHT (the reference's join multiplies by the row's
+ * weight).  So a tie row going from weight 1 to 2 outputs +1 for that row.
+ * One divergence from the reference: Min::aggregate
+ * (operator/aggregate/min.rs:38-57) sums the weights of all rows sharing a
+ * price and skips a price whose sum is zero; here a rank stays present as
+ * long as any single row at it is present.  The two agree on every relation
+ * whose weights are positive (every Nexmark stream) and differ only when
+ * different rows at one rank carry weights of mixed sign that cancel.
+ * Out of scope: a Min direction, sharded ranks, watermark-bounded state. */
+
+/* The batch primitive: the rows of the consolidated batch `in` whose rank is
+ * their group's largest, weights unchanged, in order.  Invalid shifts
+ * (negative, > 63, rank_shift > group_shift) are DBSP_ERR_INVALID.  out:
+ * device arrays owned by the caller, null when empty; host visible on
+ * return. */
+dbsp_status dbsp_argmax(dbsp_ctx *ctx, const dbsp_batch *in, int group_shift,
+                        int rank_shift, dbsp_batch *out);
+
+/* The stateful operator: the input integral and the integral of its own
+ * outputs, both as spines (the aggregate's input and output traces,
+ * operator/aggregate/mod.rs:479-547). */
+typedef struct dbsp_argmax_op dbsp_argmax_op;
+/* flags: every affected group recomputes its tie set from its whole run of
+ * the input integral (the refill path).  A diagnostic and a test oracle:
+ * outputs are the same either way. */
+#define DBSP_ARGMAX_REFILL_ALL 1u
+/* shifts as for dbsp_argmax; an unknown flag bit is DBSP_ERR_INVALID */
+dbsp_status dbsp_argmax_create(dbsp_ctx *ctx, int group_shift, int rank_shift,
+                               uint32_t flags, dbsp_argmax_op **out);
+/* k/v/w: n raw (unsorted, unconsolidated) delta rows in device memory; any
+ * (k, v) is valid.  out: the tick's consolidated change of the relation
+ * (device arrays owned by the caller, null when empty; host visible on
+ * return).  n == 0 and a delta that consolidates to nothing change nothing
+ * and return an empty out.  A group's run of the input integral is read (the
+ * refill) iff the group had a present row before the tick and no present row
+ * of at least its old largest rank remains after it: its maximum drops, or
+ * it empties.  A stream on which no group's maximum ever decreases reads
+ * nothing of the input integral. */
+dbsp_status dbsp_argmax_step(dbsp_argmax_op *op, const uint64_t *k,
+                             const uint64_t *v, const int64_t *w, int64_t n,
+                             dbsp_batch *out);
+/* as dbsp_topk_stats: rows / spine batches of the two traces and the
+ * cumulative groups a delta touched, groups refilled and rows the refill
+ * gather copied out of the input trace.  Any out pointer may be null. */
+dbsp_status dbsp_argmax_stats(dbsp_argmax_op *op, int64_t *in_rows,
+                              int *in_batches, int64_t *out_rows,
+                              int *out_batches, int64_t *groups_seen,
+                              int64_t *groups_refilled,
+                              int64_t *rows_gathered);
+dbsp_status dbsp_argmax_destroy(dbsp_argmax_op *op);
+
 dbsp_status dbsp_agg_linear_upsert(dbsp_ctx *ctx,
                                    const uint64_t *delta_keys, int64_t nd,
                                    const dbsp_batch *in_trace,
@@ -694,7 +757,20 @@ typedef struct dbsp_engine dbsp_engine;
  *  Stream::antijoin, join.rs:294-320, on the antijoin operator above; rows
  *  (auction id, seller, w), output rows are input rows, signed.  world > 1
  *  is DBSP_ERR_INVALID at create: sharding by k would be correct, but no
- *  multi-rank run of it has been made). */
+ *  multi-rank run of it has been made), or
+ * 7 (Nexmark q7, the highest bids of the last tumbled window, queries/q7.rs:
+ *  45-94: bids by date_time, watermark_monotonic(date_time - 4000) rounded
+ *  down to 10000, the window [rounded saturating-minus 10000, rounded), and
+ *  the arg-max operator above over rows k = price << 32 | date_time,
+ *  v = auction << 32 | bidder with group_shift 59 and rank_shift 32: one
+ *  group, ranked by price.  Output rows are those rows at the bids' weights,
+ *  signed.  A tick's largest date_time must be >= 4000, as for query 5.  A
+ *  bid with date_time >= 2^32, price >= 2^27, auction >= 2^32 or bidder >=
+ *  2^32 makes the step DBSP_ERR_INVALID, detected on the device, with the
+ *  state unchanged; the next tick is unaffected.  world > 1 is
+ *  DBSP_ERR_INVALID at create: one group cannot be split across ranks.  The
+ *  bid-by-time trace is not trimmed.  channel, url and extra are not in the
+ *  event row). */
 dbsp_status dbsp_engine_create(dbsp_engine **out, dbsp_ctx *ctx, int query,
                                int rank, int world);
 
@@ -736,6 +812,12 @@ dbsp_status dbsp_engine_antijoin_stats(dbsp_engine *e, int64_t *a_rows,
                                        int64_t *b_rows, int64_t *keys_flipped,
                                        int64_t *rows_gathered,
                                        int64_t *rows_filtered);
+/* query 7 trace rows of the arg-max operator and its cumulative counters
+ * (as dbsp_argmax_stats); any out pointer may be null */
+dbsp_status dbsp_engine_argmax_stats(dbsp_engine *e, int64_t *in_rows,
+                                     int64_t *out_rows, int64_t *groups_seen,
+                                     int64_t *groups_refilled,
+                                     int64_t *rows_gathered);
 dbsp_status dbsp_engine_destroy(dbsp_engine *e);
 
 /* C5 (query 100) setup: device-generates the n_trace-row (k, f64-bits, +1)

@@ -11,6 +11,7 @@ Usage (on a GPU box):  python tools/kbench.py [--rows 500000000]
                        python tools/kbench.py --only rolling_minmax [--roll-rows N]
                        python tools/kbench.py --only topk [--topk-rows N ...]
                        python tools/kbench.py --only antijoin [--anti-rows N ...]
+                       python tools/kbench.py --only argmax [--argmax-rows N ...]
 Prints one JSON line per primitive.
 """
 import argparse
@@ -763,6 +764,129 @@ def bench_topk(ctx, L, n_trace, groups=1024, K=10, n_delta=40_000, ticks=12,
     }
 
 
+def bench_argmax(ctx, L, n_trace, groups=1024, n_delta=40_000, ticks=12,
+                 warm=2):
+    """Incremental arg-max per group (dbsp_argmax_step, group_shift 40,
+    rank_shift 0) on a trace of n_trace rows in `groups` groups: (a) an
+    append-only stream, on which no group's maximum ever decreases, (b) the
+    same stream with DBSP_ARGMAX_REFILL_ALL, (c) the recompute route: sort the
+    delta, merge it into ONE consolidated integral and run dbsp_argmax over
+    all of it (the diff against the previous result, which that route also
+    needs, is NOT included: a lower bound), (d) the append-only stream kept
+    out of group 0, which instead loses its top row every tick: one refill of
+    a group of n_trace / groups rows per tick.  Host clock around calls that
+    end in a stream synchronise; `warm` leading ticks are excluded."""
+    from dbsp_amd.engine import ArgMax
+    n_per = max(ticks + warm + 2, n_trace // groups)
+    n_trace = n_per * groups
+    tk = ((torch.arange(groups, dtype=torch.int64, device="cuda")
+           << TOPK_SHIFT).repeat_interleave(n_per)
+          | (2 * torch.arange(n_per, dtype=torch.int64,
+                              device="cuda")).repeat(groups))
+    tv = torch.zeros(n_trace, dtype=torch.int64, device="cuda")
+    tw = torch.ones(n_trace, dtype=torch.int64, device="cuda")
+    appends = _topk_stream(n_per, groups, n_delta, warm + ticks, 0.0, 23)
+    hot = []
+    for t, (k, v, w) in enumerate(appends):
+        keep = (k >> TOPK_SHIFT) != 0
+        top = torch.tensor([2 * (n_per - 1 - t)], dtype=torch.int64,
+                           device="cuda")
+        hot.append((torch.cat([k[keep], top]).contiguous(),
+                    torch.cat([v[keep], torch.zeros_like(top)]).contiguous(),
+                    torch.cat([w[keep], -torch.ones_like(top)]).contiguous()))
+    torch.cuda.synchronize()
+
+    def run_op(stream, refill_all):
+        op = ArgMax(ctx, TOPK_SHIFT, 0, refill_all=refill_all)
+        out = BatchStruct()
+        t0 = time.perf_counter()
+        assert L.dbsp_argmax_step(op._h, tk.data_ptr(), tv.data_ptr(),
+                                  tw.data_ptr(), n_trace,
+                                  ctypes.byref(out)) == 0
+        load_ms = (time.perf_counter() - t0) * 1e3
+        assert out.len == groups
+        ctx.free_batch(out)
+        ms, rows_out, refilled, gathered = [], [], [], []
+        prev = op.stats()
+        for i, (k, v, w) in enumerate(stream):
+            out = BatchStruct()
+            ctx.sync()
+            t0 = time.perf_counter()
+            assert L.dbsp_argmax_step(op._h, k.data_ptr(), v.data_ptr(),
+                                      w.data_ptr(), len(k),
+                                      ctypes.byref(out)) == 0
+            dt = (time.perf_counter() - t0) * 1e3
+            st = op.stats()
+            if i >= warm:
+                ms.append(dt)
+                rows_out.append(out.len)
+                refilled.append(st["groups_refilled"] - prev["groups_refilled"])
+                gathered.append(st["rows_gathered"] - prev["rows_gathered"])
+            prev = st
+            ctx.free_batch(out)
+        op.close()
+        return {"load_ms": round(load_ms, 2),
+                "ms_per_step": [round(x, 3) for x in ms],
+                "ms_median": round(_med(ms), 3),
+                "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+                "rows_out_per_tick": rows_out,
+                "groups_refilled_per_tick": refilled,
+                "rows_gathered_per_tick": gathered,
+                "in_rows": prev["in_rows"], "in_batches": prev["in_batches"],
+                "out_rows": prev["out_rows"],
+                "out_batches": prev["out_batches"]}
+
+    a = run_op(appends, False)
+    assert sum(a["groups_refilled_per_tick"]) == 0
+    assert sum(a["rows_gathered_per_tick"]) == 0
+    b = run_op(appends, True)
+    d = run_op(hot, False)
+    assert d["groups_refilled_per_tick"] == [1] * ticks
+
+    # ---- (c) recompute: consolidated integral + batch primitive ----
+    integral = as_batch(tk, tv, tw)
+    owned = False
+    full_ms = []
+    for i, (k, v, w) in enumerate(appends):
+        ctx.sync()
+        t0 = time.perf_counter()
+        dl = BatchStruct()
+        assert L.dbsp_sort_consolidate(ctx._h, k.data_ptr(), v.data_ptr(),
+                                       w.data_ptr(), len(k),
+                                       ctypes.byref(dl)) == 0
+        m = BatchStruct()
+        assert L.dbsp_merge(ctx._h, ctypes.byref(integral), ctypes.byref(dl),
+                            ctypes.byref(m)) == 0
+        res = BatchStruct()
+        assert L.dbsp_argmax(ctx._h, ctypes.byref(m), TOPK_SHIFT, 0,
+                             ctypes.byref(res)) == 0
+        ctx.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        if i >= warm:
+            full_ms.append(dt)
+        ctx.free_batch(dl)
+        ctx.free_batch(res)
+        if owned:
+            ctx.free_batch(integral)
+        integral, owned = m, True
+    if owned:
+        ctx.free_batch(integral)
+    return {
+        "primitive": "dbsp_argmax_step (incremental arg-max per group, ties "
+                     "kept) vs refill_all vs merge + dbsp_argmax over the "
+                     "trace",
+        "trace_rows": n_trace, "groups": groups, "group_rows": n_per,
+        "delta_rows": n_delta, "ticks": ticks, "warmup_ticks": warm,
+        "a_append_only": a, "b_append_only_refill_all": b,
+        "c_recompute_ms_per_step": [round(x, 3) for x in full_ms],
+        "c_recompute_ms_median": round(_med(full_ms), 3),
+        "c_recompute_ms_min": round(min(full_ms), 3),
+        "c_recompute_ms_max": round(max(full_ms), 3),
+        "c_recompute_excludes": "diff against the previous result",
+        "d_hot_group_refilled_every_tick": d,
+    }
+
+
 def bench_antijoin(ctx, L, n_trace, per_key=64, n_delta=40_000, n_flip=256,
                    ticks=12, warm=2):
     """Incremental antijoin (dbsp_antijoin_step) over a row trace of n_trace
@@ -906,7 +1030,10 @@ def main():
     ap.add_argument("--only", default=None,
                     choices=["merge", "join", "sort", "incremental", "c5",
                              "rolling", "rolling_wm", "rolling_minmax",
-                             "topk", "antijoin"])
+                             "topk", "antijoin", "argmax"])
+    ap.add_argument("--argmax-rows", type=int, nargs="*",
+                    default=[4_000_000, 16_000_000, 64_000_000],
+                    help="argmax leg: trace rows")
     ap.add_argument("--anti-rows", type=int, nargs="*",
                     default=[4_000_000, 16_000_000, 64_000_000],
                     help="antijoin leg: row-trace rows")
@@ -960,6 +1087,9 @@ def main():
     if args.only == "antijoin":         # on request only, as the rolling leg
         for n in args.anti_rows:
             print(json.dumps(bench_antijoin(ctx, L, n)), flush=True)
+    if args.only == "argmax":           # on request only, as the rolling leg
+        for n in args.argmax_rows:
+            print(json.dumps(bench_argmax(ctx, L, n)), flush=True)
     if args.only == "rolling_wm":       # on request only, as the rolling leg
         for res in bench_rolling_wm(ctx, L, args):
             print(json.dumps(res), flush=True)
